@@ -6,12 +6,17 @@ footprint — 147 materials, 3.4 GB of full-size BGRA8 textures, 16 distinct cut
 lite` is the cache-resident scene of rounds 1-4).
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+                    [--full] [--dump-outputs DIR]
+
+A plain N=1 run sets up, warms up, times the K steps, counts the rays of a few of those frames (the headline is rays per second) and
+prints the line.  --full adds the passes that `sustained`, `ms_per_frame_serial`, `roofline` and `cpu_baseline` come from.
+--dump-outputs DIR writes the result images of the last timed step (see dump_outputs).
 
 A step = one frame = Renderer::run's 12 dispatches (renderer.cpp:154-206) at the reference defaults
 (sample_example.hpp:154-184: maxDepth 4, temporal ReSTIR, M=4, MIS, denoise on) with a fresh RNG seed per frame.
 N>1 row-tiles the frame (restir_amd/tiled.py): total work is fixed => "strong" scaling.
 
-The JSON line carries
+The JSON line of a --full run also carries
   roofline      dominant kernel: algorithmic bytes per launch (screen traffic of SURVEY.md §8d + counted BVH8 node / triangle
                 / hit / RIS-candidate gathers x declared sizes) / its mean launch time from HIP events on the launch stream
   cpu_baseline  the CPU oracle (oracle/, "port") timed on a bounded band of the same frame on the host cores (N=1 only)
@@ -112,6 +117,23 @@ def texture_bytes(desc):
         return 0
     t = np.frombuffer((ctypes.c_char * (n * 32)).from_address(desc.textures), dtype=np.dtype([("ptr", "<u8"), ("w", "<i4"), ("h", "<i4"), ("rest", "<i4", 4)]))
     return int((t["w"].astype(np.int64) * t["h"] * 4).sum())
+
+
+DUMP_BYTES = 64 * 10 ** 6 - 4096      # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, images, seed=0):
+    """--dump-outputs DIR: the (H, W, 4) float32 images of the last timed step as DIR/<name>.npy.  When they hold more than DUMP_BYTES together (the two result
+    images of a 1080p frame do), every image is cut to the same fixed, seeded sample of pixels (rows of (n, 4), pixel order), so that two builds of the
+    project can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    h, w = next(iter(images.values())).shape[:2]
+    px_bytes = sum(a.nbytes for a in images.values()) // (h * w)
+    if px_bytes * h * w > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(h * w, DUMP_BYTES // px_bytes, replace=False))
+        images = {k: a.reshape(h * w, -1)[idx] for k, a in images.items()}
+    for k, a in images.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def pmc_entry(key, kname):
@@ -219,7 +241,13 @@ def main():
     ap.add_argument("--single-host", action="store_true", help="N > 1 without --native: time the RCCL host only (default: rank 0 then also runs the native host in a child process and "
                                                                 "reports both, the faster as `value`)")
     ap.add_argument("--print-workload-key", action="store_true", help="print the key of this workload in profiles/pmc_traffic.json and exit (scripts/pmc.sh)")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the timed steps also measure what the headline does not need — the sustained pass, the serial "
+                    "(one launch at a time) pass, the roofline of the dominant kernel with the VALU ceiling, and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="N = 1: write the images of the last timed step as DIR/<name>.npy (float32; a fixed, "
+                    "seeded sample of the pixels when the images exceed 64 MB in all)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_world > 1):
+        ap.error("--dump-outputs: single-GPU runs only (--gpus 1, no --emulate-world)")
     if args.print_workload_key:
         print(workload_key(args.config, args.moving_camera or CONFIGS[args.config].get("orbit", False), footprint_of(args), args.pose))
         return None
@@ -436,11 +464,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     timing = r.counters()
+    if args.dump_outputs:
+        # the images of the last timed step (frame f - 1), read back before anything else renders into them
+        cur = (f - 1) & 1
+        bufs = {"direct_result": abi.BUF_DIRECT_RESULT0 + cur}
+        if not di_only:
+            bufs["indirect_result"] = abi.BUF_INDIRECT_RESULT0 + cur
+        dump_outputs(args.dump_outputs, {k: r.readback(b).view(np.float32).reshape(H, W, 4) for k, b in bufs.items()})
 
     # a sustained pass of >= 1 s of back-to-back frames (the K timed steps above are what `value` reports; at the driver's K = 20 they
     # last 70 ms, too short for any sampling monitor to see the GPU busy): same frames-in-flight schedule, reported beside it
     sustained = None
-    if world == 1 and frame is None and not args.profile_run and not di_only:
+    if args.full and world == 1 and frame is None and not args.profile_run and not di_only:
         n_s = max(args.steps, int(1.0 / max(1e-4, elapsed / args.steps)) + 1)
         t1 = time.perf_counter()
         for _ in range(n_s):
@@ -483,8 +518,9 @@ def main():
                        "accel": r.accel_stats()},
         }
         out["timing_mode"] = ("ms_per_step = wall clock over K back-to-back frames with frames in flight (throughput; rt_set_overlap(2), the library default); "
-                              "ms_per_frame_serial = SURVEY 8(d)'s metric: sum of the frame's kernels, HIP events, every launch alone on one stream, "
-                              "median over the frames of a separate pass; frame_latency_ms = first launch to last launch of one frame while frames are in flight")
+                              + ("ms_per_frame_serial = SURVEY 8(d)'s metric: sum of the frame's kernels, HIP events, every launch alone on one stream, "
+                                 "median over the frames of a separate pass; " if args.full else "")
+                              + "frame_latency_ms = first launch to last launch of one frame while frames are in flight")
         if sustained:
             out["sustained"] = sustained
         if via is not None:
@@ -509,7 +545,7 @@ def main():
         if frame is not None:   # what rank 0 received for the last timed frame, by purpose (restir_amd/tiled.py accounting), and the exact fallbacks of the run
             out["halo_bytes_rank0"] = dict(frame.halo_bytes)
             out["history_fallbacks"] = int(frame.history_fallbacks)
-    if world == 1 and di_only and not args.profile_run:
+    if args.full and world == 1 and di_only and not args.profile_run:
         out["roofline"], out["cpu_baseline"] = di_only_roofline(r, abi, st, W, H, first_timed, n_count, elapsed / args.steps * 1e3), None
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(abi, host, scene, env, st, desc, W, H, first_timed, di_only=True)
@@ -526,7 +562,7 @@ def main():
         # so each launch is stretched while the frame rate goes up.  A short extra pass with every launch alone on one
         # stream gives the un-overlapped duration of the same kernels on the same frames.
         serial_ms = None
-        if frame is None and not di_only:
+        if args.full and frame is None and not di_only:
             r.set_overlap(0)
             for k in range(2):
                 step(first_timed + k)
@@ -544,6 +580,8 @@ def main():
             out["ms_per_frame_serial_frames"] = ns
             r.set_overlap(2 if os.environ.get("RESTIR_OVERLAP") is None else int(os.environ["RESTIR_OVERLAP"]))
         out["frame_latency_ms"] = round(frame_latency_ms, 4)
+    if args.full and world == 1 and timing.framesTimed > 0 and not args.profile_run and not di_only:
+        # (--full) the dominant kernel: its counts launched alone, the roofline with the VALU ceiling measured in this run, and the CPU baseline
         dom = int(np.argmax(stage_ms))
         launches = {0: 1, 1: 1, 2: 4, 3: 5, 4: 1}[dom]
         # counts of the dominant stage alone

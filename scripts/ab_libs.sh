@@ -3,7 +3,7 @@
 # prints pipelined ms/frame, serial sum and the serial stage times per variant
 for v in "$@"; do
   label="${v%%|*}"; envs="${v#*|}"
-  env $envs python bench.py --no-cpu-baseline > /tmp/ab_$$.json 2>/dev/null
+  env $envs python bench.py --full --no-cpu-baseline > /tmp/ab_$$.json 2>/dev/null
   python - "$label" /tmp/ab_$$.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

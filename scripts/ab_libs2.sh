@@ -10,7 +10,7 @@ for v in "$@"; do
   IFS='|' read -r label envs <<< "$v"
   [ "$envs" == "-" ] && envs="X_=1"
   envs="${envs//\$R/$R}"
-  env $envs timeout 900 python bench.py --no-cpu-baseline $BENCH_ARGS > $O/bench_${label}_$rep.json 2> $O/bench_${label}_$rep.err || { echo "$label: bench failed"; tail -3 $O/bench_${label}_$rep.err; continue; }
+  env $envs timeout 900 python bench.py --full --no-cpu-baseline $BENCH_ARGS > $O/bench_${label}_$rep.json 2> $O/bench_${label}_$rep.err || { echo "$label: bench failed"; tail -3 $O/bench_${label}_$rep.err; continue; }
   python - "$label" $O/bench_${label}_$rep.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

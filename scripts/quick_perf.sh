@@ -2,7 +2,7 @@
 # quick perf check of a build: bench line, stages on bands (throughput vs latency kernels), 8-rank emulation
 R=$GRAFT_REPO_ROOT; T=${1:-r03quick}; O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
-timeout 600 python bench.py --steps 60 --warmup 20 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python - $O/bench.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

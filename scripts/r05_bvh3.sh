@@ -7,7 +7,7 @@ one() { # kind footprint split rotate reinsert alpha
   export RESTIR_BVH_SPLIT=$3 RESTIR_BVH_ROTATE=$4 RESTIR_BVH_REINSERT=$5 RESTIR_BVH_SPLIT_ALPHA=$6
   echo "== $1 split=$3 rotate=$4 reinsert=$5 alpha=$6" | tee -a $O/ab.txt
   timeout 600 python scripts/bvh_ab.py $1 2>/dev/null | tail -1 | tee -a $O/ab.txt
-  timeout 600 python bench.py --scene-footprint $2 --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --scene-footprint $2 --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms  %.1f Mrays/s | serial sum %.4f | latency %.4f | serial stages %s' % (d['ms_per_step'], d['value'], d.get('ms_per_frame_serial', 0), d.get('frame_latency_ms', 0), r.get('serial', {}).get('stage_ms_per_frame')))
@@ -20,7 +20,7 @@ for c in 3 5; do
   for on in 0 1; do
     if [ $on == 0 ]; then export RESTIR_BVH_SPLIT=0 RESTIR_BVH_ROTATE=0 RESTIR_BVH_REINSERT=0; else export RESTIR_BVH_SPLIT=1 RESTIR_BVH_ROTATE=4 RESTIR_BVH_REINSERT=8; fi
     echo "== config $c quality passes $on" | tee -a $O/ab.txt
-    timeout 600 python bench.py --config $c --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --config $c --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms  %.1f Mrays/s | serial sum %.4f | accel %s' % (d['ms_per_step'], d['value'], d.get('ms_per_frame_serial', 0), d['config']['accel']))

@@ -7,7 +7,7 @@ one() { # label, env assignments...
   local label=$1; shift
   echo "== $label" | tee -a $O/ab.txt
   env "$@" timeout 600 python scripts/bvh_ab.py PROC_BISTRO_EXT_REAL 2>/dev/null | tail -1 | tee -a $O/ab.txt
-  env "$@" timeout 600 python bench.py --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+  env "$@" timeout 600 python bench.py --full --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms  %.1f Mrays/s | serial sum %.4f | latency %.4f | serial stages %s' % (d['ms_per_step'], d['value'], d.get('ms_per_frame_serial', 0), d.get('frame_latency_ms', 0), r.get('serial', {}).get('stage_ms_per_frame')))

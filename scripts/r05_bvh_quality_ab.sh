@@ -11,7 +11,7 @@ for kind in PROC_BISTRO_EXT_REAL PROC_BISTRO_EXT; do
     export RESTIR_BVH_SPLIT=$1 RESTIR_BVH_SPLIT_ALPHA=$2
     echo "== $kind split=$1 alpha=$2" | tee -a $O/ab.txt
     timeout 600 python scripts/bvh_ab.py $kind 2>/dev/null | tail -1 | tee -a $O/ab.txt
-    timeout 600 python bench.py --scene-footprint $fp --no-cpu-baseline 2>/dev/null | python -c "
+    timeout 600 python bench.py --full --scene-footprint $fp --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

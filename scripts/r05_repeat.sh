@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests/test_gpu_stream_prio.py tests/test_gpu_fullsize.py tests/test_gpu_bench_cli.py -x -q > $O/pytest.log 2>&1; tail -2 $O/pytest.log | head -1
 for k in 1 2 3; do
-  timeout 900 python bench.py > $O/bench_$k.json 2> $O/bench_$k.err
+  timeout 900 python bench.py --full > $O/bench_$k.json 2> $O/bench_$k.err
   python - $O/bench_$k.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); cb=d["cpu_baseline"]
@@ -13,7 +13,7 @@ print("bench", d["ms_per_step"], d["sustained"]["ms_per_frame"], d["stream_prior
 PY
 done
 for c in "--config 3" "--config 5" "--moving-camera" "--scene-footprint lite"; do
-  timeout 900 python bench.py --no-cpu-baseline $c 2>/dev/null | python -c "
+  timeout 900 python bench.py --full --no-cpu-baseline $c 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$c', d['ms_per_step'], d['sustained']['ms_per_frame'], d['stream_priorities'])
@@ -24,7 +24,7 @@ for kind in "PROC_BISTRO_EXT_REAL real" "PROC_BISTRO_EXT lite"; do
   for slots in greedy opt greedy opt; do
     echo "== $1 slots=$slots"
     RESTIR_BVH_SLOTS=$slots timeout 600 python scripts/bvh_ab.py $1 2>/dev/null | tail -1 | cut -c1-420
-    RESTIR_BVH_SLOTS=$slots timeout 600 python bench.py --scene-footprint $2 --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+    RESTIR_BVH_SLOTS=$slots timeout 600 python bench.py --full --scene-footprint $2 --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms | serial sum %.4f | serial stages %s' % (d['ms_per_step'], d.get('ms_per_frame_serial', 0), r.get('serial', {}).get('stage_ms_per_frame')))

@@ -19,7 +19,7 @@ grep -E "^== |rounds by|all waves|wave time" $O/wave_prof_lite.txt | tee -a $O/l
 for v in "PROC_BISTRO_EXT_REAL X_=1" "PROC_BISTRO_EXT_REAL RESTIR_SCENE_TEXSIZE=128" "PROC_BISTRO_EXT X_=1" "PROC_BISTRO_EXT_REAL RESTIR_DEBUG_OPAQUE_LEAVES=1"; do
   set -- $v
   env $2 timeout 600 python scripts/gpu_direct_breakdown.py $1 2>/dev/null | grep -E "PROC|mode 3 M 4|mode 0|debug view" | tee -a $O/direct_breakdown.txt
-  env $2 timeout 600 python bench.py --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+  env $2 timeout 600 python bench.py --full --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms | serial sum %.4f | serial stages %s | texels %d MB' % (d['ms_per_step'], d.get('ms_per_frame_serial', 0), r.get('serial', {}).get('stage_ms_per_frame'), d['config']['texture_bytes'] // 1000000))
@@ -30,7 +30,7 @@ for setting in "0 0 1e-5" "0 4 1e-5" "1 0 1e-5" "1 4 1e-5" "1 4 1e-4"; do
   export RESTIR_BVH_SPLIT=$1 RESTIR_BVH_ROTATE=$2 RESTIR_BVH_SPLIT_ALPHA=$3
   echo "== real split=$1 rotate=$2 alpha=$3" | tee -a $O/bvh2.txt
   timeout 600 python scripts/bvh_ab.py PROC_BISTRO_EXT_REAL 2>/dev/null | tail -1 | tee -a $O/bvh2.txt
-  timeout 600 python bench.py --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --stream-priorities default 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('   frame in flight %.4f ms  %.1f Mrays/s | serial sum %.4f | latency %.4f | serial stages %s' % (d['ms_per_step'], d['value'], d.get('ms_per_frame_serial', 0), d.get('frame_latency_ms', 0), r.get('serial', {}).get('stage_ms_per_frame')))

@@ -7,7 +7,7 @@ cd $R
 for w in "real --scene-footprint real" "lite --scene-footprint lite" "config3 --config 3" "config5 --config 5" "moving --moving-camera"; do
   set -- $w; name=$1; shift
   for on in 0 1 0 1; do
-    RESTIR_ROW_ORDER=$on timeout 600 python bench.py --no-cpu-baseline --stream-priorities default "$@" 2>/dev/null | python -c "
+    RESTIR_ROW_ORDER=$on timeout 600 python bench.py --full --no-cpu-baseline --stream-priorities default "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('$name row_order=$on  frame in flight %.4f ms | serial sum %.4f | latency %.4f | serial stages %s' % (d['ms_per_step'], d.get('ms_per_frame_serial', 0), d.get('frame_latency_ms', 0), r.get('serial', {}).get('stage_ms_per_frame')))

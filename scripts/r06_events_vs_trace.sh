@@ -12,5 +12,5 @@ last = rows[-100:]
 print("under rocprof: ms/frame", d["ms_per_step"], "| events", d["events_in_this_run"]["stage_ms_per_frame"], "| kernel stats", [(r["Name"].split("::")[2].split("(")[0], r["Calls"], round(float(r["AverageNs"]) / 1e6, 4)) for r in k], "| trace, the 100 timed launches of k_direct_stage: %.4f ms" % (sum(e - s for s, e in last) / len(last) / 1e6))
 PY
 done
-cd $R; timeout 600 python bench.py --no-cpu-baseline > $O/bench_plain.json 2>/dev/null; python -c "
+cd $R; timeout 600 python bench.py --full --no-cpu-baseline > $O/bench_plain.json 2>/dev/null; python -c "
 import json; d=json.loads(open('$O/bench_plain.json').read().strip().splitlines()[-1]); print('plain run: ms/frame', d['ms_per_step'], 'events', d['roofline']['stage_ms_per_frame'])"

@@ -11,14 +11,14 @@ bash scripts/final_measure.sh $TAG > $O/final_measure.log 2>&1; tail -12 $O/fina
 for p in 1 2; do
   bash scripts/pmc.sh $TAG/pmc_pose$p auto --pose $p > $O/pmc_pose$p.log 2>&1
   cp profiles/pmc_traffic.json $O/pmc_traffic.json
-  timeout 900 python bench.py --pose $p > $O/bench_pose$p.json 2> $O/bench_pose$p.err
+  timeout 900 python bench.py --full --pose $p > $O/bench_pose$p.json 2> $O/bench_pose$p.err
   python - $O/bench_pose$p.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]
 print(sys.argv[1].split("/")[-1], d["ms_per_step"], d["value"], "bound", r.get("bound"), "alg", r.get("frac_algorithmic"), "hbm", r.get("frac_hbm_counter"), "valu", r.get("frac_valu"), d.get("stream_priorities"))
 PY
 done
-RESTIR_BVH_TIMING=1 timeout 1500 python bench.py --via-gltf --no-cpu-baseline > $O/bench_via_gltf.json 2> $O/bench_via_gltf.err
+RESTIR_BVH_TIMING=1 timeout 1500 python bench.py --full --via-gltf --no-cpu-baseline > $O/bench_via_gltf.json 2> $O/bench_via_gltf.err
 python -c "
 import json; d=json.loads(open('$O/bench_via_gltf.json').read().strip().splitlines()[-1]); v=d['via_gltf']; print('via gltf', d['ms_per_step'], {k: v[k] for k in ('files','bytes_on_disk','save_s','load_s','peak_rss_gb_after_load','scene_digest_equal','frames_equal')})"
 grep "scene load\|bvh8 build" $O/bench_via_gltf.err | head -30

@@ -6,7 +6,7 @@ bash scripts/r06_build_profile.sh $T/build 2>&1 | grep "==\|sequential\|BVH2\|lo
 echo "== RESTIR_CPUS=32"; RESTIR_CPUS=32 python gpurun_out/r06t/build/one.py renderer 2>&1 | grep "sequential\|BVH2\|load_scene" | cut -c1-200
 echo "== RESTIR_CPUS=64"; RESTIR_CPUS=64 python gpurun_out/r06t/build/one.py renderer 2>&1 | grep "sequential\|BVH2\|load_scene" | cut -c1-200
 timeout 800 python scripts/r06_oracle_scaling.py 2>&1 | grep threads | cut -c1-520
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; python - $O/bench.json <<'PY'
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; python - $O/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); c = d["cpu_baseline"]
 print("bench", d["ms_per_step"], d["value"], "bvh8_build_s", d["config"].get("bvh8_build_s"), "| cpu", {k: c[k] for k in ("value", "cores", "host_cpus", "cpu_quota", "threads_used", "cpus_busy", "per_core", "single_thread", "pinned")})

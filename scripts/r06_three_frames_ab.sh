@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd $R
 line() {  # label, env, bench args
   local label="$1" envs="$2"; shift; shift
-  env $envs timeout 600 python bench.py --no-cpu-baseline "$@" > $O/cell.json 2> $O/cell.err
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline "$@" > $O/cell.json 2> $O/cell.err
   python - "$label" $O/cell.json <<'PY'
 import json, sys
 try:

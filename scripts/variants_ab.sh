@@ -11,7 +11,7 @@ done
 if [ -n "$BENCH" ]; then
 for v in "$@"; do
   if [ "$v" == "product" ]; then unset RESTIR_HIP_LIB; else export RESTIR_HIP_LIB=$R/cis-565-final-vr-raytracer_amd/csrc/_ab/librestir_hip_$v.so; fi
-  timeout 600 python bench.py --steps 60 --warmup 20 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
+  timeout 600 python bench.py --full --steps 60 --warmup 20 --no-cpu-baseline > $O/bench_$v.json 2> $O/bench_$v.err
   python - $O/bench_$v.json $v <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

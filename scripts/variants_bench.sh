@@ -14,7 +14,7 @@ for v in "$@"; do
     export RESTIR_HIP_LIB=$R/cis-565-final-vr-raytracer_amd/csrc/_ab/librestir_hip_$label.so
   fi
   [ "$envs" == "-" ] && envs="X_=1"
-  env $envs timeout 900 python bench.py --no-cpu-baseline ${CFG:+--config $CFG} $BENCH_ARGS > $O/bench_$label.json 2> $O/bench_$label.err || { echo "$label: bench failed"; tail -3 $O/bench_$label.err; continue; }
+  env $envs timeout 900 python bench.py --full --no-cpu-baseline ${CFG:+--config $CFG} $BENCH_ARGS > $O/bench_$label.json 2> $O/bench_$label.err || { echo "$label: bench failed"; tail -3 $O/bench_$label.err; continue; }
   python - "$label" $O/bench_$label.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -6,10 +6,12 @@ shade_state.glsl, gltf_material.glsl, pbr_metallicworkflow.glsl, reservoir.glsl,
 as written, over a ray-query stand-in), sun_and_sky.glsl, compress.glsl, random.glsl, common.glsl, denoise_common.glsl — from where
 they lie under /root/reference into oracle/_ref/libref_stages.so (authoring container only).  Two kinds of tests:
 
-  * live (skipped where the library is absent, i.e. away from the authoring container): the oracle and the compiled reference
-    render the same seeded frames; EVERY screen-space buffer must agree bit for bit — G-buffer words, motion vectors, direct and
-    indirect reservoirs, both result images and the four filter temporaries — over scenes, RtxState variants, camera motion,
-    HDR / sun & sky / no environment, the 2-pass direct_gen + direct_reuse split and the glTF file scene.
+  * live: the oracle and the compiled reference render the same seeded frames; EVERY screen-space buffer must agree bit for bit —
+    G-buffer words, motion vectors, direct and indirect reservoirs, both result images and the four filter temporaries — over
+    scenes, RtxState variants, camera motion, HDR / sun & sky / no environment, the 2-pass direct_gen + direct_reuse split and
+    the glTF file scene.  Where the library is absent (away from the authoring container) the oracle's buffers are held to the
+    SHA-256 of the reference's, stored in tests/golden/ref_live_digests.json (minted by tests/golden/make_ref_live_digests.py);
+    where it is present, the stored digests are checked against it too.
   * travelling: tests/golden/ref_stage_vectors.npz holds the per-pixel output of the compiled reference for small seeded frames
     (minted by tests/golden/make_ref_stage_vectors.py); the oracle must reproduce them bit for bit on any machine, and
     tests/test_gpu_ref_vectors.py holds the HIP path to the same file.
@@ -21,6 +23,8 @@ ray/triangle arithmetic and hit order, instance inverse transforms, texture filt
 HitTest's per-candidate seed follows deviation 1 on both sides; ReSTIRState spatial / spatiotemporal (the reference's
 in-dispatch neighbour exchange races by construction, deviation 4).
 """
+import hashlib
+import json
 import os
 import numpy as np
 import pytest
@@ -30,6 +34,7 @@ from oracle.binding import Oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 VECTORS = os.path.join(HERE, "golden", "ref_stage_vectors.npz")
+LIVE_DIGESTS = os.path.join(HERE, "golden", "ref_live_digests.json")
 
 
 def all_buffers(f):
@@ -64,24 +69,13 @@ def drive(backends, sc, st, W, H, nframes, moving=False, stages=None, each_frame
             each_frame(f)
 
 
-def _live_pair(sc, env, W, H, sky=None):
-    desc = sc.desc(env)
-    o = Oracle(0); o.upload_scene(desc); o.resize(W, H)
-    r = ref_binding.Reference(); r.upload_scene(desc); r.resize(W, H)
-    if sky is not None:
-        o.set_sun_and_sky(sky); r.set_sun_and_sky(sky)
-    return o, r
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).view(np.uint8).tobytes()).hexdigest()
 
 
-def _assert_equal_frames(o, r, sc, st, W, H, nframes, moving, stages=None):
-    seen = {"lit": False}
-    def check(f):
-        bad = {k: v for k, v in compare_buffers(o, r, all_buffers(f)).items() if v[0]}
-        assert not bad, f"frame {f}: oracle differs from the compiled reference in {bad}"
-        img = r.readback(abi.BUF_DIRECT_RESULT0 + (f & 1)).view(np.float32)
-        seen["lit"] |= bool(np.isfinite(img).all() and img.max() > 0.01)
-    drive([o, r], sc, st, W, H, nframes, moving, stages, check)
-    assert seen["lit"], "two empty frames compare equal trivially"
+def frame_digests(backend, f):
+    """{buffer name: SHA-256 of its bytes} of every screen-space buffer of frame f"""
+    return {abi.BUFFER_NAMES[buf]: _sha(backend.readback(buf)) for buf in all_buffers(f)}
 
 
 needs_ref = pytest.mark.skipif(not ref_binding.available(), reason="oracle/_ref/libref_stages.so is built only where /root/reference exists")
@@ -96,67 +90,106 @@ LIVE_CASES = [
     ("bistro-int", abi.PROC_BISTRO_INT, 0.003, 64, 40, 3, None, True),        # many emissive triangles, punctual lights, no env
 ]
 
-
-@needs_ref
-@pytest.mark.parametrize("name,kind,scale,W,H,frames,env_size,moving", LIVE_CASES, ids=[c[0] for c in LIVE_CASES])
-def test_oracle_equals_compiled_reference(name, kind, scale, W, H, frames, env_size, moving):
-    sc, env = make_scene(kind, scale, 1, env_size)
-    st = host.default_state(W, H, sc, env)
-    if env is None:
-        st.environmentProb = 0.0; st.fireflyClampThreshold = 100.0
-    o, r = _live_pair(sc, env, W, H)
-    _assert_equal_frames(o, r, sc, st, W, H, frames, moving)
-
-
 VARIANTS = ["restir_none", "ris_only", "no_denoise", "no_modulate", "no_mis_depth2", "depth6", "m16_clamp4", "gen_reuse_split", "env_only", "no_env",
             "firefly_tight"] + [f"debug_{m}" for m in range(1, 10)]
 
+# every live case by key: `live/<name>` (LIVE_CASES), `variant/<name>` (VARIANTS), `sun_and_sky`, `gltf_file`
+LIVE_KEYS = [f"live/{c[0]}" for c in LIVE_CASES] + [f"variant/{v}" for v in VARIANTS] + ["sun_and_sky", "gltf_file"]
 
-@needs_ref
+
+def live_case(key):
+    """(scene, env, state, W, H, frames, moving camera, stages or None, sun & sky or None) of a live case"""
+    stages, sky = None, None
+    if key.startswith("live/"):
+        name, kind, scale, W, H, frames, env_size, moving = next(c for c in LIVE_CASES if c[0] == key[5:])
+        sc, env = make_scene(kind, scale, 1, env_size)
+        st = host.default_state(W, H, sc, env)
+        if env is None:
+            st.environmentProb = 0.0; st.fireflyClampThreshold = 100.0
+        return sc, env, st, W, H, frames, moving, stages, sky
+    W, H, frames, moving = 64, 40, 3, True
+    if key.startswith("variant/"):
+        variant = key[8:]
+        sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, (128, 64))
+        st = host.default_state(W, H, sc, env)
+        if variant == "restir_none": st.ReSTIRState = abi.RESTIR_NONE
+        if variant == "ris_only": st.ReSTIRState = abi.RESTIR_RIS
+        if variant == "no_denoise": st.denoise = 0
+        if variant == "no_modulate": st.modulate = 0
+        if variant == "no_mis_depth2": st.MIS = 0; st.maxDepth = 2
+        if variant == "depth6": st.maxDepth = 6
+        if variant == "m16_clamp4": st.RISSampleNum = 16; st.reservoirClamp = 4
+        if variant == "gen_reuse_split": stages = SPLIT
+        if variant == "env_only": st.environmentProb = 1.0
+        if variant == "no_env": st.environmentProb = 0.0
+        if variant == "firefly_tight": st.fireflyClampThreshold = 0.5
+        if variant.startswith("debug_"): st.debugging_mode = int(variant.split("_")[1])
+    elif key == "sun_and_sky":
+        sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, None)
+        st = host.default_state(W, H, sc, None)
+        st.environmentProb = 0.5
+        sky = abi.SunAndSky(in_use=1, haze=0.5, sun_disk_scale=3.0, physically_scaled_sun=0, multiplier=0.02)
+    elif key == "gltf_file":
+        W, H = 80, 48
+        sc = host.Scene()
+        assert sc.load(os.path.join(HERE, "golden", "mini_scene.gltf"))
+        env = host.HdrSampling(); env.makeSyntheticSky(64, 32, 5e3, 7)
+        st = host.default_state(W, H, sc, env)
+    else:
+        raise KeyError(key)
+    return sc, env, st, W, H, frames, moving, stages, sky
+
+
+def make_backend(cls, sc, env, W, H, sky):
+    b = cls(); b.upload_scene(sc.desc(env)); b.resize(W, H)
+    if sky is not None:
+        b.set_sun_and_sky(sky)
+    return b
+
+
+def check_live_case(key):
+    """The oracle against the compiled reference when it is built here (every buffer of every frame, word for word, and the stored digests against
+    the reference); elsewhere against the reference's stored digests (tests/golden/ref_live_digests.json): bit for bit either way."""
+    sc, env, st, W, H, frames, moving, stages, sky = live_case(key)
+    with open(LIVE_DIGESTS) as fh:
+        want = json.load(fh)[key]
+    assert set(want) == {f"f{f}" for f in range(frames)}, f"{key}: tests/golden/ref_live_digests.json does not cover the case's frames"
+    o = make_backend(Oracle, sc, env, W, H, sky)
+    r = make_backend(ref_binding.Reference, sc, env, W, H, sky) if ref_binding.available() else None
+    seen = {"lit": False}
+    def check(f):
+        if r is not None:
+            bad = {k: v for k, v in compare_buffers(o, r, all_buffers(f)).items() if v[0]}
+            assert not bad, f"frame {f}: oracle differs from the compiled reference in {bad}"
+            stale = [k for k, d in frame_digests(r, f).items() if d != want[f"f{f}"][k]]
+            assert not stale, f"{key} frame {f}: tests/golden/ref_live_digests.json is stale in {stale} (tests/golden/make_ref_live_digests.py)"
+        else:
+            bad = [k for k, d in frame_digests(o, f).items() if d != want[f"f{f}"][k]]
+            assert not bad, f"{key} frame {f}: oracle differs from the compiled reference's stored output in {bad}"
+        img = o.readback(abi.BUF_DIRECT_RESULT0 + (f & 1)).view(np.float32)
+        seen["lit"] |= bool(np.isfinite(img).all() and img.max() > 0.01)
+    drive([o] + ([r] if r is not None else []), sc, st, W, H, frames, moving, stages, check)
+    assert seen["lit"], "two empty frames compare equal trivially"
+
+
+@pytest.mark.parametrize("name,kind,scale,W,H,frames,env_size,moving", LIVE_CASES, ids=[c[0] for c in LIVE_CASES])
+def test_oracle_equals_compiled_reference(name, kind, scale, W, H, frames, env_size, moving):
+    check_live_case(f"live/{name}")
+
+
 @pytest.mark.parametrize("variant", VARIANTS)
 def test_state_variants_equal_compiled_reference(variant):
-    W, H = 64, 40
-    sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, (128, 64))
-    st = host.default_state(W, H, sc, env)
-    stages = None
-    if variant == "restir_none": st.ReSTIRState = abi.RESTIR_NONE
-    if variant == "ris_only": st.ReSTIRState = abi.RESTIR_RIS
-    if variant == "no_denoise": st.denoise = 0
-    if variant == "no_modulate": st.modulate = 0
-    if variant == "no_mis_depth2": st.MIS = 0; st.maxDepth = 2
-    if variant == "depth6": st.maxDepth = 6
-    if variant == "m16_clamp4": st.RISSampleNum = 16; st.reservoirClamp = 4
-    if variant == "gen_reuse_split": stages = SPLIT
-    if variant == "env_only": st.environmentProb = 1.0
-    if variant == "no_env": st.environmentProb = 0.0
-    if variant == "firefly_tight": st.fireflyClampThreshold = 0.5
-    if variant.startswith("debug_"): st.debugging_mode = int(variant.split("_")[1])
-    o, r = _live_pair(sc, env, W, H)
-    _assert_equal_frames(o, r, sc, st, W, H, 3, True, stages)
+    check_live_case(f"variant/{variant}")
 
 
-@needs_ref
 def test_sun_and_sky_equals_compiled_reference():
     """`_sunAndSky.in_use = 1`: EnvRadiance / EnvSample / EnvEval through the reference's sun_and_sky.glsl as compiled"""
-    W, H = 64, 40
-    sc, _ = make_scene(abi.PROC_SPONZA, 0.01, 1, None)
-    st = host.default_state(W, H, sc, None)
-    st.environmentProb = 0.5
-    sky = abi.SunAndSky(in_use=1, haze=0.5, sun_disk_scale=3.0, physically_scaled_sun=0, multiplier=0.02)
-    o, r = _live_pair(sc, None, W, H, sky)
-    _assert_equal_frames(o, r, sc, st, W, H, 3, True)
+    check_live_case("sun_and_sky")
 
 
-@needs_ref
 def test_gltf_file_scene_equals_compiled_reference():
     """Scene::load path: TRS hierarchy, nearest / clamp / mirror samplers, MASK material, transmission + ior, spot light"""
-    W, H = 80, 48
-    sc = host.Scene()
-    assert sc.load(os.path.join(HERE, "golden", "mini_scene.gltf"))
-    env = host.HdrSampling(); env.makeSyntheticSky(64, 32, 5e3, 7)
-    st = host.default_state(W, H, sc, env)
-    o, r = _live_pair(sc, env, W, H)
-    _assert_equal_frames(o, r, sc, st, W, H, 3, True)
+    check_live_case("gltf_file")
 
 
 # ---- travelling vectors ------------------------------------------------------------------------------------------------------
