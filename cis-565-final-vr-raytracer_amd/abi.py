@@ -84,6 +84,8 @@ assert C.sizeof(SceneCamera) == 336 and C.sizeof(RtxState) == 100
 BUFFER_NAMES = ["gbuffer0", "gbuffer1", "motion", "direct_resv0", "direct_resv1", "direct_resv_temp", "indirect_resv0", "indirect_resv1",
                 "indirect_resv_temp", "denoise_dir_a", "denoise_dir_b", "denoise_ind_a", "denoise_ind_b", "direct_result0", "direct_result1",
                 "indirect_result0", "indirect_result1", "light_id0", "light_id1", "ldr"]
+# rt_reference_readback components
+REF_DIRECT, REF_INDIRECT, REF_SUM = range(3)
 # rt_stage_id
 (STAGE_DIRECT, STAGE_INDIRECT, STAGE_DENOISE_DIRECT, STAGE_DENOISE_INDIRECT, STAGE_COMPOSE, STAGE_DIRECT_GEN, STAGE_DIRECT_REUSE) = range(7)
 # rt_restir_state

@@ -20,6 +20,7 @@
 #include "../../include/rt_cpus.h"
 #include "bvh8_builder.h"
 #include "stages.h"
+#include "reference.h"
 
 using namespace rt;
 
@@ -88,6 +89,12 @@ struct rt_ctx {
   std::vector<EvSet> evSets;
   size_t evUsed = 0;
   double accStage[RT_STAGE_COUNT] = {}; double accFrame = 0; uint32_t accFrames = 0;
+  // rt_reference_* (progressive ground-truth path tracer, csrc/reference.hip): allocated by the first rt_reference_render, freed by rt_resize / rt_destroy
+  double* refAcc = nullptr;    // W x H x 6 fp64 sums (direct rgb, indirect rgb)
+  float4* refMean = nullptr;   // W x H x 2 RGBA32F: the means rt_reference_readback / rt_reference_tonemap read
+  uint32_t refN = 0;           // samples in refAcc; 0 = the sums are stale and are cleared by the next rt_reference_render
+  bool refKeyValid = false;    // the RtxState inputs of the integral the sums were taken with (the others reset refN where they change)
+  int32_t refMaxDepth = 0, refMIS = 0; float refHdrMultiplier = 0.f, refEnvironmentProb = 0.f;
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -403,6 +410,8 @@ int rt_destroy(rt_ctx* c)
   if(c->dCounters) (void)hipFree(c->dCounters);
   if(c->dSky) (void)hipFree(c->dSky);
   if(c->dPick) (void)hipFree(c->dPick);
+  if(c->refAcc) (void)hipFree(c->refAcc);
+  if(c->refMean) (void)hipFree(c->refMean);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
@@ -469,6 +478,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   LoadTimer lt;
   freePool(c->sceneAllocs); freePool(c->accelAllocs);
   c->haveScene = c->haveAccel = false;
+  c->refN = 0;   // a new scene: the reference sums start again
   c->ds = DevScene{};
   c->ds.sky = (c->sunAndSky.in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
   c->primMeshes.assign(d->primMeshes, d->primMeshes + d->numPrimMeshes);
@@ -658,6 +668,7 @@ int rt_build_accel(rt_ctx* c)
   RT_HIP(c, syncAll(c));
   freePool(c->accelAllocs);
   c->haveAccel = false;
+  c->refN = 0;
   // Host products (BVH8, alpha records, opacity micro-maps): built once per distinct scene in this process and shared by every context that uploads
   // the same scene — the N ranks of an rt_mgpu context, or an application's contexts on several devices (1.4-1.6 s per build at 2.8 M triangles).
   std::shared_ptr<const HostAccel> ha;
@@ -721,6 +732,8 @@ int rt_resize(rt_ctx* c, int w, int h)
   for(int i = 0; i < RT_BUF_COUNT; i++) { if(c->bufs[i]) (void)hipFree(c->bufs[i]); c->bufs[i] = nullptr; c->bufBytes[i] = 0; }
   for(void** p : {&c->spareG, &c->spareMotion, &c->spareG2, &c->spareMotion2, &c->spareDirRes}) if(*p) { (void)hipFree(*p); *p = nullptr; }
   c->W = c->H = 0;
+  for(void* p : {static_cast<void*>(c->refAcc), static_cast<void*>(c->refMean)}) if(p) (void)hipFree(p);
+  c->refAcc = nullptr; c->refMean = nullptr; c->refN = 0;
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -794,6 +807,8 @@ static int ensureStackOverflow(rt_ctx* c)
 int rt_set_camera(rt_ctx* c, const rt_scene_camera* cam)
 {
   if(!c || !cam) return RT_ERR_INVALID_ARG;
+  // the reference sums belong to one view: a new viewInverse / projInverse resets them (the history matrices move every frame and do not)
+  if(std::memcmp(&c->cam.viewInverse, &cam->viewInverse, sizeof(rt_mat4)) != 0 || std::memcmp(&c->cam.projInverse, &cam->projInverse, sizeof(rt_mat4)) != 0) c->refN = 0;
   c->cam = *cam;
   return RT_OK;
 }
@@ -1213,6 +1228,7 @@ int rt_set_sun_and_sky(rt_ctx* c, const rt_sun_and_sky* ss)
     RT_HIP(c, hipStreamSynchronize(c->stream));
   }
   c->ds.sky = (ss->in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
+  c->refN = 0;
   return RT_OK;
 }
 
@@ -1225,6 +1241,96 @@ int rt_tonemap(rt_ctx* c, const rt_tonemapper* tm, int debugging_mode, int frame
   const int cur = frames & 1;
   RT_HIP(c, launchTonemap(c->stream, static_cast<const float4*>(c->bufs[RT_BUF_DIRECT_RESULT0 + cur]), static_cast<const float4*>(c->bufs[RT_BUF_INDIRECT_RESULT0 + cur]),
                           c->scratch.postRowSums, c->scratch.postMean, *tm, debugging_mode, c->W, c->H, static_cast<uint32_t*>(c->bufs[RT_BUF_LDR]),
+                          c->scratch.postMipD, c->scratch.postMipI));
+  return RT_OK;
+}
+
+// ---- rt_reference_*: the progressive ground-truth path tracer (csrc/reference.hip).  Main stream only, after the frames in flight; it reads the scene, the
+// camera and the RtxState it is given and touches no frame buffer, counter, stream decision or rotation of the real-time path.
+static int ensureReferenceBuffers(rt_ctx* c)
+{
+  if(c->refAcc) return RT_OK;
+  const size_t n = size_t(c->W) * size_t(c->H);
+  RT_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->refAcc), n * REF_ACC_DOUBLES * sizeof(double)));
+  if(hipMalloc(reinterpret_cast<void**>(&c->refMean), n * 2 * sizeof(float4)) != hipSuccess) {
+    (void)hipFree(c->refAcc); c->refAcc = nullptr;
+    return fail(c, RT_ERR_OOM, "rt_reference_render: hipMalloc of the reference accumulators failed");
+  }
+  c->refN = 0;
+  return RT_OK;
+}
+
+int rt_reference_render(rt_ctx* c, const rt_state* st, int samples)
+{
+  int rc = checkReady(c, st);
+  if(rc) return rc;
+  if(samples < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_reference_render: samples must be >= 0");
+  if(st->debugging_mode != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_reference_render: debugging_mode must be 0 (the reference mode has no debug views)");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, joinInFlight(c));
+  if((rc = ensureReferenceBuffers(c))) return rc;
+  // the RtxState inputs of the integral; the other inputs (size, scene, tree, sun & sky, view) reset refN where they change
+  const bool same = c->refKeyValid && st->maxDepth == c->refMaxDepth && st->MIS == c->refMIS &&
+                    std::memcmp(&st->hdrMultiplier, &c->refHdrMultiplier, sizeof(float)) == 0 && std::memcmp(&st->environmentProb, &c->refEnvironmentProb, sizeof(float)) == 0;
+  if(!same) c->refN = 0;
+  c->refKeyValid = true; c->refMaxDepth = st->maxDepth; c->refMIS = st->MIS; c->refHdrMultiplier = st->hdrMultiplier; c->refEnvironmentProb = st->environmentProb;
+  if(samples == 0) return RT_OK;
+  if(uint64_t(c->refN) + uint64_t(samples) > 0xffffffffull) return fail(c, RT_ERR_INVALID_ARG, "rt_reference_render: more than 2^32 - 1 samples");
+  if(c->refN == 0) RT_HIP(c, hipMemsetAsync(c->refAcc, 0, size_t(c->W) * size_t(c->H) * REF_ACC_DOUBLES * sizeof(double), c->stream));
+  const auto launch = c->ds.sky ? rt::ref_sky::launchReference : rt::ref_base::launchReference;
+  const int band = std::max(8, (REF_BAND_PIXELS / c->W) & ~7);   // rows per launch: no launch longer than a frame's stages on the largest scenes
+  for(int s = 0; s < samples; s++)
+    for(int r0 = 0; r0 < c->H; r0 += band) RT_HIP(c, launch(c->stream, c->ds, *st, c->cam, c->refAcc, c->refN + uint32_t(s), r0, std::min(c->H, r0 + band)));
+  c->refN += uint32_t(samples);
+  return RT_OK;
+}
+
+int rt_reference_reset(rt_ctx* c)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  c->refN = 0;
+  return RT_OK;
+}
+
+int rt_reference_samples(rt_ctx* c, uint32_t* n)
+{
+  if(!c || !n) return RT_ERR_INVALID_ARG;
+  *n = c->refN;
+  return RT_OK;
+}
+
+int rt_reference_readback(rt_ctx* c, int component, float* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(component < 0 || component > 2) return fail(c, RT_ERR_INVALID_ARG, "rt_reference_readback: component must be 0 (direct), 1 (indirect) or 2 (sum)");
+  if(c->W == 0) return fail(c, RT_ERR_NO_TARGET, "rt_reference_readback: rt_resize has not been called");
+  const size_t n = size_t(c->W) * size_t(c->H);
+  if(bytes != n * sizeof(float4)) return fail(c, RT_ERR_INVALID_ARG, "rt_reference_readback: size mismatch (W * H * 16 bytes, RGBA32F)");
+  if(c->refN == 0 || !c->refAcc) {   // nothing accumulated: the mean of no samples is 0
+    for(size_t i = 0; i < n; i++) { dst[4 * i] = dst[4 * i + 1] = dst[4 * i + 2] = 0.f; dst[4 * i + 3] = 1.f; }
+    return RT_OK;
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, joinInFlight(c));
+  RT_HIP(c, launchReferenceMean(c->stream, c->refAcc, c->refN, component, n, c->refMean));
+  RT_HIP(c, hipMemcpyAsync(dst, c->refMean, bytes, hipMemcpyDeviceToHost, c->stream));
+  RT_HIP(c, hipStreamSynchronize(c->stream));
+  return RT_OK;
+}
+
+int rt_reference_tonemap(rt_ctx* c, const rt_tonemapper* tm)
+{
+  if(!c || !tm) return RT_ERR_INVALID_ARG;
+  if(c->W == 0) return fail(c, RT_ERR_NO_TARGET, "rt_reference_tonemap: rt_resize has not been called");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, joinInFlight(c));
+  int rc;
+  if((rc = ensureReferenceBuffers(c))) return rc;
+  const size_t n = size_t(c->W) * size_t(c->H);
+  RT_HIP(c, launchReferenceMean(c->stream, c->refAcc, c->refN, 0, n, c->refMean));
+  RT_HIP(c, launchReferenceMean(c->stream, c->refAcc, c->refN, 1, n, c->refMean + n));
+  // post.frag over the two means in place of the two result images (rt_tonemap's pass, default view)
+  RT_HIP(c, launchTonemap(c->stream, c->refMean, c->refMean + n, c->scratch.postRowSums, c->scratch.postMean, *tm, 0, c->W, c->H, static_cast<uint32_t*>(c->bufs[RT_BUF_LDR]),
                           c->scratch.postMipD, c->scratch.postMipI));
   return RT_OK;
 }

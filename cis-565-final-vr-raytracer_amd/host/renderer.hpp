@@ -65,6 +65,27 @@ class Renderer {
     return rt_readback(m_ctx, RT_BUF_DIRECT_RESULT0 + (frames & 1), direct.data(), n * sizeof(float)) == RT_OK
            && rt_readback(m_ctx, RT_BUF_INDIRECT_RESULT0 + (frames & 1), indirect.data(), n * sizeof(float)) == RT_OK;
   }
+  // Reference mode (include/rt_abi.h, ABI 2.4): the progressive ground-truth path tracer the reference left as RtxState.accumulate / frame +
+  // SampleExample::updateFrame's m_maxFrames (sample_example.cpp:176-204).  Adds `samples` samples per pixel; the sums reset by themselves when
+  // the view, the size, the scene, the sun & sky or maxDepth / hdrMultiplier / environmentProb / MIS change.
+  bool referenceRender(const rt_state& state, int samples)
+  {
+    if(rt_reference_render(m_ctx, &state, samples) != RT_OK) { fprintf(stderr, "Renderer::referenceRender: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  void referenceReset() { rt_reference_reset(m_ctx); }
+  uint32_t referenceSamples()
+  {
+    uint32_t n = 0;
+    rt_reference_samples(m_ctx, &n);
+    return n;
+  }
+  // RGBA32F mean of component 0 (direct), 1 (indirect) or 2 (sum)
+  bool readReference(int component, std::vector<float>& rgba)
+  {
+    rgba.resize(size_t(m_width) * m_height * 4);
+    return rt_reference_readback(m_ctx, component, rgba.data(), rgba.size() * sizeof(float)) == RT_OK;
+  }
   rt_ctx* context() { return m_ctx; }
  private:
   rt_ctx* m_ctx = nullptr;
@@ -86,6 +107,14 @@ class RenderOutput {
     rt_tonemapper tm = (state.debugging_mode == RT_DBG_DEPTH) ? m_depthTm : m_tm;  // render_output.cpp:228-230
     tm.zoom = zoom; tm.renderingRatio = ratio;
     if(rt_tonemap(m_ctx, &tm, state.debugging_mode, frames) != RT_OK) { fprintf(stderr, "RenderOutput::run: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  // run() over the two means of the reference mode instead of a frame's result images
+  bool runReference(float zoom, rt_vec2 ratio)
+  {
+    rt_tonemapper tm = m_tm;
+    tm.zoom = zoom; tm.renderingRatio = ratio;
+    if(rt_reference_tonemap(m_ctx, &tm) != RT_OK) { fprintf(stderr, "RenderOutput::runReference: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
   // the image the reference presents: RGBA8, row-major, top row first

@@ -2,7 +2,10 @@
 //   loadEnvironmentHdr -> loadScene (Scene::load + AccelStructure::create) -> createRender -> per frame:
 //   updateFrame / Scene::updateCamera -> Renderer::run -> (post.frag's sum of the two HDR images, written to disk)
 // Usage mirrors main.cpp:52-54:  restir_demo [-f scene.gltf | -p cornell|helmet|sponza|bistro|interior] [-e env.hdr]
-//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure]
+//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples]
+// -r N: after the real-time frames, N samples per pixel of the reference mode (rt_reference_render: the converged image the frame estimates)
+//       at the last frame's camera, tonemapped like the frame into <out>_reference.png.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -87,6 +90,21 @@ int main(int argc, char** argv)
     ppm << "P6\n" << W << " " << H << "\n255\n";
     for(size_t p = 0; p < size_t(W) * H; p++) ppm.write(reinterpret_cast<const char*>(&rgba[p * 4]), 3);
     if(!writePng(out + ".png", rgba.data(), W, H)) fprintf(stderr, "cannot write %s.png\n", out.c_str());
+  }
+  const int refSamples = atoi(arg(argc, argv, "-r", "0"));
+  if(refSamples > 0) {
+    const auto r0 = std::chrono::steady_clock::now();
+    for(int done = 0; done < refSamples; done += 16)   // (calls of 16 samples: the sums do not depend on the split)
+      if(!render.referenceRender(st, std::min(16, refSamples - done))) return 8;
+    RenderOutput offscreen;
+    offscreen.setup(render.context());
+    offscreen.create(W, H);
+    offscreen.m_tm.autoExposure = atoi(arg(argc, argv, "-a", "0"));
+    std::vector<uint8_t> rgba;
+    if(!offscreen.runReference(1.0f, rt_vec2{1.0f, 1.0f}) || !offscreen.readImage(rgba)) return 9;
+    const double rms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r0).count();
+    printf("reference: %u samples per pixel %dx%d in %.1f ms\n", render.referenceSamples(), W, H, rms);
+    if(!writePng(out + "_reference.png", rgba.data(), W, H)) { fprintf(stderr, "cannot write %s_reference.png\n", out.c_str()); return 10; }
   }
   render.destroy();
   return 0;

@@ -17,6 +17,7 @@ PRIO_FILTER_SHARE = 0.30   # the threshold of rt_render_frame's stream-priority 
 ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "rt_build_accel", "rt_resize", "rt_set_camera",
                "rt_render_frame", "rt_run_stage", "rt_readback", "rt_upload_history", "rt_buffer_bytes", "rt_device_ptr",
                "rt_set_counting", "rt_get_counters", "rt_sync", "rt_last_error", "rt_abi_version", "rt_set_traversal", "rt_set_history_rows", "rt_history_miss", "rt_set_overlap", "rt_tonemap", "rt_set_sun_and_sky", "rt_pick", "rt_trace_rays", "rt_history_miss_stage", "rt_rotate_buffers", "rt_select_frame", "rt_measure_valu_peak", "rt_set_stream_priorities", "rt_get_stream_priorities", "rt_get_streams", "rt_get_stream_layout",
+               "rt_reference_render", "rt_reference_reset", "rt_reference_samples", "rt_reference_readback", "rt_reference_tonemap",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -89,6 +90,12 @@ def hip_lib():
             L.rt_get_streams.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
             L.rt_get_stream_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int * 3)]
             L.rt_mgpu_get_stream_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_reference_render"):   # ABI 2.4 (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_reference_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.rt_reference_reset.argtypes = [C.c_void_p]
+            L.rt_reference_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+            L.rt_reference_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.rt_reference_tonemap.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -278,6 +285,31 @@ class Renderer:
         n, idx = C.c_int(), (C.c_int * 3)()
         self._chk(hip_lib().rt_get_stream_layout(self._h, C.byref(n), C.byref(idx)), "rt_get_stream_layout")
         return {"library_streams_created": n.value, "creation_index": {"main": idx[0], "ind": idx[1], "side": idx[2]}}
+
+    # ---- reference mode (ABI 2.4): the progressive ground-truth path tracer (include/rt_abi.h)
+    def reference_render(self, state, samples):
+        """add `samples` samples per pixel to the reference sums (n resets where an input of the integral changed: see rt_abi.h)"""
+        self._chk(hip_lib().rt_reference_render(self._h, C.byref(state), int(samples)), "rt_reference_render")
+
+    def reference_reset(self):
+        self._chk(hip_lib().rt_reference_reset(self._h), "rt_reference_reset")
+
+    def reference_samples(self):
+        n = C.c_uint32()
+        self._chk(hip_lib().rt_reference_samples(self._h, C.byref(n)), "rt_reference_samples")
+        return n.value
+
+    def reference_readback(self, component=abi.REF_SUM):
+        """(H, W, 4) float32 mean of abi.REF_DIRECT / REF_INDIRECT / REF_SUM, a = 1"""
+        W, H = self.size
+        out = np.empty((H, W, 4), dtype=np.float32)
+        self._chk(hip_lib().rt_reference_readback(self._h, int(component), out.ctypes.data, out.nbytes), "rt_reference_readback")
+        return out
+
+    def reference_tonemap(self, tm=None):
+        """post.frag over the two reference means -> BUF_LDR (RGBA8)"""
+        tm = tm if tm is not None else abi.Tonemapper()
+        self._chk(hip_lib().rt_reference_tonemap(self._h, C.byref(tm)), "rt_reference_tonemap")
 
     def accel_stats(self):
         n, t, d = C.c_uint64(), C.c_uint64(), C.c_int()

@@ -511,14 +511,46 @@ const char* rt_mgpu_last_error(rt_mgpu* m);
  * bench.py prices `roofline.valu` against this measurement instead of an assumed cycles-per-instruction figure.
  * (Introspection like rt_get_counters; no counterpart in the reference.) */
 int rt_measure_valu_peak(rt_ctx* ctx, int variant, int wavesPerSimd, double* waveInstPerSec);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Reference mode (ABI 2.4): a progressive, unbiased, deterministic path tracer over the same scene, camera, traversal and shading code
+ * as the frame — the converged image the real-time estimator approximates (the reference's RtxState.accumulate / frame slot,
+ * host_device.h:209,222, whose accumulating shader body it never wired).  Per sample of pixel (x, y) it estimates, in fp32:
+ *   primary ray = raySpawn (pathtrace.glsl:260-270), no extra jitter;  miss: direct = EnvRadiance;  emitter hit: direct = emission, the path ends;
+ *   vertex 1: direct = emission + one SampleDirectLight sample with its shadow ray, weight 1, BSDF with the material's real albedo;
+ *   vertices 2..maxDepth: pathTraceIndirect's integrand (indirect_stage.comp:129-226) into indirect — NEE with the power heuristic when MIS > 0, BSDF-sampled
+ *   env and emitter hits at depth > 1 with their MIS weight — with every path multi-bounce, throughput starting at 1 and the real albedo at vertex 1.
+ * No firefly clamp, no HDR->LDR encoding, no reservoirs, no denoiser: fireflyClampThreshold, modulate, ReSTIRState, RISSampleNum, reservoirClamp,
+ * denoise*, sig*, frame, time and accumulate are ignored; debugging_mode != 0 is RT_ERR_INVALID_ARG.  
+ * Determinism: sample s (0-based since the last reset) of pixel (x, y) of a W-wide image is seeded with
+ *     seed = tea(W * y + x, tea(s, 0x52454631))          (tea = random.glsl:34-48)
+ * and nothing else, so the result does not depend on how samples are split over calls, on rt_set_traversal or on frames in flight.  Each sample's
+ * radiance is added, in sample order, to per-pixel fp64 sums (direct rgb, indirect rgb: 48 B/px, allocated by the first rt_reference_render and
+ * freed by rt_resize / rt_destroy); a mean is float(sum / n) in IEEE double, one rounding.
+ * The sums reset (n -> 0) when an input of the integral changes: rt_resize, rt_upload_scene, rt_build_accel, rt_set_sun_and_sky, a camera whose
+ * viewInverse or projInverse differs (rt_set_camera; the history matrices do not count), and a call whose maxDepth, hdrMultiplier, environmentProb or
+ * MIS differ from the previous call's.  Nothing else resets them.
+ * The calls join the frames in flight and run on the context's main stream; they read and write no frame buffer (rt_reference_tonemap writes
+ * RT_BUF_LDR only), leave rt_get_counters, the stream-priority decision and the buffer rotation alone, and do not change what rt_render_frame computes.
+ * One launch adds one sample to a band of at most 2^20 pixels.  The multi-GPU context has no reference mode. */
+/* adds `samples` (>= 0) samples to every pixel.  RT_ERR_NO_SCENE / NO_ACCEL / NO_TARGET like rt_render_frame (state->size must match rt_resize). */
+int rt_reference_render(rt_ctx* ctx, const rt_state* state, int samples);
+/* n -> 0 */
+int rt_reference_reset(rt_ctx* ctx);
+/* samples accumulated since the last reset */
+int rt_reference_samples(rt_ctx* ctx, uint32_t* n);
+/* the mean of component 0 (direct), 1 (indirect) or 2 (direct + indirect: float((sumDirect + sumIndirect) / n)) as RGBA32F, a = 1; bytes = W * H * 16.
+ * With n == 0 every pixel is (0, 0, 0, 1).  Synchronous. */
+int rt_reference_readback(rt_ctx* ctx, int component, float* dst, size_t bytes);
+/* rt_tonemap's pass (post.frag, default view) over the direct and indirect means in place of the frame's two result images -> RT_BUF_LDR. */
+int rt_reference_tonemap(rt_ctx* ctx, const rt_tonemapper* tm);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
+/* ABI version: (major<<16)|minor.  2.4: + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
-#define RT_ABI_VERSION_MINOR 3u
+#define RT_ABI_VERSION_MINOR 4u
 uint32_t rt_abi_version(void);
 
 #ifdef __cplusplus

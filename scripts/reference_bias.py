@@ -1,0 +1,200 @@
+"""How far the shipped real-time frame is from the image it estimates: K real-time frames at a fixed camera (modulate = 1) averaged, against the
+reference mode (rt_reference_render) at S samples per pixel, per component (direct, indirect, sum).
+
+Per configuration (bench.py's CONFIGS: 2 Cornell 512^2, 3 Sponza-class 1080p maxDepth 2, 4 bistro-exterior-class 1080p, lite footprint) and per variant
+of the real-time state (default; denoise off; temporal reuse off = ReSTIRState RIS) it prints one JSON line with, per component and over all pixels and over
+the pixels whose primary ray hits a surface (G-buffer depth < infinity):
+  lum_ratio    mean luminance of the frame average / mean luminance of the reference
+  median_px_ratio  median over pixels of (frame luminance / reference luminance) — not dominated by the few brightest pixels
+  rel_rmse     RMS of (frame average - reference) over pixels and channels / mean of the reference over pixels and channels
+  out_3sigma   share of pixels whose luminance difference exceeds 3 sigma of the reference's own mean (sigma from B batch means of the reference)
+The reference ignores the real-time state (its sums are taken once per configuration); every frame of the average uses the same camera (its history matrices
+advanced per frame, as SampleExample::updateFrame does), time = 1000 + f.
+Config 2 runs the whole frame here (bench.py times the direct stage alone for it).
+
+  python scripts/reference_bias.py [--configs 2 3 4] [--frames 64] [--warmup 8] [--spp 256] [--batches 8] [--out profiles/reference_bias.jsonl]
+  python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]       # reference time per sample at the configuration's size (host-timed, synchronised)
+  python scripts/reference_bias.py --rays-per-path [--configs 4 2]         # CPU only: ray queries per path of the CPU restatement (tests/refpt_checker.cpp)
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import restir_amd  # noqa: E402,F401
+from restir_amd import abi, host  # noqa: E402
+
+# (kind, size, env, state overrides) of bench.py's CONFIGS, lite footprint
+CONFIGS = {
+    2: ("PROC_CORNELL", (512, 512), None, {"environmentProb": 0.0, "fireflyClampThreshold": 100.0}),
+    3: ("PROC_SPONZA", (1920, 1080), (2048, 1024), {"maxDepth": 2}),
+    4: ("PROC_BISTRO_EXT", (1920, 1080), (2048, 1024), {}),
+}
+VARIANTS = {"default": {}, "denoise_off": {"denoise": 0}, "temporal_off": {"ReSTIRState": abi.RESTIR_RIS}}
+LUM = np.array([0.2126, 0.7152, 0.0722])
+
+
+def setup(config, width=0, height=0):
+    kind, size, env_size, over = CONFIGS[config]
+    W, H = width or size[0], height or size[1]
+    sc = host.Scene().makeProcedural(getattr(abi, kind), 1.0, 1)
+    env = None
+    if env_size:
+        env = host.HdrSampling()
+        env.makeSyntheticSky(env_size[0], env_size[1], 5e4, 7)
+    st = host.default_state(W, H, sc, env)
+    for k, v in over.items():
+        setattr(st, k, v)
+    st.modulate = 1
+    sc.updateCamera(W, H)
+    return sc, env, st, W, H
+
+
+def reference(r, st, spp, batches):
+    """mean of each component after spp samples, and the standard error of the luminance of the sum's mean (from `batches` batch means)"""
+    r.reference_reset()
+    per = spp // batches
+    prev = np.zeros((st.size.y, st.size.x, 3))
+    bmeans = []
+    t0 = time.time()
+    for b in range(batches):
+        r.reference_render(st, per)
+        cur = r.reference_readback(abi.REF_SUM)[..., :3].astype(np.float64)
+        n = r.reference_samples()
+        bmeans.append((cur * n - prev * (n - per)) / per)     # the batch's own mean
+        prev = cur
+    secs = time.time() - t0
+    lum_b = np.stack([m @ LUM for m in bmeans])
+    sigma = lum_b.std(axis=0, ddof=1) / np.sqrt(batches)
+    return [r.reference_readback(c)[..., :3].astype(np.float64) for c in range(3)], sigma, secs
+
+
+def realtime_average(r, sc, st, frames, warmup):
+    acc = [None, None]
+    for f in range(warmup + frames):
+        st.time = 1000 + f
+        st.frame = f
+        sc.updateCamera(st.size.x, st.size.y)                   # static camera; advances the history matrices like SampleExample does (temporal reuse needs them)
+        r.set_camera(sc.getCamera())
+        r.run(st, f)
+        if f >= warmup:
+            cur = f & 1
+            for k, buf in enumerate((abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)):
+                img = r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
+                acc[k] = img if acc[k] is None else acc[k] + img
+    last = (warmup + frames - 1) & 1
+    g = r.readback(abi.BUF_GBUFFER0 + last).view(np.uint32).reshape(st.size.y, st.size.x, 4)
+    surface = g[..., 0].view(np.float32) < 1e28 * 0.8
+    d, i = acc[0] / frames, acc[1] / frames
+    return [d, i, d + i], surface
+
+
+def metrics(frame, ref, sigma, mask):
+    f, g = frame[mask], ref[mask]
+    lf, lg = f @ LUM, g @ LUM
+    pos = lg > 0
+    return {"lum_ratio": round(float(lf.mean() / lg.mean()), 4) if lg.mean() > 0 else None,
+            "median_px_ratio": round(float(np.median(lf[pos] / lg[pos])), 4) if pos.any() else None,
+            "rel_rmse": round(float(np.sqrt(((f - g) ** 2).mean()) / g.mean()), 4) if g.mean() > 0 else None,
+            "out_3sigma": round(float((np.abs(lf - lg) > 3 * sigma[mask]).mean()), 4) if sigma is not None else None}
+
+
+def bias(args):
+    from restir_amd.renderer import Renderer
+    for config in args.configs:
+        sc, env, st0, W, H = setup(config, args.width, args.height)
+        desc = sc.desc(env)
+        r = Renderer().setup(0)
+        r.load_scene(desc)
+        r.update(W, H)
+        r.set_camera(sc.getCamera())
+        ref, sigma, secs = reference(r, st0, args.spp, args.batches)
+        for vname, over in VARIANTS.items():
+            st = abi.RtxState.from_buffer_copy(st0)
+            for k, v in over.items():
+                setattr(st, k, v)
+            r.update(W, H)                                      # fresh history for every variant
+            r.set_camera(sc.getCamera())
+            frame, surface = realtime_average(r, sc, st, args.frames, args.warmup)
+            out = {"config": config, "variant": vname, "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
+                   "ref_batches": args.batches, "ref_seconds": round(secs, 2), "surface_share": round(float(surface.mean()), 4)}
+            everything = np.ones_like(surface)
+            for name, c in (("direct", 0), ("indirect", 1), ("sum", 2)):
+                out[name] = {"all": metrics(frame[c], ref[c], sigma if c == 2 else None, everything),
+                             "surface": metrics(frame[c], ref[c], sigma if c == 2 else None, surface)}
+            line = json.dumps(out)
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, "a") as fh:
+                    fh.write(line + "\n")
+        r.destroy()
+
+
+def timing(args):
+    from restir_amd.renderer import Renderer
+    for config in args.configs:
+        sc, env, st, W, H = setup(config, args.width, args.height)
+        r = Renderer().setup(0)
+        r.load_scene(sc.desc(env))
+        r.update(W, H)
+        r.set_camera(sc.getCamera())
+        r.reference_render(st, 1)
+        r.reference_readback(abi.REF_SUM)                        # warm: first launch, allocation
+        r.reference_reset()
+        t0 = time.time()
+        r.reference_render(st, args.spp)
+        r.reference_readback(abi.REF_SUM)
+        dt = (time.time() - t0) / args.spp
+        print(json.dumps({"config": config, "size": [W, H], "maxDepth": st.maxDepth, "spp": args.spp, "ms_per_sample": round(dt * 1e3, 3),
+                          "paths_per_s": round(W * H / dt / 1e6, 2), "unit": "Mpaths/s (host-timed, includes one readback)"}), flush=True)
+        r.destroy()
+
+
+def rays_per_path(args):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tempfile
+    import refpt
+    lib = refpt.build(tempfile.mkdtemp(prefix="refpt"))
+    for config in args.configs:
+        sc, env, st, W, H = setup(config, args.width, args.height)
+        w, h = max(8, W // 8), max(8, H // 8)
+        s = abi.RtxState.from_buffer_copy(st); s.size.x, s.size.y = w, h
+        sc.updateCamera(w, h)
+        desc = sc.desc(env)
+        k = refpt.RefChecker(lib, desc)
+        k.resize(w, h)
+        k.set_camera(sc.getCamera())
+        k.render(s, args.spp, threads=os.cpu_count() and min(16, os.cpu_count()))
+        print(json.dumps({"config": config, "size": [w, h], "spp": args.spp, "maxDepth": s.maxDepth,
+                          "rays_per_path": round(k.rays() / (w * h * args.spp), 3), "source": "CPU restatement (tests/refpt_checker.cpp), same camera at 1/8 size"}), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--configs", type=int, nargs="+", default=[2, 3, 4], choices=sorted(CONFIGS))
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--warmup", type=int, default=8)
+    ap.add_argument("--spp", type=int, default=256)
+    ap.add_argument("--batches", type=int, default=8)
+    ap.add_argument("--width", type=int, default=0)
+    ap.add_argument("--height", type=int, default=0)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--timing", action="store_true")
+    ap.add_argument("--rays-per-path", action="store_true")
+    args = ap.parse_args()
+    if args.rays_per_path:
+        rays_per_path(args)
+    elif args.timing:
+        timing(args)
+    else:
+        assert args.spp % args.batches == 0 and args.batches >= 2
+        bias(args)
+
+
+if __name__ == "__main__":
+    main()
