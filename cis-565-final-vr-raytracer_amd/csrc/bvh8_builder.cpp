@@ -33,6 +33,11 @@
 namespace rt {
 namespace {
 
+// Binned SAH of both builders: object bins, spatial bins, and the cost of one wide-node slot in triangle tests (the leaf rule).  Measured: a slot cost of 0.25
+// beats 0.5 by 2 % on the Bistro-class scene; 16, 32 or 64 bins make no difference.
+constexpr int NB = 16, NBS = 16;
+constexpr float LEAF_SLOT_COST = 0.25f;
+
 struct Box {
   float lo[3], hi[3];
   void reset() { for(int a = 0; a < 3; a++) { lo[a] = 3e38f; hi[a] = -3e38f; } }
@@ -112,9 +117,6 @@ struct Builder2 {
   alignas(64) std::atomic<uint32_t> nodeCount{1};   // (a line of its own: every node of every thread draws from it)
   alignas(64) std::atomic<int> liveThreads{0};
   alignas(64) int maxThreads;
-  // (read per build, not once per process: the settings are part of rt_build_accel's cache key)
-  const int envNB = getenv("RESTIR_BVH_BINS") ? std::min(64, std::max(4, atoi(getenv("RESTIR_BVH_BINS")))) : 16;
-  const float leafSlotCost = getenv("RESTIR_BVH_SLOTCOST") ? float(atof(getenv("RESTIR_BVH_SLOTCOST"))) : 0.25f;  // measured: 0.25 beats 0.5 by 2 % on the Bistro-class scene, bins 16 vs 32 vs 64 make no difference
   Builder2(const std::vector<Prim>& p, std::vector<uint32_t>& i, int threads) : prims(p), idx(i), nodes(std::max<size_t>(2, 2 * p.size() + 2), N2{}), maxThreads(threads) {}
 
   void build(uint32_t node, uint32_t b, uint32_t e)
@@ -128,13 +130,11 @@ struct Builder2 {
       auto makeLeaf = [&] { N.leaf = true; N.a = b; N.n = cnt; };
       if(cnt <= 1) { makeLeaf(); return; }
       // binned SAH over the three axes
-      constexpr int NBMAX = 64;
-      const int NB = envNB;
       float best = 3e38f; int bestAxis = -1, bestBin = 0;
       for(int ax = 0; ax < 3; ax++) {
         float ext = cb.hi[ax] - cb.lo[ax];
         if(!(ext > 0)) continue;
-        Box bb[NBMAX]; uint32_t bc[NBMAX];
+        Box bb[NB]; uint32_t bc[NB];
         for(int i = 0; i < NB; i++) { bb[i].reset(); bc[i] = 0; }
         const float k1 = NB * (1.f - 1e-6f) / ext;
         for(uint32_t k = b; k < e; k++) {
@@ -142,7 +142,7 @@ struct Builder2 {
           int bi = std::min(NB - 1, std::max(0, int((p.c[ax] - cb.lo[ax]) * k1)));
           bb[bi].grow(p.b); bc[bi]++;
         }
-        float ra[NBMAX]; uint32_t rc[NBMAX];
+        float ra[NB]; uint32_t rc[NB];
         Box acc; acc.reset(); uint32_t c = 0;
         for(int i = NB - 1; i > 0; i--) { acc.grow(bb[i]); c += bc[i]; ra[i] = acc.area(); rc[i] = c; }
         acc.reset(); c = 0;
@@ -156,7 +156,7 @@ struct Builder2 {
       const float pa = std::max(N.b.area(), 1e-30f);
       if(cnt <= 3) {
         // leaf of <= 3 triangles unless splitting is clearly cheaper (one wide-node slot costs a fraction of a triangle test)
-        if(bestAxis < 0 || leafSlotCost * pa + best >= float(cnt) * pa) { makeLeaf(); return; }
+        if(bestAxis < 0 || LEAF_SLOT_COST * pa + best >= float(cnt) * pa) { makeLeaf(); return; }
       }
       uint32_t mid;
       if(bestAxis >= 0) {
@@ -238,9 +238,6 @@ struct BuilderS {
   alignas(64) int64_t rootBudget;
   int maxThreads;
   float rootArea = 1.f, alpha = 1e-5f;
-  int NB = 16, NBS = 16;   // bins of the object / of the spatial split search
-  float leafSlotCost = 0.25f;
-  bool areaRule = false;
   // nodes with more than PAR_MIN references bin them in parallel, in chunks of PAR_CHUNK; subtrees of at most SEQ_MAX references: one thread, budget pooled (see above).
   // (RESTIR_BVH_PAR_MIN / RESTIR_BVH_SEQ_MAX: test hooks — the sanitizer jobs of tests/test_bvh_quality.py reach every parallel path on a 50 k-triangle scene.  The
   //  thresholds are part of the build's definition: another value is another, equally reproducible, tree.)
@@ -322,12 +319,11 @@ struct BuilderS {
     if(pool) pool->leafRefs += refs.size(); else leafRefs += refs.size();
   }
 
-  static constexpr int NBMAX = 64;
   struct Bins {   // what one pass over (a chunk of) a node's references collects: object bins by centroid and spatial bins by clipped extent, for the three axes
-    Box ob[3][NBMAX]; uint32_t oc[3][NBMAX];
-    Box sb[3][NBMAX]; uint32_t en[3][NBMAX], ex[3][NBMAX];
-    void reset(int nb, int nbs) { for(int a = 0; a < 3; a++) { for(int i = 0; i < nb; i++) { ob[a][i].reset(); oc[a][i] = 0; } for(int i = 0; i < nbs; i++) { sb[a][i].reset(); en[a][i] = ex[a][i] = 0; } } }
-    void merge(const Bins& o, int nb, int nbs) { for(int a = 0; a < 3; a++) { for(int i = 0; i < nb; i++) { ob[a][i].grow(o.ob[a][i]); oc[a][i] += o.oc[a][i]; } for(int i = 0; i < nbs; i++) { sb[a][i].grow(o.sb[a][i]); en[a][i] += o.en[a][i]; ex[a][i] += o.ex[a][i]; } } }
+    Box ob[3][NB]; uint32_t oc[3][NB];
+    Box sb[3][NBS]; uint32_t en[3][NBS], ex[3][NBS];
+    void reset() { for(int a = 0; a < 3; a++) { for(int i = 0; i < NB; i++) { ob[a][i].reset(); oc[a][i] = 0; } for(int i = 0; i < NBS; i++) { sb[a][i].reset(); en[a][i] = ex[a][i] = 0; } } }
+    void merge(const Bins& o) { for(int a = 0; a < 3; a++) { for(int i = 0; i < NB; i++) { ob[a][i].grow(o.ob[a][i]); oc[a][i] += o.oc[a][i]; } for(int i = 0; i < NBS; i++) { sb[a][i].grow(o.sb[a][i]); en[a][i] += o.en[a][i]; ex[a][i] += o.ex[a][i]; } } }
   };
   // which: 1 = the object bins, 2 = the spatial bins (a second pass, only for the nodes whose object split leaves its children overlapping: it clips every straddling
   // reference per bin — until round 6's first restructuring merged the two passes, and with a working budget that is never exhausted EVERY node paid for it)
@@ -399,14 +395,14 @@ struct BuilderS {
       if(cnt <= 1) { leafHere(); return; }
       // ---- object bins on the reference centroids (the rule of Builder2) ----
       const bool mayAdd = budget > 0;
-      Bins B;   // (on the stack: 23 KB; the recursion is as deep as the tree)
-      B.reset(NB, NBS);
+      Bins B;   // (on the stack: 3 KB; the recursion is as deep as the tree)
+      B.reset();
       auto binAll = [&](int which) {
         if(par > 1) {
           const size_t nch = (cnt + PAR_CHUNK - 1) / PAR_CHUNK;
           std::vector<std::unique_ptr<Bins>> part(nch);
-          parallelChunks(cnt, PAR_CHUNK, par, [&](size_t c, size_t b, size_t e) { part[c].reset(new Bins); part[c]->reset(NB, NBS); binRefs(refs.data() + b, e - b, nb, cb, which, *part[c]); });
-          for(size_t c = 0; c < nch; c++) B.merge(*part[c], NB, NBS);
+          parallelChunks(cnt, PAR_CHUNK, par, [&](size_t c, size_t b, size_t e) { part[c].reset(new Bins); part[c]->reset(); binRefs(refs.data() + b, e - b, nb, cb, which, *part[c]); });
+          for(size_t c = 0; c < nch; c++) B.merge(*part[c]);
         } else binRefs(refs.data(), cnt, nb, cb, which, B);
       };
       binAll(1);
@@ -416,7 +412,7 @@ struct BuilderS {
         const float ext = cb.hi[ax] - cb.lo[ax];
         if(!(ext > 0)) continue;
         const Box* bb = B.ob[ax]; const uint32_t* bc = B.oc[ax];
-        Box rb[NBMAX]; uint32_t rc[NBMAX];
+        Box rb[NB]; uint32_t rc[NB];
         Box acc; acc.reset(); uint32_t c = 0;
         for(int i = NB - 1; i > 0; i--) { acc.grow(bb[i]); c += bc[i]; rb[i] = acc; rc[i] = c; }
         acc.reset(); c = 0;
@@ -443,7 +439,7 @@ struct BuilderS {
           if(!(ext > 0)) continue;
           const Box* bb = B.sb[ax]; const uint32_t* en = B.en[ax]; const uint32_t* exx = B.ex[ax];
           const float w = ext / NBS;
-          Box rb[NBMAX]; uint32_t rc[NBMAX];
+          Box rb[NBS]; uint32_t rc[NBS];
           Box acc; acc.reset(); uint32_t c = 0;
           for(int i = NBS - 1; i > 0; i--) { acc.grow(bb[i]); c += exx[i]; rb[i] = acc; rc[i] = c; }
           acc.reset(); c = 0;
@@ -458,7 +454,7 @@ struct BuilderS {
       const bool spatial = sAxis >= 0 && sBest < best && int64_t(sNL + sNR) - int64_t(cnt) <= budget;
       const float chosen = spatial ? sBest : best;
       if(cnt <= 3) {
-        if((bestAxis < 0 && !spatial) || leafSlotCost * pa + chosen >= float(cnt) * pa) { leafHere(); return; }
+        if((bestAxis < 0 && !spatial) || LEAF_SLOT_COST * pa + chosen >= float(cnt) * pa) { leafHere(); return; }
       }
       RefVec left, right;
       if(spatial) {
@@ -508,9 +504,7 @@ struct BuilderS {
         continue;
       }
       // what this split did not use of the subtree's budget goes to the children in proportion to their reference counts; their record / leaf ranges follow from it
-      // (RESTIR_BVH_BUDGET_RULE=area weighs a child's count with the area of its references' bounds: measured against the count rule in profiles/r06_bvh_build.txt)
-      double wl = double(left.size()), wr = double(right.size());
-      if(areaRule) { Box bL, bR; bL.reset(); bR.reset(); for(const Ref& r : left) bL.grow(r.b); for(const Ref& r : right) bR.grow(r.b); wl *= double(bL.area()) + 1e-30; wr *= double(bR.area()) + 1e-30; }
+      const double wl = double(left.size()), wr = double(right.size());
       const int64_t bl = std::min<int64_t>(rest, std::max<int64_t>(0, int64_t(double(rest) * (wl / (wl + wr))))), br = rest - bl;
       const uint32_t child = nodeBase;
       const uint32_t lNodes = uint32_t(2 * (int64_t(left.size()) + bl) - 2), lLeaves = uint32_t(int64_t(left.size()) + bl);
@@ -859,10 +853,6 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
       RefVec refs = refs0;
       if(strict) RefVec().swap(refs0);
       BS->rootArea = std::max(root.area(), 1e-30f); BS->alpha = splitAlpha;
-      BS->NB = getenv("RESTIR_BVH_BINS") ? std::min(64, std::max(4, atoi(getenv("RESTIR_BVH_BINS")))) : 16;
-      BS->NBS = getenv("RESTIR_BVH_SBINS") ? std::min(64, std::max(4, atoi(getenv("RESTIR_BVH_SBINS")))) : 16;
-      BS->leafSlotCost = getenv("RESTIR_BVH_SLOTCOST") ? float(atof(getenv("RESTIR_BVH_SLOTCOST"))) : 0.25f;
-      BS->areaRule = getenv("RESTIR_BVH_BUDGET_RULE") && strcmp(getenv("RESTIR_BVH_BUDGET_RULE"), "area") == 0;
       BS->build(0, std::move(refs), BS->rootBudget, 1u, 0u);
       BS->report();
       n2count = uint32_t(BS->nodes.size());   // (record ranges are handed out per subtree: the records in use are not contiguous)
@@ -877,11 +867,11 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
   }
   timer.lap("BVH2 (splits)");
   {
-    const bool dp = plainTree;   // (plain tree: no quality passes.  The SAH-optimal collapse takes its bottom-up order from the tree itself since round 5, so the passes may run before it)
-    const int rotate = dp ? 0 : (getenv("RESTIR_BVH_ROTATE") ? atoi(getenv("RESTIR_BVH_ROTATE")) : RT_BVH_ROTATE_DEFAULT);
+    // (plain tree: no quality passes)
+    const int rotate = plainTree ? 0 : (getenv("RESTIR_BVH_ROTATE") ? atoi(getenv("RESTIR_BVH_ROTATE")) : RT_BVH_ROTATE_DEFAULT);
     N2Vec& M = BS ? BS->nodes : B2->nodes;
     const bool rotateGG = getenv("RESTIR_BVH_ROTATE_GG") && atoi(getenv("RESTIR_BVH_ROTATE_GG")) != 0;
-    const int reins = dp ? 0 : (getenv("RESTIR_BVH_REINSERT") ? atoi(getenv("RESTIR_BVH_REINSERT")) : RT_BVH_REINSERT_DEFAULT);
+    const int reins = plainTree ? 0 : (getenv("RESTIR_BVH_REINSERT") ? atoi(getenv("RESTIR_BVH_REINSERT")) : RT_BVH_REINSERT_DEFAULT);
     if(reins > 0) {
       Reinserter RI(M, n2count);
       for(int pass = 0; pass < reins; pass++) RI.pass(0.02f);
@@ -893,68 +883,13 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
   const N2Vec& N = BS ? BS->nodes : B2->nodes;
   const std::vector<uint32_t>& leafTris = BS ? BS->leafTris : idx;
 
-  // ---- 3a. which BVH2 nodes become wide nodes: SAH-optimal collapse (Ylitie, Karras, Laine 2017, §3.1) -------------------------
-  // cost[n][i] = cheapest way to hang BVH2 subtree n under a parent using at most i of the parent's 8 slots, where a slot holds
-  // either a BVH2 leaf (<= 3 triangles, area x triangles x cTri) or a wide node (area x cNode + the cost of ITS 8 slots).
-  //   cost[n][1] = A_n cNode + min_k cost[l][k] + cost[r][8-k]          (n becomes a wide node)
-  //   cost[n][i] = min(cost[n][i-1], min_k cost[l][k] + cost[r][i-k])   (n dissolves: its children share i slots)
-  // The greedy "open the largest child" rule leaves wide nodes 2.8 of 8 slots full on average (636 k nodes for 2.8 M
-  // triangles, depth 11, 16.5 node visits per ray); the tree does not change any result, only the step counts.
-  // Measured on the 2.8 M-triangle bench scene (scripts/bvh_ab.py, profiles/r02_bvh_collapse_ab.txt): 408 k nodes instead of 636 k, but
-  // node visits per ray only 16.49 -> 16.18 (the visits are in the upper and middle levels, not in the under-filled bottom nodes), depth
-  // 11 -> 13, direct stage -2 %, indirect stage +4.6 %: no net gain, so the greedy rule stays the default (RESTIR_BVH_COLLAPSE=dp selects this).
-  const bool useDp = getenv("RESTIR_BVH_COLLAPSE") && strcmp(getenv("RESTIR_BVH_COLLAPSE"), "dp") == 0;
-  static const float cNode = 2.3f;   // a node step is ~230 instructions,
-  static const float cTri = 1.0f;                                                                            // a triangle step ~100
-  std::vector<float> cost;        // [n][i], i = 1..7 at [n * 8 + i]
-  std::vector<uint8_t> choice;    // [n][i]: 0 = single slot (leaf / wide node), 0xff = same as i - 1, else k = slots of the left child
-  std::vector<uint8_t> k8;        // [n]: left child's share of the 8 slots when n becomes a wide node
-  if(useDp) {
-    cost.assign(size_t(n2count) * 8, 0.f); choice.assign(size_t(n2count) * 8, 0); k8.assign(n2count, 1);
-    // bottom-up order: children before their parent.  The builders allocate children after their parent, but the quality passes move records (a rotation swaps
-    // two records, a reinsertion moves three), so the order is taken from the tree itself
-    std::vector<uint32_t> post; post.reserve(n2count);
-    {
-      std::vector<uint32_t> st2; st2.push_back(0u);
-      while(!st2.empty()) { const uint32_t q = st2.back(); st2.pop_back(); post.push_back(q); if(!N[q].leaf) { st2.push_back(N[q].a); st2.push_back(N[q].a + 1); } }
-    }
-    for(size_t pi = post.size(); pi-- > 0;) {   // reverse pre-order: every node comes after all of its descendants
-      const uint32_t n = post[pi];
-      const N2& x = N[n];
-      const float A = x.b.area();
-      float* c = &cost[size_t(n) * 8];
-      uint8_t* ch = &choice[size_t(n) * 8];
-      if(x.leaf) { for(int i = 1; i < 8; i++) { c[i] = A * float(x.n) * cTri; ch[i] = 0; } continue; }
-      const float* cl = &cost[size_t(x.a) * 8];
-      const float* cr = &cost[size_t(x.a + 1) * 8];
-      auto dist = [&](int j, int& kBest) { float b = 3e38f; kBest = 1; for(int k = std::max(1, j - 7); k <= std::min(7, j - 1); k++) { const float v = cl[k] + cr[j - k]; if(v < b) { b = v; kBest = k; } } return b; };
-      int kb;
-      const float d8 = dist(8, kb);
-      k8[n] = uint8_t(kb);
-      c[1] = A * cNode + d8; ch[1] = 0;
-      for(int i = 2; i < 8; i++) {
-        const float d = dist(i, kb);
-        if(d < c[i - 1]) { c[i] = d; ch[i] = uint8_t(kb); } else { c[i] = c[i - 1]; ch[i] = 0xff; }
-      }
-    }
-  }
-  // children of a wide node: follow the recorded choices
-  auto expand = [&](auto&& self, uint32_t n, int i, uint32_t* out, int& nc) -> void {
-    while(i > 1 && choice[size_t(n) * 8 + i] == 0xff) i--;
-    const uint8_t c = (N[n].leaf || i == 1) ? uint8_t(0) : choice[size_t(n) * 8 + i];
-    if(c == 0) { out[nc++] = n; return; }
-    self(self, N[n].a, int(c), out, nc);
-    self(self, N[n].a + 1, i - int(c), out, nc);
-  };
-
-  // ---- 3b. build the 8-wide nodes, breadth-first so that a node's internal children are contiguous ------------------
+  // ---- 3. build the 8-wide nodes, breadth-first so that a node's internal children are contiguous ------------------
   // Round 6: level by level, two parallel passes per level around a prefix sum.  Pass 1 picks a wide node's children (collapse), assigns them to slots and counts its
   // internal children and leaf triangles; the prefix sum over the level (in level order) gives every node its child base and triangle base — the same numbers the
   // sequential breadth-first queue of rounds 1-5 produced; pass 2 quantises, writes the node, copies its triangle records and names its children's records for the
   // next level.  The statistics are summed per fixed chunk and then in chunk order: the same bits for any thread count.
   struct Work { uint32_t n2; uint32_t wide; };
   struct Wide { uint32_t ch[8]; int8_t childInSlot[8]; uint8_t nc, nInner, nTris; };
-  const bool optSlots = getenv("RESTIR_BVH_SLOTS") && strcmp(getenv("RESTIR_BVH_SLOTS"), "opt") == 0;
   const int T = std::max(1, threads);
   constexpr size_t WCH = 512;
   std::vector<Work> level, nextLevel;
@@ -977,12 +912,7 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
         Wide& X = wide[wi];
         uint32_t* ch = X.ch; int nc = 0;
         if(N[w.n2].leaf) ch[nc++] = w.n2;
-        else if(useDp) {
-          // the optimal 8 children of this wide node under the cost model: left subtree in k8 slots, right subtree in the rest
-          const int k = k8[w.n2];
-          expand(expand, N[w.n2].a, k, ch, nc);
-          expand(expand, N[w.n2].a + 1, 8 - k, ch, nc);
-        } else {
+        else {
           ch[nc++] = N[w.n2].a; ch[nc++] = N[w.n2].a + 1;
           for(;;) {  // greedily open the internal child with the largest surface area
             int pick = -1; float bestA = -1.f;
@@ -1012,32 +942,6 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
             }
           }
           done[bc] = true; slotUsed[bs] = true; slotOf[bc] = bs;
-        }
-        // RESTIR_BVH_SLOTS=opt (experiment, profiles/r05_bvh_quality_ab.txt): the assignment that MAXIMISES the summed projection (Ylitie et al. 2017 solve it with an
-        // auction; with 8 x 8 an exact subset DP is 2 k steps per node) instead of the greedy best pair above
-        if(optSlots && nc > 1) {
-          float score[8][8];
-          for(int i = 0; i < nc; i++) {
-            const Box& cb = N[ch[i]].b;
-            const float d[3] = {0.5f * (cb.lo[0] + cb.hi[0]) - cen[0], 0.5f * (cb.lo[1] + cb.hi[1]) - cen[1], 0.5f * (cb.lo[2] + cb.hi[2]) - cen[2]};
-            for(int s2 = 0; s2 < 8; s2++) score[i][s2] = d[0] * slotSign(s2, 0) + d[1] * slotSign(s2, 1) + d[2] * slotSign(s2, 2);
-          }
-          // dp[mask] = best total for children 0 .. popcount(mask) - 1 placed in the slots of mask
-          float dp[256]; int8_t from[256];
-          for(int m = 0; m < 256; m++) { dp[m] = -3e38f; from[m] = -1; }
-          dp[0] = 0.f;
-          for(int m = 0; m < 256; m++) {
-            const int i = __builtin_popcount(unsigned(m));
-            if(i >= nc || dp[m] < -1e38f) continue;
-            for(int s2 = 0; s2 < 8; s2++) {
-              if(m & (1 << s2)) continue;
-              const float v = dp[m] + score[i][s2];
-              if(v > dp[m | (1 << s2)]) { dp[m | (1 << s2)] = v; from[m | (1 << s2)] = int8_t(s2); }
-            }
-          }
-          int bestMask = -1; float bestV = -3e38f;
-          for(int m = 0; m < 256; m++) if(__builtin_popcount(unsigned(m)) == nc && dp[m] > bestV) { bestV = dp[m]; bestMask = m; }
-          for(int i = nc - 1, m = bestMask; i >= 0; i--) { const int s2 = from[m]; slotOf[i] = s2; m &= ~(1 << s2); }
         }
         for(int s = 0; s < 8; s++) X.childInSlot[s] = -1;
         for(int i = 0; i < nc; i++) X.childInSlot[slotOf[i]] = int8_t(i);

@@ -20,16 +20,8 @@ namespace rt {
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-#ifndef RT_GENERIC_AS
-#define RT_GENERIC_AS 0   // 1 (measurement builds, scripts/r06_addrspace_ab.sh): the accessors below go through generic pointers again = the code of rounds 1-5
-#endif
-#if RT_GENERIC_AS
-#define RT_AS_GLOBAL
-#define RT_AS_LDS
-#else
 #define RT_AS_GLOBAL __attribute__((address_space(1)))
 #define RT_AS_LDS __attribute__((address_space(3)))
-#endif
 RT_DEV uint8_t gLoadU8(const void* p) { return *(const RT_AS_GLOBAL uint8_t*)p; }
 RT_DEV uint32_t gLoadU32(const void* p) { return *(const RT_AS_GLOBAL uint32_t*)p; }
 RT_DEV uint2 gLoadU2(const void* p) { const u32x2_t v = *(const RT_AS_GLOBAL u32x2_t*)p; return make_uint2(v.x, v.y); }

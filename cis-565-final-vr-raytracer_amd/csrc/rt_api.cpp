@@ -38,7 +38,6 @@ struct rt_ctx {
   // context that destroyed and re-created its streams while trying settings ended with its filter stream on the main stream's queue (the 5th normal-priority stream of
   // the process lands on the 1st one's queue): 3.38 -> 3.71 ms per frame, found by two back-to-back bench lines in round 5.
   hipStream_t indStreams[3] = {nullptr, nullptr, nullptr}, sideStreams[3] = {nullptr, nullptr, nullptr};   // index = level + 1
-  std::vector<hipStream_t> padStreams;   // idle streams of the creation-order probe (RESTIR_STREAM_PAD)
   int prio[3] = {0, 1, 0};   // priority level of the main / indirect / filter stream (-1 low, 0 normal, +1 high): prioSpec() at rt_create, rt_set_stream_priorities, the rule
   bool prioFromEnv = false;  // RESTIR_PRIO was set (A/B scripts stay in control)
   bool prioExplicit = false; // rt_set_stream_priorities was called: the rule stays out of it, also after rt_resize / a new scene
@@ -250,21 +249,6 @@ static void buildOpacityMap(const AlphaRec& a, const std::vector<uint8_t>* alpha
 
 static int fail(rt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
 
-// CU-partitioned streams (experiment, round 4: profiles/r04_cu_mask_ab.txt).  RESTIR_CU_SPLIT="a-b,c-d,e-f": the main (direct stage), indirect and filter
-// streams of rt_render_frame's overlapped schedules are created with hipExtStreamCreateWithCUMask and may use compute units [a,b) / [c,d) / [e,f) of EVERY XCD
-// (32 per XCD on MI355X; mask bit i selects CU i / 8 of XCD i % 8 — scripts/probe/cu_mask_probe.hip).  Unset: ordinary streams, the whole chip.
-static bool cuSplitRange(int which, int& lo, int& hi)
-{
-  static int r[3][2]; static int have = -1;
-  if(have < 0) {
-    have = 0;
-    if(const char* e = getenv("RESTIR_CU_SPLIT"))
-      if(sscanf(e, "%d-%d,%d-%d,%d-%d", &r[0][0], &r[0][1], &r[1][0], &r[1][1], &r[2][0], &r[2][1]) == 6) have = 1;
-  }
-  if(!have) return false;
-  lo = std::max(0, std::min(32, r[which][0])); hi = std::max(lo + 1, std::min(32, r[which][1]));
-  return !(lo == 0 && hi == 32);
-}
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
 // default —, 3 filter stream high) or three characters over {-, 0, +} for the main (direct stage) / indirect / filter stream: "+00" = main stream high, "0+-" =
 // indirect high and filters low.  level: -1 low, 0 normal, +1 high.
@@ -275,29 +259,16 @@ static void prioSpec(int level[3])   // (read at every rt_create: a host may cha
   if(e && strlen(e) == 3 && strspn(e, "-0+") == 3) { for(int i = 0; i < 3; i++) level[i] = e[i] == '+' ? 1 : (e[i] == '-' ? -1 : 0); }
   else if(e) { const int m = atoi(e); level[0] = 0; level[1] = (m == 1 || m == 2) ? 1 : 0; level[2] = (m == 1 || m == 3) ? 1 : 0; }
 }
-static hipError_t createStreamLevel(hipStream_t* s, int which, int level);
-static hipError_t createStream(hipStream_t* s, int which, bool high) { return createStreamLevel(s, which, high ? 1 : 0); }
 static std::atomic<int> g_streamsCreated{0};   // HIP streams this library has created in the process so far (a stream's worth depends on its place in that order)
-static hipError_t createStreamLevelRaw(hipStream_t* s, int which, int level);
-static hipError_t createStreamLevel(hipStream_t* s, int which, int level)
+static hipError_t createStreamLevel(hipStream_t* s, int level)
 {
-  const hipError_t e = createStreamLevelRaw(s, which, level);
-  if(e == hipSuccess) g_streamsCreated.fetch_add(1);
-  return e;
-}
-static hipError_t createStreamLevelRaw(hipStream_t* s, int which, int level)
-{
-  const bool high = level > 0;
-  int lo, hi;
-  if(cuSplitRange(which, lo, hi)) {
-    uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for(int b = 8 * lo; b < 8 * hi; b++) mask[b >> 5] |= 1u << (b & 31);
-    return hipExtStreamCreateWithCUMask(s, 8, mask);
-  }
   int plo = 0, phi = 0;
   (void)hipDeviceGetStreamPriorityRange(&plo, &phi);
-  if(level < 0 && phi < plo) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, plo);   // (numerically larger = lower priority)
-  return (high && phi < plo) ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, phi) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+  hipError_t e;
+  if(level < 0 && phi < plo) e = hipStreamCreateWithPriority(s, hipStreamNonBlocking, plo);   // (numerically larger = lower priority)
+  else e = (level > 0 && phi < plo) ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, phi) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+  if(e == hipSuccess) g_streamsCreated.fetch_add(1);
+  return e;
 }
 
 template <class T> static int upload(rt_ctx* c, std::vector<void*>& pool, const T* src, size_t count, const T** out)
@@ -370,7 +341,7 @@ int rtCreateWithLevels(rt_ctx** out, int device, const int* levels)
   {
     prioSpec(c->prio); c->prioFromEnv = getenv("RESTIR_PRIO") != nullptr; c->prioDecided = c->prioFromEnv;
     if(levels) { for(int i = 0; i < 3; i++) c->prio[i] = std::max(-1, std::min(1, levels[i])); c->prioDecided = c->prioExplicit = true; }
-    bool ok = createStreamLevel(&c->ownStream, 0, c->prio[0]) == hipSuccess;
+    bool ok = createStreamLevel(&c->ownStream, c->prio[0]) == hipSuccess;
     if(!ok) { g_createErr = "rt_create: hipStreamCreate failed"; rt_destroy(c); return RT_ERR_HIP; }
     c->mainIdx = g_streamsCreated.load() - 1;
     c->stream = c->ownStream;
@@ -401,7 +372,6 @@ int rt_destroy(rt_ctx* c)
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
-  for(hipStream_t q : c->padStreams) if(q) (void)hipStreamDestroy(q);
   for(hipStream_t& q : c->indStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
   for(hipStream_t& q : c->sideStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
   c->indStream = c->sideStream = nullptr;
@@ -588,8 +558,8 @@ static void sceneKey(const rt_ctx* c, uint64_t& h0, uint64_t& h1)
   }
   // the builder's settings are part of what is cached: a host that changes RESTIR_BVH_* between two contexts of one process gets the tree it asked for, not the first
   // one's (advisor finding of round 5)
-  for(const char* name : {"RESTIR_BVH_SPLIT", "RESTIR_BVH_SPLIT_BUDGET", "RESTIR_BVH_SPLIT_ALPHA", "RESTIR_BVH_SPLIT_WORK", "RESTIR_BVH_BUDGET_RULE", "RESTIR_BVH_ROTATE", "RESTIR_BVH_ROTATE_GG",
-                           "RESTIR_BVH_REINSERT", "RESTIR_BVH_BINS", "RESTIR_BVH_SBINS", "RESTIR_BVH_SLOTCOST", "RESTIR_BVH_COLLAPSE", "RESTIR_BVH_SLOTS", "RESTIR_BVH_PAR_MIN", "RESTIR_BVH_SEQ_MAX"}) {
+  for(const char* name : {"RESTIR_BVH_SPLIT", "RESTIR_BVH_SPLIT_BUDGET", "RESTIR_BVH_SPLIT_ALPHA", "RESTIR_BVH_SPLIT_WORK", "RESTIR_BVH_ROTATE", "RESTIR_BVH_ROTATE_GG",
+                           "RESTIR_BVH_REINSERT", "RESTIR_BVH_PAR_MIN", "RESTIR_BVH_SEQ_MAX"}) {
     const char* v = getenv(name);
     hashBytes(name, strlen(name), h0, h1);
     if(v) hashBytes(v, strlen(v) + 1, h0, h1);
@@ -773,7 +743,6 @@ int rt_resize(rt_ctx* c, int w, int h)
   RT_SCRATCH(geomN, n, float4); RT_SCRATCH(geomP, n, float4); RT_SCRATCH(geomNh, nh, float4); RT_SCRATCH(geomPh, nh, float4);
   RT_SCRATCH(postRowSums, size_t(h) * 6, double); RT_SCRATCH(postMean, 8, float);
   RT_SCRATCH(postMipD, n + 64, float4); RT_SCRATCH(postMipI, n + 64, float4);   // levels 1..7 (n/3 texels; up to n for one-pixel-wide images)
-  RT_SCRATCH(rowCost, 4096 + 64, uint32_t); RT_SCRATCH(rowOrder, 4096 + 64, uint16_t);
   RT_SCRATCH(tileOrder, (size_t(w / 2 + 7) / 8) * (size_t(h / 2 + 7) / 8 + 16 * 2) + 64 + 4096, uint32_t);   // 8 per-XCD lists: tiles + one chunk of slack each
 #if RT_WAVEPROF
   RT_SCRATCH(waveProf, WAVEPROF_RECORDS * 16, uint32_t);
@@ -795,7 +764,7 @@ static int ensureStackOverflow(rt_ctx* c)
   if(!(stackLdsEnv() || c->overlap >= 2)) return RT_OK;
   if(!c->haveAccel || c->W <= 0 || c->ds.stackTotal <= stackLdsMin()) return RT_OK;
   const size_t tilesX = size_t(c->W + 7) / 8, tilesY = size_t(c->H + 7) / 8;
-  const size_t blocks = std::max<size_t>(16384, tilesX * tilesY + 8 * tilesX + 1024);   // >= any traced grid: tileGrid() of the full frame; 4 waves per half-res tile; persistent launches
+  const size_t blocks = std::max<size_t>(16384, tilesX * tilesY + 8 * tilesX + 1024);   // >= any traced grid: tileGrid() of the full frame; 4 waves per half-res tile
   const size_t bytes = blocks * 64 * size_t(c->ds.stackTotal - stackLdsMin()) * sizeof(uint2);
   void* p[2] = {nullptr, nullptr};
   for(int i = 0; i < 2; i++) { RT_HIP(c, hipMalloc(&p[i], bytes)); c->ovfAllocs.push_back(p[i]); }
@@ -825,13 +794,8 @@ static hipError_t ensureOverlapStreams(rt_ctx* c)
   hipError_t e = hipSuccess;
   hipStream_t& side = c->sideStreams[c->prio[2] + 1];
   hipStream_t& ind = c->indStreams[c->prio[1] + 1];
-  // probe (round 5, scripts/r05_stream_pad_probe.sh): RESTIR_STREAM_PAD="a,b[,level]" creates a / b idle streams before the filter / the indirect stream — how a stream's
-  // position in the process's creation order maps to the hardware queue it shares
-  static int padA = -1, padB = 0, padL = 0;
-  if(padA < 0) { padA = 0; if(const char* pe = getenv("RESTIR_STREAM_PAD")) (void)sscanf(pe, "%d,%d,%d", &padA, &padB, &padL); }
-  auto pad = [&](int n) { for(int i = 0; i < n; i++) { hipStream_t d = nullptr; (void)createStreamLevel(&d, 2, padL); c->padStreams.push_back(d); } };
-  if(!side) { pad(padA); e = createStreamLevel(&side, 2, c->prio[2]); if(e == hipSuccess) c->sideIdx[c->prio[2] + 1] = g_streamsCreated.load() - 1; }
-  if(e == hipSuccess && !ind) { pad(padB); e = createStreamLevel(&ind, 1, c->prio[1]); if(e == hipSuccess) c->indIdx[c->prio[1] + 1] = g_streamsCreated.load() - 1; }
+  if(!side) { e = createStreamLevel(&side, c->prio[2]); if(e == hipSuccess) c->sideIdx[c->prio[2] + 1] = g_streamsCreated.load() - 1; }
+  if(e == hipSuccess && !ind) { e = createStreamLevel(&ind, c->prio[1]); if(e == hipSuccess) c->indIdx[c->prio[1] + 1] = g_streamsCreated.load() - 1; }
   c->sideStream = side; c->indStream = ind;
   return e;
 }
@@ -872,10 +836,6 @@ static DevFrame makeFrame(rt_ctx* c, int frames)
   const DevFrame& X = c->scratch;
   F.surf = X.surf; F.status = X.status; F.qcount = X.qcount; F.waveProf = X.waveProf;
   F.histRow0 = c->histRow0; F.histRow1 = c->histRow1; F.histMiss = X.qcount + 250;
-  // (measured, profiles/r05_row_order_ab.txt: -1.1 % in flight on the real scene and on config 3, +0.9 % on lite and under a moving camera, the stage ALONE 2-12 % slower —
-  //  the heavy rows then all run at once instead of between cheap ones.  Off unless RESTIR_ROW_ORDER=1.)
-  { static const bool rowOrderOn = getenv("RESTIR_ROW_ORDER") && atoi(getenv("RESTIR_ROW_ORDER")) != 0;
-    F.rowCost = rowOrderOn ? X.rowCost : nullptr; F.rowOrder = rowOrderOn ? X.rowOrder : nullptr; }
   F.geomN = X.geomN; F.geomP = X.geomP; F.geomNh = X.geomNh; F.geomPh = X.geomPh; F.tileOrder = X.tileOrder; F.postRowSums = X.postRowSums; F.postMean = X.postMean;
   return F;
 }

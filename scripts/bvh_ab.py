@@ -13,7 +13,7 @@ r.update(W, H); r.set_overlap(0)
 sc.updateCamera(W, H)
 for f in range(4):
     st.time = 1000 + f; sc.updateCamera(W, H); r.set_camera(sc.getCamera()); r.run(st, f)
-out = [KIND, "split=%s alpha=%s collapse=%s" % (os.environ.get("RESTIR_BVH_SPLIT", "default"), os.environ.get("RESTIR_BVH_SPLIT_ALPHA", "default"), os.environ.get("RESTIR_BVH_COLLAPSE", "greedy")),
+out = [KIND, "split=%s alpha=%s" % (os.environ.get("RESTIR_BVH_SPLIT", "default"), os.environ.get("RESTIR_BVH_SPLIT_ALPHA", "default")),
        str(r.accel_stats()), "upload + build %.2fs" % tb]
 for stage, name in ((abi.STAGE_DIRECT, "direct"), (abi.STAGE_INDIRECT, "indirect")):
     r.sync(); t0 = time.perf_counter()

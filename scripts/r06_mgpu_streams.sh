@@ -1,13 +1,10 @@
 #!/bin/bash
 # Round 6, verdict item 1: the hardware-queue finding of round 5 carried into both multi-GPU hosts and into the emulation.  usage (gpurun): bash scripts/r06_mgpu_streams.sh <tag> [N]
-#  1. one band through every host, each in a fresh process (scripts/r06_host_period.py): context streams vs torch's pool, created before / after the process group
-#  2. bench.py --emulate-world N (default 8) with lazy per-rank streams, --solo-fresh 2: the two slowest ranks again in processes of their own
-#  3. RESTIR_MGPU_PRIO sweep: the slowest and a middle rank of that partition, one fresh process per (rank, setting)
+#  1. bench.py --emulate-world N (default 8) with lazy per-rank streams, --solo-fresh 2: the two slowest ranks again in processes of their own
+#  2. RESTIR_MGPU_PRIO sweep: the slowest and a middle rank of that partition, one fresh process per (rank, setting)
 R=$GRAFT_REPO_ROOT; T=${1:-r06m}; N=${2:-8}; O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
-echo "== 1. one band per host (ms/frame, fresh process each)" | tee $O/summary.txt
-timeout 1500 python scripts/r06_host_period.py --reps 2 2> $O/host_period.err | tee $O/host_period.txt | grep -v '^{' | tee -a $O/summary.txt
-echo "== 2. emulate $N ranks, 1080p, lazy streams, --solo-fresh 2" | tee -a $O/summary.txt
+echo "== 1. emulate $N ranks, 1080p, lazy streams, --solo-fresh 2" | tee $O/summary.txt
 timeout 1500 python bench.py --emulate-world $N --solo-fresh 2 --no-cpu-baseline > $O/emulate$N.json 2> $O/emulate$N.err || tail -3 $O/emulate$N.err
 python - $O/emulate$N.json $N <<'PY' | tee -a $O/summary.txt
 import json, sys
@@ -24,7 +21,7 @@ order = sorted(range(len(per)), key=lambda q: -per[q])
 open(sys.argv[1] + ".part", "w").write(",".join(str(x[0]) for x in b) + "," + str(b[-1][1]) + "\n%d %d\n" % (order[0], order[len(order) // 2]))
 PY
 PART=$(head -1 $O/emulate$N.json.part); RANKS=$(tail -1 $O/emulate$N.json.part)
-echo "== 3. RESTIR_MGPU_PRIO sweep (main / indirect / filter), ranks $RANKS of partition $PART, fresh process each" | tee -a $O/summary.txt
+echo "== 2. RESTIR_MGPU_PRIO sweep (main / indirect / filter), ranks $RANKS of partition $PART, fresh process each" | tee -a $O/summary.txt
 for rep in 1 2; do for prio in +00 0+0 0++ 000 ++0; do for q in $RANKS; do
   RESTIR_MGPU_PRIO=$prio timeout 600 python bench.py --emulate-world $N --emulate-child "$q:$PART" --no-cpu-baseline 2> $O/child.err | grep '^{' | python -c "
 import json,sys

@@ -1,10 +1,9 @@
 #!/bin/bash
-# r06e: changed GPU tests; builder on the box; persistent waves under PMC; typed vs generic accessors in the wave profile; emulation set with the round-6 stream layout;
+# r06e: changed GPU tests; builder on the box; emulation set with the round-6 stream layout;
 # the glTF path at BASELINE scale; the driver's 8-rank command line on one device with its wall time
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06e; mkdir -p $O; cd $R
 (timeout 1500 python -m pytest tests/test_gpu_bench_cli.py tests/test_gpu_tiled_rccl.py tests/test_gpu_stream_prio.py tests/test_gpu_mgpu.py "tests/test_gpu_fullsize_allstages.py::test_config3_sponza_1k_textures_1080p_all_stages" -m gpu -x -q > $O/gputests.log 2>&1; grep -n "passed\|failed\|Error" $O/gputests.log | tail -5)
 echo "== builder"; bash scripts/r06_bvh_build.sh r06e_bvh 2>&1 | head -24
-echo "== persistent waves under PMC"; bash scripts/r06_persist_pmc.sh r06e_persist_pmc
 echo "== via glTF at BASELINE scale"
 timeout 1500 python bench.py --via-gltf --no-cpu-baseline > $O/bench_via_gltf.json 2> $O/bench_via_gltf.err || tail -5 $O/bench_via_gltf.err
 python -c "
@@ -26,4 +25,3 @@ HSA_ENABLE_IPC_MODE_LEGACY=0 RESTIR_BENCH_SHARE_DEVICE=1 RESTIR_DIST_BACKEND=glo
 echo "exit $? wall $(( $(date +%s) - s )) s"
 python -c "
 import json; d=json.loads([l for l in open('$O/bench_eight_ranks_shared_device.json') if l.startswith('{')][-1]); print({k: d.get(k) for k in ('value','ms_per_step','host','faster_host','wall_s','tiled_equals_untiled','hosts_all_verified','stream_layout')}); print(d.get('hosts'))"
-echo "== typed vs generic accessors in the wave profile"; bash scripts/r06_addrspace_wave.sh r06e_as > /dev/null 2>&1; cat $R/gpurun_out/r06e_as/summary.txt | head -80

@@ -275,12 +275,10 @@ def test_cpp_demo_application_matches_python_host(tmp_path):
     assert np.array_equal(r.readback(abi.BUF_LDR).reshape(H, W, 4)[..., :3], ldr)
 
 
-@pytest.mark.parametrize("persist", [1, 2, 3, 5])
-def test_persistent_multibounce_waves_bit_exact(persist, monkeypatch):
-    """Round 6: the multi-bounce tiles of LARGE indirect launches (> 3072 half-res tiles: the three-tiles-per-wave single-bounce body + persistent waves that regenerate a
-    path per lane from their XCD's tile list, csrc/stages.hip indirectMultiBouncePersistent) against the oracle: full frames of 1040 x 784 (65 x 49 half-res tiles), maxDepth 4,
-    temporal reuse under a moving camera, a scene with sky pixels (lanes that pull a pixel without a surface), RESTIR_IND_PERSIST tiles' worth of pixels per wave."""
-    monkeypatch.setenv("RESTIR_IND_PERSIST", str(persist))
+def test_large_launch_indirect_bit_exact():
+    """The shipped path of LARGE indirect launches (> 3072 half-res tiles: the three-tiles-per-wave single-bounce body + the generic multi-bounce body, one wave per
+    tile from its XCD's tile list) against the oracle: full frames of 1040 x 784 (65 x 49 half-res tiles), maxDepth 4, temporal reuse under a moving camera, a scene
+    with sky pixels."""
     W, H = 1040, 784
     sc, env = make_scene(abi.PROC_BISTRO_EXT_REAL, 0.01, 1, (256, 128))
     st = host.default_state(W, H, sc, env)
