@@ -86,6 +86,21 @@ BUFFER_NAMES = ["gbuffer0", "gbuffer1", "motion", "direct_resv0", "direct_resv1"
                 "indirect_result0", "indirect_result1", "light_id0", "light_id1", "ldr"]
 # rt_reference_readback components
 REF_DIRECT, REF_INDIRECT, REF_SUM = range(3)
+# rt_status (include/rt_abi.h)
+(OK, ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NO_SCENE, ERR_NO_ACCEL, ERR_NO_TARGET, ERR_OOM) = (0, -1, -2, -3, -4, -5, -6, -7)
+# rt_set_denoiser (include/rt_abi.h "Denoiser selection"); rt_denoiser_readback ids
+DENOISER_ATROUS, DENOISER_SVGF = range(2)
+SVGF_DIRECT_COLOR, SVGF_INDIRECT_COLOR, SVGF_DIRECT_MOMENTS, SVGF_INDIRECT_MOMENTS = range(4)
+
+
+class Denoiser(C.Structure):  # rt_denoiser, 32 B; defaults = the library's
+    _fields_ = [("mode", C.c_int32), ("alphaColor", C.c_float), ("alphaMoments", C.c_float), ("historyCap", C.c_int32),
+                ("phiLumDirect", C.c_float), ("phiLumIndirect", C.c_float), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, **kw):
+        d = dict(mode=DENOISER_ATROUS, alphaColor=0.2, alphaMoments=0.2, historyCap=32, phiLumDirect=4.0, phiLumIndirect=4.0)
+        d.update(kw)
+        super().__init__(**d)
 # rt_stage_id
 (STAGE_DIRECT, STAGE_INDIRECT, STAGE_DENOISE_DIRECT, STAGE_DENOISE_INDIRECT, STAGE_COMPOSE, STAGE_DIRECT_GEN, STAGE_DIRECT_REUSE) = range(7)
 # rt_restir_state

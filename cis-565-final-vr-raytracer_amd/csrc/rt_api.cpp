@@ -21,6 +21,7 @@
 #include "bvh8_builder.h"
 #include "stages.h"
 #include "reference.h"
+#include "svgf.h"
 
 using namespace rt;
 
@@ -94,6 +95,12 @@ struct rt_ctx {
   uint32_t refN = 0;           // samples in refAcc; 0 = the sums are stale and are cleared by the next rt_reference_render
   bool refKeyValid = false;    // the RtxState inputs of the integral the sums were taken with (the others reset refN where they change)
   int32_t refMaxDepth = 0, refMIS = 0; float refHdrMultiplier = 0.f, refEnvironmentProb = 0.f;
+  // rt_set_denoiser (csrc/svgf.hip).  SVGF history: [frame parity][direct colour + n, indirect colour + n, direct moments, indirect moments], allocated by the
+  // first frame rendered in SVGF mode, freed by rt_resize / rt_destroy.  Frame f reads parity (f + 1) & 1 and writes f & 1.
+  rt_denoiser den{RT_DENOISER_ATROUS, 0.2f, 0.2f, 32, 4.0f, 4.0f, {0, 0}};
+  void* svgfHist[2][4] = {};
+  bool svgfValid = false;    // the history of parity svgfParity may be read by the next frame (host-side, consumed when a frame is enqueued)
+  int svgfParity = -1;       // parity of the last SVGF frame (-1: none since the history was allocated)
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -248,6 +255,12 @@ static void buildOpacityMap(const AlphaRec& a, const std::vector<uint8_t>* alpha
 }
 
 static int fail(rt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+// the SVGF history (the caller has drained the context)
+static void freeSvgfHistory(rt_ctx* c)
+{
+  for(auto& par : c->svgfHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
+  c->svgfValid = false; c->svgfParity = -1;
+}
 
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
 // default —, 3 filter stream high) or three characters over {-, 0, +} for the main (direct stage) / indirect / filter stream: "+00" = main stream high, "0+-" =
@@ -382,6 +395,7 @@ int rt_destroy(rt_ctx* c)
   if(c->dPick) (void)hipFree(c->dPick);
   if(c->refAcc) (void)hipFree(c->refAcc);
   if(c->refMean) (void)hipFree(c->refMean);
+  freeSvgfHistory(c);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
@@ -449,6 +463,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   freePool(c->sceneAllocs); freePool(c->accelAllocs);
   c->haveScene = c->haveAccel = false;
   c->refN = 0;   // a new scene: the reference sums start again
+  c->svgfValid = false;
   c->ds = DevScene{};
   c->ds.sky = (c->sunAndSky.in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
   c->primMeshes.assign(d->primMeshes, d->primMeshes + d->numPrimMeshes);
@@ -639,6 +654,7 @@ int rt_build_accel(rt_ctx* c)
   freePool(c->accelAllocs);
   c->haveAccel = false;
   c->refN = 0;
+  c->svgfValid = false;
   // Host products (BVH8, alpha records, opacity micro-maps): built once per distinct scene in this process and shared by every context that uploads
   // the same scene — the N ranks of an rt_mgpu context, or an application's contexts on several devices (1.4-1.6 s per build at 2.8 M triangles).
   std::shared_ptr<const HostAccel> ha;
@@ -704,6 +720,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   c->W = c->H = 0;
   for(void* p : {static_cast<void*>(c->refAcc), static_cast<void*>(c->refMean)}) if(p) (void)hipFree(p);
   c->refAcc = nullptr; c->refMean = nullptr; c->refN = 0;
+  freeSvgfHistory(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -813,6 +830,46 @@ static void reopenPriorityDecision(rt_ctx* c)
   c->indStream = c->sideStream = nullptr;
 }
 
+// The SVGF history of both parities (rt_render_frame's first SVGF frame; the caller has drained the context).  Zeroed: nothing reads it before a frame wrote it.
+static int allocSvgfHistory(rt_ctx* c)
+{
+  const size_t n = size_t(c->W) * c->H, nh = size_t(c->W / 2) * (c->H / 2);
+  const size_t bytes[4] = {n * sizeof(float4), nh * sizeof(float4), n * sizeof(float2), nh * sizeof(float2)};
+  for(auto& par : c->svgfHist)
+    for(int k = 0; k < 4; k++) {
+      if(hipMalloc(&par[k], std::max<size_t>(bytes[k], 256)) != hipSuccess) { par[k] = nullptr; freeSvgfHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the SVGF history failed"); }
+      RT_HIP(c, hipMemset(par[k], 0, std::max<size_t>(bytes[k], 256)));
+    }
+  RT_HIP(c, hipDeviceSynchronize());
+  c->svgfValid = false; c->svgfParity = -1;
+  return RT_OK;
+}
+
+// the arguments of one SVGF chain of frame `frames` (ind: the half-resolution indirect component)
+static SvgfArgs svgfArgs(const rt_ctx* c, const DevFrame& F, const rt_state& st, int frames, bool ind, bool histValid)
+{
+  SvgfArgs A{};
+  const int cur = frames & 1, prev = (frames + 1) & 1, k = ind ? 1 : 0;
+  A.thisG = F.thisG; A.lastG = F.lastG; A.motion = F.motion;
+  A.noisy = ind ? F.denoiseIndA : F.thisDirectResult;
+  // the A-Trous temporaries: direct DirA <-> DirB; indirect thisIndirectResult (scratch, as in the A-Trous chain) <-> the noisy buffer, read by then
+  A.bufA = ind ? F.thisIndirectResult : F.denoiseDirA;
+  A.bufB = ind ? F.denoiseIndA : F.denoiseDirB;
+  A.out = ind ? F.denoiseIndB : F.thisDirectResult;
+  A.geomN = ind ? F.geomNh : F.geomN; A.geomP = ind ? F.geomPh : F.geomP;
+  A.prevC = static_cast<const float4*>(c->svgfHist[prev][k]); A.prevM = static_cast<const float2*>(c->svgfHist[prev][2 + k]);
+  A.histC = static_cast<float4*>(c->svgfHist[cur][k]); A.histM = static_cast<float2*>(c->svgfHist[cur][2 + k]);
+  A.W = c->W; A.H = c->H;
+  A.bx = ind ? c->W / 2 : c->W; A.by = ind ? c->H / 2 : c->H;
+  A.histValid = histValid ? 1 : 0;
+  A.cap = c->den.historyCap;
+  A.alphaC = c->den.alphaColor; A.alphaM = c->den.alphaMoments;
+  A.phiLum = ind ? c->den.phiLumIndirect : c->den.phiLumDirect;
+  A.sigN = ind ? st.sigNormalIndirect : st.sigNormalDirect;
+  A.sigD = ind ? st.sigDepthIndirect : st.sigDepthDirect;
+  return A;
+}
+
 static DevFrame makeFrame(rt_ctx* c, int frames)
 {
   selectFrame(c, frames);
@@ -854,6 +911,8 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
   int rc = checkReady(c, st);
   if(rc) return rc;
   if(stage < 0 || stage >= RT_STAGE_COUNT) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: unknown stage");
+  if(c->den.mode == RT_DENOISER_SVGF && (stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT))
+    return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: the denoise stages are the A-Trous chain; this context is in SVGF mode (rt_set_denoiser), which only rt_render_frame runs");
   if(rowBegin < 0 || (rowBegin & 7)) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: rowBegin must be a non-negative multiple of 8");
   {  // levels: the filter chains have 4 / 5, the direct stage its two halves in the spatial modes, every other stage only level 0
     const bool spatial = st->ReSTIRState == RT_RESTIR_SPATIAL || st->ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
@@ -896,6 +955,9 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   // profiles/r05_prio_by_config_ab.txt), so settings cannot be compared in place — and cannot be switched later for free either.  A new target size, a new scene / tree
   // or a denoise toggle re-opens the decision (reopenPriorityDecision); an explicit rt_set_stream_priorities / RESTIR_PRIO closes it for good.
   if(c->prioDecided && !c->prioExplicit && !c->prioFromEnv && c->denoiseSeen >= 0 && (st->denoise > 0) != (c->denoiseSeen > 0)) { RT_HIP(c, syncAll(c)); reopenPriorityDecision(c); }
+  // SVGF (rt_set_denoiser) replaces both A-Trous chains at their place in every schedule; its history is allocated by the first frame that needs it
+  const bool svgf = c->den.mode == RT_DENOISER_SVGF && st->denoise > 0;
+  if(svgf && !c->svgfHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocSvgfHistory(c))) return rc; }
   const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
@@ -922,13 +984,42 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   }
   const DevFrame F = makeFrame(c, frames);
   int k = 0, lastMain = 0, lastSide = 0, lastInd = 0;
-  auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    hipError_t e = stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, c->cam, stage, level, 0, 0);
-    if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-    e = hipEventRecord(E.ev[k], strm);
+  auto record = [&](hipStream_t strm, int stage) -> int {   // end-of-launch timestamp, timed against the previous one of the stream
+    const hipError_t e = hipEventRecord(E.ev[k], strm);
     if(e != hipSuccess) { c->err = std::string("hipEventRecord: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     int& last = (strm == c->stream) ? lastMain : (strm == c->indStream ? lastInd : lastSide);
     E.stage[k] = stage; E.prev[k] = last; last = k; k++;
+    return RT_OK;
+  };
+  auto run = [&](hipStream_t strm, int stage, int level) -> int {
+    hipError_t e = stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, c->cam, stage, level, 0, 0);
+    if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    return record(strm, stage);
+  };
+  // The SVGF history this frame reads is the one the previous SVGF frame wrote, if nothing invalidated it and that frame had the other parity.
+  // The history of this frame's parity becomes valid once both chains are enqueued (svgfEnqueued); until then, and on every error return, it is not.
+  SvgfArgs svgfA[2] = {};
+  if(svgf) {
+    const bool histOk = c->svgfValid && c->svgfParity == ((frames + 1) & 1);
+    svgfA[0] = svgfArgs(c, F, *st, frames, false, histOk);
+    svgfA[1] = svgfArgs(c, F, *st, frames, true, histOk);
+    c->svgfParity = frames & 1;
+  }
+  if(st->denoise == 0 || svgf) c->svgfValid = false;
+  auto svgfEnqueued = [&]() { if(svgf) c->svgfValid = true; };
+  // one component's filter chain: the 4 / 5 A-Trous levels, or the SVGF steps; timed under the stage's RT_STAGE_DENOISE_* entry
+  auto filters = [&](hipStream_t strm, bool ind) -> int {
+    const int stage = ind ? RT_STAGE_DENOISE_INDIRECT : RT_STAGE_DENOISE_DIRECT;
+    int r;
+    if(!svgf) {
+      for(int i = 0; i < (ind ? 5 : 4); i++) if((r = run(strm, stage, i))) return r;
+      return RT_OK;
+    }
+    for(int s = 0; s < svgfSteps(ind); s++) {
+      const hipError_t e = launchSvgfStep(strm, svgfA[ind ? 1 : 0], c->cam, ind, s);
+      if(e != hipSuccess) { c->err = std::string("launchSvgfStep: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+      if((r = record(strm, stage))) return r;
+    }
     return RT_OK;
   };
   auto mark = [&](hipStream_t strm, int& last) -> hipError_t {  // start-of-chain timestamp on a stream (after its waits)
@@ -949,6 +1040,12 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     //   indirect(f) overwrites the noisy-indirect buffer of its parity, which the indirect A-Trous of f-2 read (two buffers: no wait for f-1's filters).
     // Mode 3: with the deeper rotation above the same three hazards are those of frame f-3.  Mode 2's wait closes a loop direct(f-2) -> filters(f-2) -> direct(f):
     // two periods cannot be shorter than a direct stage plus the whole filter chain of one frame, and in flight that chain is stretched to the length of a frame.
+    // SVGF (rt_set_denoiser) adds reads across frames, all covered by the same waits:
+    //   its history is double-buffered by parity: the chains of f read parity f-1 and write parity f, and every filter chain runs in order on sideStream, so
+    //   the chains of f-1 have finished writing before those of f read, and those of f-2 before those of f overwrite;
+    //   its temporal pass reads G(f-1) (lastG) and motion(f): direct(f+1) writes the G-buffer that held G(f-2) and the motion buffer of f-1, and the first
+    //   writer of G(f-1) / motion(f) is direct(f+2) (mode 3: f+3), which waits for evDone(f) (s >= depth above);
+    //   mode 3's three-deep direct image: the direct chain reads and rewrites the image of f only, which direct(f+3) overwrites after evDone(f).
     const uint64_t s = c->seq;
     const int r = int(s & 3);
     const uint64_t depth = (c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) ? 3u : 2u;
@@ -968,12 +1065,13 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
 
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evD[r], 0));
     RT_HIP(c, mark(c->sideStream, lastSide));
-    if(st->denoise > 0) for(int i = 0; i < 4; i++) if((rc = run(c->sideStream, RT_STAGE_DENOISE_DIRECT, i))) return rc;
+    if(st->denoise > 0 && (rc = filters(c->sideStream, false))) return rc;
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evI[r], 0));
     RT_HIP(c, mark(c->sideStream, lastSide));
-    if(st->denoise > 0) for(int i = 0; i < 5; i++) if((rc = run(c->sideStream, RT_STAGE_DENOISE_INDIRECT, i))) return rc;
+    if(st->denoise > 0 && (rc = filters(c->sideStream, true))) return rc;
     if((rc = run(c->sideStream, RT_STAGE_COMPOSE, 0))) return rc;
     RT_HIP(c, hipEventRecord(c->evDone[r], c->sideStream));
+    svgfEnqueued();
     c->seq = s + 1; c->inFlight = true;
     E.count = k; E.last = lastSide;
     c->evUsed++;
@@ -990,16 +1088,17 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     RT_HIP(c, hipEventRecord(c->evFork, c->stream));
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evFork, 0));
     RT_HIP(c, mark(c->sideStream, lastSide));
-    for(int i = 0; i < 4; i++) if((rc = run(c->sideStream, RT_STAGE_DENOISE_DIRECT, i))) return rc;
+    if((rc = filters(c->sideStream, false))) return rc;
     RT_HIP(c, hipEventRecord(c->evJoin, c->sideStream));
   }
   if((rc = run(c->stream, RT_STAGE_INDIRECT, 0))) return rc;
   if(st->denoise > 0) {
-    if(!fork) for(int i = 0; i < 4; i++) if((rc = run(c->stream, RT_STAGE_DENOISE_DIRECT, i))) return rc;
-    for(int i = 0; i < 5; i++) if((rc = run(c->stream, RT_STAGE_DENOISE_INDIRECT, i))) return rc;
+    if(!fork && (rc = filters(c->stream, false))) return rc;
+    if((rc = filters(c->stream, true))) return rc;
   }
   if(fork) RT_HIP(c, hipStreamWaitEvent(c->stream, c->evJoin, 0));
   if((rc = run(c->stream, RT_STAGE_COMPOSE, 0))) return rc;
+  svgfEnqueued();
   E.count = k; E.last = lastMain;
   c->evUsed++;
   if(decide) {
@@ -1292,6 +1391,56 @@ int rt_reference_tonemap(rt_ctx* c, const rt_tonemapper* tm)
   // post.frag over the two means in place of the two result images (rt_tonemap's pass, default view)
   RT_HIP(c, launchTonemap(c->stream, c->refMean, c->refMean + n, c->scratch.postRowSums, c->scratch.postMean, *tm, 0, c->W, c->H, static_cast<uint32_t*>(c->bufs[RT_BUF_LDR]),
                           c->scratch.postMipD, c->scratch.postMipI));
+  return RT_OK;
+}
+
+// ---- rt_set_denoiser: A-Trous (default) or SVGF (csrc/svgf.hip); the settings are host state read when a frame is enqueued
+int rt_set_denoiser(rt_ctx* c, const rt_denoiser* d)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!d) return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: NULL settings");
+  if(d->mode != RT_DENOISER_ATROUS && d->mode != RT_DENOISER_SVGF) return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: mode must be RT_DENOISER_ATROUS or RT_DENOISER_SVGF");
+  if(!(d->alphaColor > 0.0f && d->alphaColor <= 1.0f) || !(d->alphaMoments > 0.0f && d->alphaMoments <= 1.0f))
+    return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: alphaColor and alphaMoments must lie in (0, 1]");
+  if(d->historyCap < 1) return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: historyCap must be >= 1");
+  if(!(d->phiLumDirect > 0.0f && std::isfinite(d->phiLumDirect)) || !(d->phiLumIndirect > 0.0f && std::isfinite(d->phiLumIndirect)))
+    return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: phiLumDirect and phiLumIndirect must be positive and finite");
+  if(d->reserved[0] != 0 || d->reserved[1] != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_denoiser: reserved fields must be 0");
+  if(std::memcmp(&c->den, d, sizeof(rt_denoiser)) == 0) return RT_OK;
+  if(d->mode != c->den.mode) {   // the filter share the stream priorities were decided on has changed, like a denoise toggle
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    reopenPriorityDecision(c);
+  }
+  c->den = *d;
+  c->svgfValid = false;
+  return RT_OK;
+}
+
+int rt_get_denoiser(rt_ctx* c, rt_denoiser* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->den;
+  return RT_OK;
+}
+
+int rt_denoiser_reset(rt_ctx* c)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  c->svgfValid = false;
+  return RT_OK;
+}
+
+int rt_denoiser_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(which < 0 || which > 3) return fail(c, RT_ERR_INVALID_ARG, "rt_denoiser_readback: which must be 0 (direct colour + n), 1 (indirect colour + n), 2 (direct moments) or 3 (indirect moments)");
+  if(!c->svgfHist[0][0] || c->svgfParity < 0) return fail(c, RT_ERR_NO_TARGET, "rt_denoiser_readback: no frame has been rendered in SVGF mode since the last rt_resize");
+  const size_t px = (which & 1) ? size_t(c->W / 2) * (c->H / 2) : size_t(c->W) * c->H;
+  if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float2))) return fail(c, RT_ERR_INVALID_ARG, "rt_denoiser_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, c->svgfHist[c->svgfParity][which], bytes, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

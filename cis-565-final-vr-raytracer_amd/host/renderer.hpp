@@ -86,6 +86,32 @@ class Renderer {
     rgba.resize(size_t(m_width) * m_height * 4);
     return rt_reference_readback(m_ctx, component, rgba.data(), rgba.size() * sizeof(float)) == RT_OK;
   }
+  // Denoiser selection (include/rt_abi.h): the reference's A-Trous chain (default) or the variance-guided spatiotemporal filter its README asks for
+  // ("Future Work -> Better Denoiser"); the SVGF history resets by itself on resize, a new scene / tree, a settings change and a frame with denoise == 0.
+  bool setDenoiser(const rt_denoiser& d)
+  {
+    if(rt_set_denoiser(m_ctx, &d) != RT_OK) { fprintf(stderr, "Renderer::setDenoiser: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_denoiser getDenoiser()
+  {
+    rt_denoiser d{};
+    rt_get_denoiser(m_ctx, &d);
+    return d;
+  }
+  bool denoiserReset() { return rt_denoiser_reset(m_ctx) == RT_OK; }
+  // the SVGF history the last SVGF frame wrote: which = 0 direct colour + n (RGBA32F, W x H), 1 indirect colour + n (W/2 x H/2), 2 / 3 the moments
+  // (2 x f32 per pixel) of direct / indirect.  False before the first SVGF frame after a resize.
+  bool readDenoiserHistory(int which, std::vector<float>& out)
+  {
+    const size_t px = (which & 1) ? size_t(m_width / 2) * (m_height / 2) : size_t(m_width) * m_height;
+    out.resize(px * (which < 2 ? 4 : 2));
+    if(rt_denoiser_readback(m_ctx, which, out.data(), out.size() * sizeof(float)) != RT_OK) {
+      fprintf(stderr, "Renderer::readDenoiserHistory: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
   rt_ctx* context() { return m_ctx; }
  private:
   rt_ctx* m_ctx = nullptr;

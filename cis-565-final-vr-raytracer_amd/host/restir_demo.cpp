@@ -2,7 +2,8 @@
 //   loadEnvironmentHdr -> loadScene (Scene::load + AccelStructure::create) -> createRender -> per frame:
 //   updateFrame / Scene::updateCamera -> Renderer::run -> (post.frag's sum of the two HDR images, written to disk)
 // Usage mirrors main.cpp:52-54:  restir_demo [-f scene.gltf | -p cornell|helmet|sponza|bistro|interior] [-e env.hdr]
-//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples]
+//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf]
+// -d svgf: the variance-guided spatiotemporal denoiser (rt_set_denoiser, default settings) instead of the reference's A-Trous chain.
 // -r N: after the real-time frames, N samples per pixel of the reference mode (rt_reference_render: the converged image the frame estimates)
 //       at the last frame's camera, tonemapped like the frame into <out>_reference.png.
 #include <algorithm>
@@ -60,6 +61,14 @@ int main(int argc, char** argv)
   st.lightLuminIntegInv = 1.f / (scene.m_trigLightWeight + scene.m_puncLightWeight); st.MIS = 1;
   st.sigLuminDirect = 0.4f; st.sigNormalDirect = 0.1f; st.sigDepthDirect = 0.02f; st.denoise = 1;
   st.sigLuminIndirect = 4.f; st.sigNormalIndirect = 0.4f; st.sigDepthIndirect = 1.f;
+
+  const std::string denoiser = arg(argc, argv, "-d", "atrous");
+  if(denoiser != "atrous" && denoiser != "svgf") { fprintf(stderr, "-d must be atrous or svgf\n"); return 11; }
+  if(denoiser == "svgf") {
+    rt_denoiser d = render.getDenoiser();
+    d.mode = RT_DENOISER_SVGF;
+    if(!render.setDenoiser(d)) return 11;
+  }
 
   auto t0 = std::chrono::steady_clock::now();
   for(int f = 0; f < frames; f++) {

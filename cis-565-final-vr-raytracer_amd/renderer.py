@@ -18,6 +18,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_render_frame", "rt_run_stage", "rt_readback", "rt_upload_history", "rt_buffer_bytes", "rt_device_ptr",
                "rt_set_counting", "rt_get_counters", "rt_sync", "rt_last_error", "rt_abi_version", "rt_set_traversal", "rt_set_history_rows", "rt_history_miss", "rt_set_overlap", "rt_tonemap", "rt_set_sun_and_sky", "rt_pick", "rt_trace_rays", "rt_history_miss_stage", "rt_rotate_buffers", "rt_select_frame", "rt_measure_valu_peak", "rt_set_stream_priorities", "rt_get_stream_priorities", "rt_get_streams", "rt_get_stream_layout",
                "rt_reference_render", "rt_reference_reset", "rt_reference_samples", "rt_reference_readback", "rt_reference_tonemap",
+               "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -96,6 +97,11 @@ def hip_lib():
             L.rt_reference_samples.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
             L.rt_reference_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
             L.rt_reference_tonemap.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_denoiser"):   # the denoiser selection (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_set_denoiser.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_get_denoiser.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_denoiser_reset.argtypes = [C.c_void_p]
+            L.rt_denoiser_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -310,6 +316,29 @@ class Renderer:
         """post.frag over the two reference means -> BUF_LDR (RGBA8)"""
         tm = tm if tm is not None else abi.Tonemapper()
         self._chk(hip_lib().rt_reference_tonemap(self._h, C.byref(tm)), "rt_reference_tonemap")
+
+    # ---- denoiser selection: A-Trous (default) or SVGF (include/rt_abi.h, DESIGN.md §14)
+    def set_denoiser(self, d=None, **kw):
+        """rt_set_denoiser with an abi.Denoiser, or the library defaults overridden by keywords (set_denoiser(mode=abi.DENOISER_SVGF))"""
+        d = d if d is not None else abi.Denoiser(**kw)
+        self._chk(hip_lib().rt_set_denoiser(self._h, C.byref(d)), "rt_set_denoiser")
+
+    def get_denoiser(self):
+        d = abi.Denoiser()
+        self._chk(hip_lib().rt_get_denoiser(self._h, C.byref(d)), "rt_get_denoiser")
+        return d
+
+    def denoiser_reset(self):
+        self._chk(hip_lib().rt_denoiser_reset(self._h), "rt_denoiser_reset")
+
+    def denoiser_readback(self, which):
+        """the SVGF history the last SVGF frame wrote: abi.SVGF_DIRECT_COLOR / _INDIRECT_COLOR -> (h, w, 4) float32 (colour, n);
+        abi.SVGF_DIRECT_MOMENTS / _INDIRECT_MOMENTS -> (h, w, 2) float32 (m1, m2); the indirect ones at half resolution"""
+        W, H = self.size
+        w, h = (W // 2, H // 2) if which in (abi.SVGF_INDIRECT_COLOR, abi.SVGF_INDIRECT_MOMENTS) else (W, H)
+        out = np.empty((h, w, 4 if which in (abi.SVGF_DIRECT_COLOR, abi.SVGF_INDIRECT_COLOR) else 2), dtype=np.float32)
+        self._chk(hip_lib().rt_denoiser_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_denoiser_readback")
+        return out
 
     def accel_stats(self):
         n, t, d = C.c_uint64(), C.c_uint64(), C.c_int()

@@ -543,11 +543,50 @@ int rt_reference_samples(rt_ctx* ctx, uint32_t* n);
 int rt_reference_readback(rt_ctx* ctx, int component, float* dst, size_t bytes);
 /* rt_tonemap's pass (post.frag, default view) over the direct and indirect means in place of the frame's two result images -> RT_BUF_LDR. */
 int rt_reference_tonemap(rt_ctx* ctx, const rt_tonemapper* tm);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Denoiser selection (added within ABI 2.4, no version bump): the filter that turns the two noisy, demodulated, LDR-encoded colour images of a frame
+ * (HDRToLDR(clampRadiance(x)): the direct image and the half-resolution indirect image) into the images compose reads.
+ *   RT_DENOISER_ATROUS (default)  the reference's edge-aware A-Trous chain (denoise_direct.comp / denoise_indirect.comp), fixed luminance sigma sigLumin*.
+ *   RT_DENOISER_SVGF              variance-guided spatiotemporal filter, per component, in the same signal domain:
+ *     (a) temporal accumulation: previous pixel q = motion(p) (direct) / motion(2p) >> 1 (indirect); q is consistent when it lies in the image, the previous
+ *         G-buffer at q (2q for indirect) has the same material hash, dot(n, n_prev) > 0.9 and |cam.lastPosition - position| < depth_prev * 1.05 (the temporal
+ *         test of the direct stage).  n = consistent ? min(n_prev + 1, historyCap) : 1; a = max(alphaColor, 1/n), am = max(alphaMoments, 1/n);
+ *         C = mix(C_prev, c, a), m1 = mix(m1_prev, l, am), m2 = mix(m2_prev, l^2, am) with l = luminance(c).  Pixels without a valid material get what the
+ *         A-Trous chain writes there and cleared history.
+ *     (b) variance: n >= 4: max(0, m2 - m1^2); else the same over a 7x7 neighbourhood of moments weighted by the normal and depth terms, same material only.
+ *     (c) 4 (direct) / 5 (indirect) A-Trous levels, step 2^level, the 5x5 kGauss weights, the A-Trous normal and depth terms, luminance term
+ *         exp(-|l_p - l_q| / (phiLum * sqrt(g3x3(var)_p) + 1e-10)); colour = sum(w c) / sum(w), variance = sum(w^2 var) / sum(w)^2; the filtered colour of
+ *         level 0 becomes the colour history; the last level applies LDRToHDR (direct -> RT_BUF_DIRECT_RESULT, indirect -> RT_BUF_DENOISE_IND_B).
+ *   History (colour + n, moments; per component) is double-buffered by frame parity, allocated by the first frame rendered in SVGF mode and freed by rt_resize /
+ *   rt_destroy.  It is invalid (every valid pixel restarts at n = 1) after rt_resize, rt_upload_scene, rt_build_accel, an rt_set_denoiser that changes anything,
+ *   a frame rendered with denoise == 0, rt_denoiser_reset, and a frame whose parity does not follow the previous SVGF frame's.
+ *   rt_run_stage of RT_STAGE_DENOISE_DIRECT / _INDIRECT on a context in SVGF mode is RT_ERR_INVALID_ARG (row-tiled hosts keep the A-Trous chain).
+ *   Timings accumulate under the RT_STAGE_DENOISE_* entries of rt_counters.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_DENOISER_ATROUS = 0 /* default: the reference's filter */, RT_DENOISER_SVGF = 1 };
+typedef struct {
+  int32_t mode;          /* RT_DENOISER_* */
+  float alphaColor;      /* (0, 1]: colour history blend factor floor */
+  float alphaMoments;    /* (0, 1]: moments history blend factor floor */
+  int32_t historyCap;    /* >= 1: longest history n counts */
+  float phiLumDirect;    /* > 0, finite: luminance edge-stopping scale of the direct filter */
+  float phiLumIndirect;  /* > 0, finite: ... of the indirect filter */
+  int32_t reserved[2];   /* must be 0 */
+} rt_denoiser;           /* 32 B; defaults: ATROUS, 0.2, 0.2, 32, 4.0, 4.0 */
+/* validates every field (bad values: RT_ERR_INVALID_ARG, the settings in use stay); a change of mode re-opens the stream-priority decision like a denoise toggle */
+int rt_set_denoiser(rt_ctx* ctx, const rt_denoiser* d);
+int rt_get_denoiser(rt_ctx* ctx, rt_denoiser* out);
+/* the next SVGF frame starts without history */
+int rt_denoiser_reset(rt_ctx* ctx);
+/* the history the last SVGF frame wrote: which = 0 direct colour + n (RGBA32F, W * H * 16 B), 1 indirect colour + n (RGBA32F, (W/2) * (H/2) * 16 B),
+ * 2 direct moments (m1, m2 as 2 x f32, W * H * 8 B), 3 indirect moments ((W/2) * (H/2) * 8 B).  RT_ERR_NO_TARGET before the first SVGF frame.  Synchronous. */
+int rt_denoiser_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
+/* ABI version: (major<<16)|minor.  2.4: + the denoiser selection (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; an opt-in addition
+ * that changes no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
 #define RT_ABI_VERSION_MINOR 4u
@@ -568,6 +607,7 @@ static_assert(sizeof(rt_trig_light) == 96, "TrigLight host_device.h:314-325");
 static_assert(sizeof(rt_light_buf_info) == 16, "LightBufInfo host_device.h:327-333");
 static_assert(sizeof(rt_tonemapper) == 48, "Tonemapper host_device.h:336-351");
 static_assert(sizeof(rt_sun_and_sky) == 96, "SunAndSky host_device.h:353-377");
+static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
 #endif
 
 #endif /* RT_ABI_H */

@@ -8,11 +8,16 @@ the pixels whose primary ray hits a surface (G-buffer depth < infinity):
   median_px_ratio  median over pixels of (frame luminance / reference luminance) — not dominated by the few brightest pixels
   rel_rmse     RMS of (frame average - reference) over pixels and channels / mean of the reference over pixels and channels
   out_3sigma   share of pixels whose luminance difference exceeds 3 sigma of the reference's own mean (sigma from B batch means of the reference)
+  flicker      frame-to-frame noise: the mean over pixels of the per-pixel standard deviation of the luminance over the K frames (fixed camera) / the mean
+               luminance of the reference
+--denoiser selects the filter of the real-time frames (rt_set_denoiser), one JSON line per entry: `atrous` (the default), `svgf` (library defaults) or
+`svgf:key=value:...` with rt_denoiser fields (alphaColor, alphaMoments, historyCap, phiLumDirect, phiLumIndirect) — the reference is taken once per configuration.
 The reference ignores the real-time state (its sums are taken once per configuration); every frame of the average uses the same camera (its history matrices
 advanced per frame, as SampleExample::updateFrame does), time = 1000 + f.
 Config 2 runs the whole frame here (bench.py times the direct stage alone for it).
 
   python scripts/reference_bias.py [--configs 2 3 4] [--frames 64] [--warmup 8] [--spp 256] [--batches 8] [--out profiles/reference_bias.jsonl]
+  python scripts/reference_bias.py --denoiser atrous svgf --variants default [--out profiles/denoiser_svgf.jsonl]      # the denoiser A/B
   python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]       # reference time per sample at the configuration's size (host-timed, synchronised)
   python scripts/reference_bias.py --rays-per-path [--configs 4 2]         # CPU only: ray queries per path of the CPU restatement (tests/refpt_checker.cpp)
 """
@@ -74,8 +79,24 @@ def reference(r, st, spp, batches):
     return [r.reference_readback(c)[..., :3].astype(np.float64) for c in range(3)], sigma, secs
 
 
+def denoiser_settings(spec):
+    """`atrous` | `svgf` | `svgf:key=value:...` -> (label, abi.Denoiser)"""
+    parts = spec.split(":")
+    if parts[0] not in ("atrous", "svgf"):
+        raise SystemExit(f"--denoiser {spec}: atrous or svgf[:key=value...]")
+    kw = {}
+    for p in parts[1:]:
+        k, v = p.split("=")
+        kw[k] = int(v) if k == "historyCap" else float(v)
+    return spec, abi.Denoiser(mode=abi.DENOISER_SVGF if parts[0] == "svgf" else abi.DENOISER_ATROUS, **kw)
+
+
 def realtime_average(r, sc, st, frames, warmup):
-    acc = [None, None]
+    """the mean of each component over the frames after warm-up, the per-pixel standard deviation of each component's luminance over those frames,
+    and the pixels that hit a surface"""
+    acc = [None, None, None]
+    lsum = [0.0, 0.0, 0.0]
+    lsq = [0.0, 0.0, 0.0]
     for f in range(warmup + frames):
         st.time = 1000 + f
         st.frame = f
@@ -84,21 +105,28 @@ def realtime_average(r, sc, st, frames, warmup):
         r.run(st, f)
         if f >= warmup:
             cur = f & 1
-            for k, buf in enumerate((abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)):
-                img = r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
+            imgs = [r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
+                    for buf in (abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)]
+            imgs.append(imgs[0] + imgs[1])
+            for k, img in enumerate(imgs):
                 acc[k] = img if acc[k] is None else acc[k] + img
+                lum = img @ LUM
+                lsum[k] = lsum[k] + lum
+                lsq[k] = lsq[k] + lum * lum
     last = (warmup + frames - 1) & 1
     g = r.readback(abi.BUF_GBUFFER0 + last).view(np.uint32).reshape(st.size.y, st.size.x, 4)
     surface = g[..., 0].view(np.float32) < 1e28 * 0.8
     d, i = acc[0] / frames, acc[1] / frames
-    return [d, i, d + i], surface
+    std = [np.sqrt(np.maximum(lsq[k] / frames - (lsum[k] / frames) ** 2, 0.0)) for k in range(3)]
+    return [d, i, d + i], std, surface
 
 
-def metrics(frame, ref, sigma, mask):
+def metrics(frame, ref, sigma, mask, std=None):
     f, g = frame[mask], ref[mask]
     lf, lg = f @ LUM, g @ LUM
     pos = lg > 0
-    return {"lum_ratio": round(float(lf.mean() / lg.mean()), 4) if lg.mean() > 0 else None,
+    extra = {} if std is None else {"flicker": round(float(std[mask].mean() / lg.mean()), 4) if lg.mean() > 0 else None}
+    return {**extra, "lum_ratio": round(float(lf.mean() / lg.mean()), 4) if lg.mean() > 0 else None,
             "median_px_ratio": round(float(np.median(lf[pos] / lg[pos])), 4) if pos.any() else None,
             "rel_rmse": round(float(np.sqrt(((f - g) ** 2).mean()) / g.mean()), 4) if g.mean() > 0 else None,
             "out_3sigma": round(float((np.abs(lf - lg) > 3 * sigma[mask]).mean()), 4) if sigma is not None else None}
@@ -114,19 +142,20 @@ def bias(args):
         r.update(W, H)
         r.set_camera(sc.getCamera())
         ref, sigma, secs = reference(r, st0, args.spp, args.batches)
-        for vname, over in VARIANTS.items():
+        for (vname, over), (dname, den) in [(v, d) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)]:
             st = abi.RtxState.from_buffer_copy(st0)
             for k, v in over.items():
                 setattr(st, k, v)
             r.update(W, H)                                      # fresh history for every variant
+            r.set_denoiser(den)
             r.set_camera(sc.getCamera())
-            frame, surface = realtime_average(r, sc, st, args.frames, args.warmup)
-            out = {"config": config, "variant": vname, "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
+            frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup)
+            out = {"config": config, "variant": vname, "denoiser": dname, "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
                    "ref_batches": args.batches, "ref_seconds": round(secs, 2), "surface_share": round(float(surface.mean()), 4)}
             everything = np.ones_like(surface)
             for name, c in (("direct", 0), ("indirect", 1), ("sum", 2)):
-                out[name] = {"all": metrics(frame[c], ref[c], sigma if c == 2 else None, everything),
-                             "surface": metrics(frame[c], ref[c], sigma if c == 2 else None, surface)}
+                out[name] = {"all": metrics(frame[c], ref[c], sigma if c == 2 else None, everything, std[c]),
+                             "surface": metrics(frame[c], ref[c], sigma if c == 2 else None, surface, std[c])}
             line = json.dumps(out)
             print(line, flush=True)
             if args.out:
@@ -184,6 +213,8 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--denoiser", nargs="+", default=["atrous"], help="atrous | svgf | svgf:key=value:... (one run of the real-time frames per entry)")
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=list(VARIANTS))
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--rays-per-path", action="store_true")
     args = ap.parse_args()
