@@ -101,6 +101,18 @@ class Denoiser(C.Structure):  # rt_denoiser, 32 B; defaults = the library's
         d = dict(mode=DENOISER_ATROUS, alphaColor=0.2, alphaMoments=0.2, historyCap=32, phiLumDirect=4.0, phiLumIndirect=4.0)
         d.update(kw)
         super().__init__(**d)
+# rt_set_gi_spatial (include/rt_abi.h "ReSTIR GI spatial reuse")
+GI_SPATIAL_OFF, GI_SPATIAL_ON, GI_SPATIAL_VISIBILITY = range(3)
+
+
+class GiSpatial(C.Structure):  # rt_gi_spatial, 32 B; defaults = the library's
+    _fields_ = [("mode", C.c_int32), ("samples", C.c_int32), ("radius", C.c_int32), ("normalThreshold", C.c_float),
+                ("depthThreshold", C.c_float), ("jacobianMax", C.c_float), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, **kw):
+        d = dict(mode=GI_SPATIAL_OFF, samples=4, radius=10, normalThreshold=0.9, depthThreshold=0.1, jacobianMax=10.0)
+        d.update(kw)
+        super().__init__(**d)
 # rt_stage_id
 (STAGE_DIRECT, STAGE_INDIRECT, STAGE_DENOISE_DIRECT, STAGE_DENOISE_INDIRECT, STAGE_COMPOSE, STAGE_DIRECT_GEN, STAGE_DIRECT_REUSE) = range(7)
 # rt_restir_state

@@ -22,6 +22,7 @@
 #include "stages.h"
 #include "reference.h"
 #include "svgf.h"
+#include "gi_spatial.h"
 
 using namespace rt;
 
@@ -101,6 +102,10 @@ struct rt_ctx {
   void* svgfHist[2][4] = {};
   bool svgfValid = false;    // the history of parity svgfParity may be read by the next frame (host-side, consumed when a frame is enqueued)
   int svgfParity = -1;       // parity of the last SVGF frame (-1: none since the history was allocated)
+  // rt_set_gi_spatial (csrc/gi_spatial.hip).  The pass's reservoirs, allocated by the first frame rendered with the mode on, freed by rt_resize / rt_destroy.
+  rt_gi_spatial gis{RT_GI_SPATIAL_OFF, 4, 10, 0.9f, 0.1f, 10.0f, {0, 0}};
+  void* gisResv = nullptr;
+  bool gisWritten = false;   // a frame with the mode on has been enqueued since gisResv was allocated
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -261,6 +266,12 @@ static void freeSvgfHistory(rt_ctx* c)
   for(auto& par : c->svgfHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
   c->svgfValid = false; c->svgfParity = -1;
 }
+// the GI spatial reservoirs (the caller has drained the context)
+static void freeGiSpatial(rt_ctx* c)
+{
+  if(c->gisResv) (void)hipFree(c->gisResv);
+  c->gisResv = nullptr; c->gisWritten = false;
+}
 
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
 // default —, 3 filter stream high) or three characters over {-, 0, +} for the main (direct stage) / indirect / filter stream: "+00" = main stream high, "0+-" =
@@ -396,6 +407,7 @@ int rt_destroy(rt_ctx* c)
   if(c->refAcc) (void)hipFree(c->refAcc);
   if(c->refMean) (void)hipFree(c->refMean);
   freeSvgfHistory(c);
+  freeGiSpatial(c);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
@@ -721,6 +733,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   for(void* p : {static_cast<void*>(c->refAcc), static_cast<void*>(c->refMean)}) if(p) (void)hipFree(p);
   c->refAcc = nullptr; c->refMean = nullptr; c->refN = 0;
   freeSvgfHistory(c);
+  freeGiSpatial(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -870,6 +883,30 @@ static SvgfArgs svgfArgs(const rt_ctx* c, const DevFrame& F, const rt_state& st,
   return A;
 }
 
+// The GI spatial reservoirs (rt_render_frame's first frame with the mode on; the caller has drained the context)
+static int allocGiSpatial(rt_ctx* c)
+{
+  const size_t bytes = std::max<size_t>(size_t(c->W / 2) * (c->H / 2) * sizeof(rt_indirect_reservoir), 256);
+  if(hipMalloc(&c->gisResv, bytes) != hipSuccess) { c->gisResv = nullptr; return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the GI spatial reservoirs failed"); }
+  RT_HIP(c, hipMemset(c->gisResv, 0, bytes));
+  RT_HIP(c, hipDeviceSynchronize());
+  c->gisWritten = false;
+  return RT_OK;
+}
+
+// the arguments of a frame's GI spatial pass
+static GiSpatialArgs giSpatialArgs(const rt_ctx* c, const DevFrame& F)
+{
+  GiSpatialArgs A{};
+  A.thisG = F.thisG; A.resv = F.thisIndirectResv;
+  A.out = static_cast<rt_indirect_reservoir*>(c->gisResv);
+  A.indA = F.denoiseIndA;
+  A.W = c->W; A.H = c->H;
+  A.mode = c->gis.mode; A.samples = c->gis.samples; A.radius = c->gis.radius;
+  A.normalThreshold = c->gis.normalThreshold; A.depthThreshold = c->gis.depthThreshold; A.jacobianMax = c->gis.jacobianMax;
+  return A;
+}
+
 static DevFrame makeFrame(rt_ctx* c, int frames)
 {
   selectFrame(c, frames);
@@ -913,6 +950,8 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
   if(stage < 0 || stage >= RT_STAGE_COUNT) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: unknown stage");
   if(c->den.mode == RT_DENOISER_SVGF && (stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT))
     return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: the denoise stages are the A-Trous chain; this context is in SVGF mode (rt_set_denoiser), which only rt_render_frame runs");
+  if(c->gis.mode != RT_GI_SPATIAL_OFF && stage == RT_STAGE_INDIRECT)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has GI spatial reuse on (rt_set_gi_spatial), whose pass after the indirect stage only rt_render_frame runs");
   if(rowBegin < 0 || (rowBegin & 7)) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: rowBegin must be a non-negative multiple of 8");
   {  // levels: the filter chains have 4 / 5, the direct stage its two halves in the spatial modes, every other stage only level 0
     const bool spatial = st->ReSTIRState == RT_RESTIR_SPATIAL || st->ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
@@ -958,6 +997,9 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   // SVGF (rt_set_denoiser) replaces both A-Trous chains at their place in every schedule; its history is allocated by the first frame that needs it
   const bool svgf = c->den.mode == RT_DENOISER_SVGF && st->denoise > 0;
   if(svgf && !c->svgfHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocSvgfHistory(c))) return rc; }
+  // GI spatial reuse (rt_set_gi_spatial): a pass right after the indirect stage on its stream in every schedule; its reservoirs are allocated by the first frame that needs them
+  const bool gis = c->gis.mode != RT_GI_SPATIAL_OFF;
+  if(gis && !c->gisResv) { RT_HIP(c, syncAll(c)); if((rc = allocGiSpatial(c))) return rc; }
   const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
@@ -1022,6 +1064,16 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     }
     return RT_OK;
   };
+  // the indirect stage, then the GI spatial pass when the mode is on; both timed under RT_STAGE_INDIRECT
+  auto indirect = [&](hipStream_t strm) -> int {
+    int r;
+    if((r = run(strm, RT_STAGE_INDIRECT, 0))) return r;
+    if(!gis) return RT_OK;
+    const hipError_t e = launchGiSpatial(strm, c->ds, *st, c->cam, giSpatialArgs(c, F));
+    if(e != hipSuccess) { c->err = std::string("launchGiSpatial: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    c->gisWritten = true;
+    return record(strm, RT_STAGE_INDIRECT);
+  };
   auto mark = [&](hipStream_t strm, int& last) -> hipError_t {  // start-of-chain timestamp on a stream (after its waits)
     hipError_t e = hipEventRecord(E.ev[k], strm);
     E.stage[k] = -1; E.prev[k] = k; last = k; k++;
@@ -1046,6 +1098,10 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     //   its temporal pass reads G(f-1) (lastG) and motion(f): direct(f+1) writes the G-buffer that held G(f-2) and the motion buffer of f-1, and the first
     //   writer of G(f-1) / motion(f) is direct(f+2) (mode 3: f+3), which waits for evDone(f) (s >= depth above);
     //   mode 3's three-deep direct image: the direct chain reads and rewrites the image of f only, which direct(f+3) overwrites after evDone(f).
+    // GI spatial reuse (rt_set_gi_spatial) runs on indStream right after indirect(f), before evI is recorded, so stream order covers it:
+    //   it reads G(f) and the indirect reservoirs of f and rewrites IND_A of f; indirect(f+2), the next writer of that reservoir parity and of that IND_A,
+    //   runs after it on the same stream; the filters and compose of f, which read IND_A, wait on evI.  Its own reservoir buffer is rewritten by the pass of
+    //   f+1, again on indStream; rt_gi_spatial_readback drains the context first.
     const uint64_t s = c->seq;
     const int r = int(s & 3);
     const uint64_t depth = (c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) ? 3u : 2u;
@@ -1060,7 +1116,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     RT_HIP(c, hipStreamWaitEvent(c->indStream, c->evD[r], 0));
     if(s >= 2) RT_HIP(c, hipStreamWaitEvent(c->indStream, c->evDone[(s - 2) & 3], 0));   // the noisy-indirect buffer of this parity: filtered for f-2
     RT_HIP(c, mark(c->indStream, lastInd));
-    if((rc = run(c->indStream, RT_STAGE_INDIRECT, 0))) return rc;
+    if((rc = indirect(c->indStream))) return rc;
     RT_HIP(c, hipEventRecord(c->evI[r], c->indStream));
 
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evD[r], 0));
@@ -1091,7 +1147,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if((rc = filters(c->sideStream, false))) return rc;
     RT_HIP(c, hipEventRecord(c->evJoin, c->sideStream));
   }
-  if((rc = run(c->stream, RT_STAGE_INDIRECT, 0))) return rc;
+  if((rc = indirect(c->stream))) return rc;
   if(st->denoise > 0) {
     if(!fork && (rc = filters(c->stream, false))) return rc;
     if((rc = filters(c->stream, true))) return rc;
@@ -1441,6 +1497,47 @@ int rt_denoiser_readback(rt_ctx* c, int which, void* dst, size_t bytes)
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   if(bytes) RT_HIP(c, hipMemcpy(dst, c->svgfHist[c->svgfParity][which], bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// ---- rt_set_gi_spatial: ReSTIR GI spatial reuse (csrc/gi_spatial.hip); the settings are host state read when a frame is enqueued
+int rt_set_gi_spatial(rt_ctx* c, const rt_gi_spatial* s)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!s) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: NULL settings");
+  if(s->mode != RT_GI_SPATIAL_OFF && s->mode != RT_GI_SPATIAL_ON && s->mode != RT_GI_SPATIAL_VISIBILITY)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: mode must be RT_GI_SPATIAL_OFF, RT_GI_SPATIAL_ON or RT_GI_SPATIAL_VISIBILITY");
+  if(s->samples < 0 || s->samples > 16) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: samples must lie in 0..16");
+  if(s->radius < 1 || s->radius > 64) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: radius must lie in 1..64");
+  if(!(s->normalThreshold >= -1.0f && s->normalThreshold <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: normalThreshold must lie in [-1, 1]");
+  if(!(s->depthThreshold > 0.0f && std::isfinite(s->depthThreshold))) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: depthThreshold must be positive and finite");
+  if(!(s->jacobianMax >= 1.0f && std::isfinite(s->jacobianMax))) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: jacobianMax must be >= 1 and finite");
+  if(s->reserved[0] != 0 || s->reserved[1] != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_gi_spatial: reserved fields must be 0");
+  if(std::memcmp(&c->gis, s, sizeof(rt_gi_spatial)) == 0) return RT_OK;
+  if(s->mode != c->gis.mode) {   // the indirect stream's share of the frame, which the stream priorities were decided on, has changed
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    reopenPriorityDecision(c);
+  }
+  c->gis = *s;
+  return RT_OK;
+}
+
+int rt_get_gi_spatial(rt_ctx* c, rt_gi_spatial* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->gis;
+  return RT_OK;
+}
+
+int rt_gi_spatial_readback(rt_ctx* c, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(!c->gisResv || !c->gisWritten) return fail(c, RT_ERR_NO_TARGET, "rt_gi_spatial_readback: no frame has been rendered with GI spatial reuse on since the last rt_resize");
+  if(bytes != size_t(c->W / 2) * (c->H / 2) * sizeof(rt_indirect_reservoir)) return fail(c, RT_ERR_INVALID_ARG, "rt_gi_spatial_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, c->gisResv, bytes, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -112,6 +112,29 @@ class Renderer {
     }
     return true;
   }
+  // ReSTIR GI spatial reuse (include/rt_abi.h): off by default; RT_GI_SPATIAL_ON resamples each half-resolution pixel's indirect reservoir with its
+  // neighbours' after the indirect stage, RT_GI_SPATIAL_VISIBILITY also traces a shadow ray per accepted neighbour.  Nothing carries over between frames.
+  bool setGiSpatial(const rt_gi_spatial& s)
+  {
+    if(rt_set_gi_spatial(m_ctx, &s) != RT_OK) { fprintf(stderr, "Renderer::setGiSpatial: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_gi_spatial getGiSpatial()
+  {
+    rt_gi_spatial s{};
+    rt_get_gi_spatial(m_ctx, &s);
+    return s;
+  }
+  // the resampled reservoirs of the last frame rendered with the mode on, (W/2) x (H/2).  False before the first such frame after a resize.
+  bool readGiSpatialReservoirs(std::vector<rt_indirect_reservoir>& out)
+  {
+    out.resize(size_t(m_width / 2) * (m_height / 2));
+    if(rt_gi_spatial_readback(m_ctx, out.data(), out.size() * sizeof(rt_indirect_reservoir)) != RT_OK) {
+      fprintf(stderr, "Renderer::readGiSpatialReservoirs: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
   rt_ctx* context() { return m_ctx; }
  private:
   rt_ctx* m_ctx = nullptr;

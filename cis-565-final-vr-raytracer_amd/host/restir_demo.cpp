@@ -2,8 +2,9 @@
 //   loadEnvironmentHdr -> loadScene (Scene::load + AccelStructure::create) -> createRender -> per frame:
 //   updateFrame / Scene::updateCamera -> Renderer::run -> (post.frag's sum of the two HDR images, written to disk)
 // Usage mirrors main.cpp:52-54:  restir_demo [-f scene.gltf | -p cornell|helmet|sponza|bistro|interior] [-e env.hdr]
-//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf]
+//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf] [-g off|on|vis]
 // -d svgf: the variance-guided spatiotemporal denoiser (rt_set_denoiser, default settings) instead of the reference's A-Trous chain.
+// -g on|vis: ReSTIR GI spatial reuse (rt_set_gi_spatial, default settings; vis = with a visibility ray per accepted neighbour).
 // -r N: after the real-time frames, N samples per pixel of the reference mode (rt_reference_render: the converged image the frame estimates)
 //       at the last frame's camera, tonemapped like the frame into <out>_reference.png.
 #include <algorithm>
@@ -68,6 +69,13 @@ int main(int argc, char** argv)
     rt_denoiser d = render.getDenoiser();
     d.mode = RT_DENOISER_SVGF;
     if(!render.setDenoiser(d)) return 11;
+  }
+  const std::string giSpatial = arg(argc, argv, "-g", "off");
+  if(giSpatial != "off" && giSpatial != "on" && giSpatial != "vis") { fprintf(stderr, "-g must be off, on or vis\n"); return 12; }
+  if(giSpatial != "off") {
+    rt_gi_spatial g = render.getGiSpatial();
+    g.mode = giSpatial == "vis" ? RT_GI_SPATIAL_VISIBILITY : RT_GI_SPATIAL_ON;
+    if(!render.setGiSpatial(g)) return 12;
   }
 
   auto t0 = std::chrono::steady_clock::now();

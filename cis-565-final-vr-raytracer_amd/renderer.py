@@ -19,6 +19,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_counting", "rt_get_counters", "rt_sync", "rt_last_error", "rt_abi_version", "rt_set_traversal", "rt_set_history_rows", "rt_history_miss", "rt_set_overlap", "rt_tonemap", "rt_set_sun_and_sky", "rt_pick", "rt_trace_rays", "rt_history_miss_stage", "rt_rotate_buffers", "rt_select_frame", "rt_measure_valu_peak", "rt_set_stream_priorities", "rt_get_stream_priorities", "rt_get_streams", "rt_get_stream_layout",
                "rt_reference_render", "rt_reference_reset", "rt_reference_samples", "rt_reference_readback", "rt_reference_tonemap",
                "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
+               "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -102,6 +103,10 @@ def hip_lib():
             L.rt_get_denoiser.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_denoiser_reset.argtypes = [C.c_void_p]
             L.rt_denoiser_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        if hasattr(L, "rt_set_gi_spatial"):   # the GI spatial reuse (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_set_gi_spatial.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_get_gi_spatial.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_gi_spatial_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -338,6 +343,25 @@ class Renderer:
         w, h = (W // 2, H // 2) if which in (abi.SVGF_INDIRECT_COLOR, abi.SVGF_INDIRECT_MOMENTS) else (W, H)
         out = np.empty((h, w, 4 if which in (abi.SVGF_DIRECT_COLOR, abi.SVGF_INDIRECT_COLOR) else 2), dtype=np.float32)
         self._chk(hip_lib().rt_denoiser_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_denoiser_readback")
+        return out
+
+    # ---- ReSTIR GI spatial reuse (include/rt_abi.h)
+    def set_gi_spatial(self, s=None, **kw):
+        """rt_set_gi_spatial with an abi.GiSpatial, or the library defaults overridden by keywords (set_gi_spatial(mode=abi.GI_SPATIAL_ON))"""
+        s = s if s is not None else abi.GiSpatial(**kw)
+        self._chk(hip_lib().rt_set_gi_spatial(self._h, C.byref(s)), "rt_set_gi_spatial")
+
+    def get_gi_spatial(self):
+        s = abi.GiSpatial()
+        self._chk(hip_lib().rt_get_gi_spatial(self._h, C.byref(s)), "rt_get_gi_spatial")
+        return s
+
+    def gi_spatial_readback(self):
+        """the spatially resampled reservoirs of the last frame rendered with the mode on: rt_indirect_reservoir records as raw bytes,
+        (W/2) * (H/2) * 76 (the layout of rt_readback(RT_BUF_INDIRECT_RESV0))"""
+        W, H = self.size
+        out = np.empty((W // 2) * (H // 2) * 76, dtype=np.uint8)
+        self._chk(hip_lib().rt_gi_spatial_readback(self._h, out.ctypes.data, out.nbytes), "rt_gi_spatial_readback")
         return out
 
     def accel_stats(self):

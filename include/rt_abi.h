@@ -581,12 +581,55 @@ int rt_denoiser_reset(rt_ctx* ctx);
 /* the history the last SVGF frame wrote: which = 0 direct colour + n (RGBA32F, W * H * 16 B), 1 indirect colour + n (RGBA32F, (W/2) * (H/2) * 16 B),
  * 2 direct moments (m1, m2 as 2 x f32, W * H * 8 B), 3 indirect moments ((W/2) * (H/2) * 8 B).  RT_ERR_NO_TARGET before the first SVGF frame.  Synchronous. */
 int rt_denoiser_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+/* ------------------------------------------------------------------------------------------------------------------
+ * ReSTIR GI spatial reuse (added within ABI 2.4, no version bump): one pass per frame after the indirect stage, at half resolution, that
+ * resamples each pixel's indirect reservoir with up to `samples` neighbours (biased variant: no 1/Z correction).  It reads this frame's G-buffer (at 2p) and the
+ * indirect reservoirs as the indirect stage wrote them (after temporal reuse), and writes its own reservoir buffer and RT_BUF_DENOISE_IND_A.  Per pixel p:
+ *   receiver   the indirect stage's decode: ray = raySpawn(p, indSize), state from the G-buffer at 2p, position moved 2e-2 along ffnormal -> x_r, n_r = ffnormal,
+ *              wo = -ray.direction, albedo 1.  No surface: IND_A stays as the stage wrote it (0), the pass writes a zero reservoir.
+ *   seed       tea(indW * y + x, tea(time, 0x47495350)), a stream of its own; visibility rays draw alpha tests from it as every ray does.
+ *   start      r_s = the pixel's reservoir r_p, unchanged (sample, stored xv / nv, weight, num).
+ *   taps       k = 0 .. samples - 1: u1, u2, rr drawn in that order, always.  o = (floor(u1 (2R+1)) - R, floor(u2 (2R+1)) - R); skipped when o = (0, 0) or
+ *              q = p + o lies outside the half-resolution image.  Rejected unless q has a surface, the same material hash, dot(n_p, n_q) >= normalThreshold
+ *              and |d_q - d_p| <= depthThreshold * d_p (G-buffer normals and depths), r_q has num > 0, a valid weight and a valid sample, and the sample lies
+ *              in the receiver's hemisphere, dot(n_r, x_s - x_r) > 0 (sky samples: -n_s in place of x_s - x_r).
+ *              Jacobian, v_r = x_r - x_s, v_n = x_n - x_s (x_n = r_q's stored xv):
+ *                J = (|dot(n_s, v_r)| / sqrt(|v_r|^2)) * |v_n|^2 / ((|dot(n_s, v_n)| / sqrt(|v_n|^2)) * |v_r|^2), left to right, no contraction;
+ *              a sky sample (any |x_s| component >= 1e20) has J = 1.  Rejected when J is not finite, J > jacobianMax or J < 1 / jacobianMax.
+ *              RT_GI_SPATIAL_VISIBILITY: an any-hit ray from x_r towards normalize(x_s - x_r) with tmax = length(x_s - x_r) - 2e-2 (rejected when tmax <= 0),
+ *              for a sky sample along -n_s with tmax = RT_INFINITY; occluded taps are rejected.
+ *              merge: w = W_q * J (pHat = luminance(L) is the same at every receiver); r_s.weight += w; r_s.num += r_q.num; if rr * r_s.weight < w the sample
+ *              becomes r_s's with xv = x_r, nv = n_r.  A rejected tap adds nothing.
+ *   output     r_s, unclamped (nothing feeds it back), to the pass's buffer; the indirect stage's shading of r_s (BSDF at the stored xv / nv,
+ *              bigW = weight / (luminance(L) * num), clampRadiance, HDRToLDR, clampRadiance) -> RT_BUF_DENOISE_IND_A, the image the filters (or compose with
+ *              denoise == 0) read.
+ *   samples = 0 reproduces the mode-off IND_A bit for bit; the pass never writes RT_BUF_INDIRECT_RESV0 / 1; nothing carries over between frames.
+ *   The pass runs on the indirect stage's stream right after it in every schedule and every debugging_mode, and is timed under RT_STAGE_INDIRECT; it does not
+ *   feed the ray counters.  Its reservoir buffer is allocated by the first frame rendered with the mode on and freed by rt_resize / rt_destroy.
+ *   rt_run_stage(RT_STAGE_INDIRECT) on a context with the mode on is RT_ERR_INVALID_ARG (row-tiled hosts and the reference mode do not use the pass).
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_GI_SPATIAL_OFF = 0 /* default */, RT_GI_SPATIAL_ON = 1, RT_GI_SPATIAL_VISIBILITY = 2 };
+typedef struct {
+  int32_t mode;            /* RT_GI_SPATIAL_* ; default OFF */
+  int32_t samples;         /* 0..16 neighbour taps per half-res pixel; default 4 (0 = the pass runs and merges nothing) */
+  int32_t radius;          /* 1..64, half-resolution pixels; default 10 */
+  float   normalThreshold; /* [-1, 1]: dot(n_p, n_q) >= it; default 0.9 */
+  float   depthThreshold;  /* > 0, finite: |d_q - d_p| <= it * d_p; default 0.1 */
+  float   jacobianMax;     /* >= 1, finite: taps with J > it or J < 1/it are rejected; default 10 */
+  int32_t reserved[2];     /* must be 0 */
+} rt_gi_spatial;           /* 32 B */
+/* validates every field (bad values: RT_ERR_INVALID_ARG, the settings in use stay); a change of mode re-opens the stream-priority decision */
+int rt_set_gi_spatial(rt_ctx* ctx, const rt_gi_spatial* s);
+int rt_get_gi_spatial(rt_ctx* ctx, rt_gi_spatial* out);
+/* the spatially resampled reservoirs of the last frame rendered with the mode on: rt_indirect_reservoir, (W/2) * (H/2) * 76 B; synchronous;
+ * RT_ERR_NO_TARGET before the first such frame since rt_resize */
+int rt_gi_spatial_readback(rt_ctx* ctx, void* dst, size_t bytes);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + the denoiser selection (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; an opt-in addition
- * that changes no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
+/* ABI version: (major<<16)|minor.  2.4: + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
+ * (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; opt-in additions that change no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
 #define RT_ABI_VERSION_MINOR 4u
@@ -608,6 +651,7 @@ static_assert(sizeof(rt_light_buf_info) == 16, "LightBufInfo host_device.h:327-3
 static_assert(sizeof(rt_tonemapper) == 48, "Tonemapper host_device.h:336-351");
 static_assert(sizeof(rt_sun_and_sky) == 96, "SunAndSky host_device.h:353-377");
 static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
+static_assert(sizeof(rt_gi_spatial) == 32, "rt_gi_spatial");
 #endif
 
 #endif /* RT_ABI_H */

@@ -18,7 +18,8 @@ Config 2 runs the whole frame here (bench.py times the direct stage alone for it
 
   python scripts/reference_bias.py [--configs 2 3 4] [--frames 64] [--warmup 8] [--spp 256] [--batches 8] [--out profiles/reference_bias.jsonl]
   python scripts/reference_bias.py --denoiser atrous svgf --variants default [--out profiles/denoiser_svgf.jsonl]      # the denoiser A/B
-  python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]       # reference time per sample at the configuration's size (host-timed, synchronised)
+  python scripts/reference_bias.py --gi-spatial off on vis --denoiser atrous svgf --variants default [--out profiles/gi_spatial.jsonl]
+  python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]      # reference time per sample at the configuration's size (host-timed, synchronised)
   python scripts/reference_bias.py --rays-per-path [--configs 4 2]         # CPU only: ray queries per path of the CPU restatement (tests/refpt_checker.cpp)
 """
 import argparse
@@ -91,6 +92,19 @@ def denoiser_settings(spec):
     return spec, abi.Denoiser(mode=abi.DENOISER_SVGF if parts[0] == "svgf" else abi.DENOISER_ATROUS, **kw)
 
 
+def gi_spatial_settings(spec):
+    """`off` | `on` | `vis` | `on:key=value:...` with rt_gi_spatial fields (samples, radius, normalThreshold, depthThreshold, jacobianMax) -> (label, abi.GiSpatial)"""
+    parts = spec.split(":")
+    modes = {"off": abi.GI_SPATIAL_OFF, "on": abi.GI_SPATIAL_ON, "vis": abi.GI_SPATIAL_VISIBILITY}
+    if parts[0] not in modes:
+        raise SystemExit(f"--gi-spatial {spec}: off, on or vis[:key=value...]")
+    kw = {}
+    for p in parts[1:]:
+        k, v = p.split("=")
+        kw[k] = int(v) if k in ("samples", "radius") else float(v)
+    return spec, abi.GiSpatial(mode=modes[parts[0]], **kw)
+
+
 def realtime_average(r, sc, st, frames, warmup):
     """the mean of each component over the frames after warm-up, the per-pixel standard deviation of each component's luminance over those frames,
     and the pixels that hit a surface"""
@@ -142,15 +156,19 @@ def bias(args):
         r.update(W, H)
         r.set_camera(sc.getCamera())
         ref, sigma, secs = reference(r, st0, args.spp, args.batches)
-        for (vname, over), (dname, den) in [(v, d) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)]:
+        runs = [(v, d, g) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)
+                for g in map(gi_spatial_settings, args.gi_spatial)]
+        for (vname, over), (dname, den), (gname, gis) in runs:
             st = abi.RtxState.from_buffer_copy(st0)
             for k, v in over.items():
                 setattr(st, k, v)
             r.update(W, H)                                      # fresh history for every variant
             r.set_denoiser(den)
+            r.set_gi_spatial(gis)
             r.set_camera(sc.getCamera())
             frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup)
-            out = {"config": config, "variant": vname, "denoiser": dname, "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
+            out = {"config": config, "variant": vname, "denoiser": dname, **({"gi_spatial": gname} if args.gi_spatial != ["off"] else {}),
+                   "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
                    "ref_batches": args.batches, "ref_seconds": round(secs, 2), "surface_share": round(float(surface.mean()), 4)}
             everything = np.ones_like(surface)
             for name, c in (("direct", 0), ("indirect", 1), ("sum", 2)):
@@ -214,6 +232,7 @@ def main():
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--out", default="")
     ap.add_argument("--denoiser", nargs="+", default=["atrous"], help="atrous | svgf | svgf:key=value:... (one run of the real-time frames per entry)")
+    ap.add_argument("--gi-spatial", nargs="+", default=["off"], help="off | on | vis | on:key=value:... (ReSTIR GI spatial reuse; one run per entry)")
     ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=list(VARIANTS))
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--rays-per-path", action="store_true")
