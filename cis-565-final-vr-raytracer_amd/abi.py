@@ -113,6 +113,18 @@ class GiSpatial(C.Structure):  # rt_gi_spatial, 32 B; defaults = the library's
         d = dict(mode=GI_SPATIAL_OFF, samples=4, radius=10, normalThreshold=0.9, depthThreshold=0.1, jacobianMax=10.0)
         d.update(kw)
         super().__init__(**d)
+# rt_set_taa (include/rt_abi.h "Temporal anti-aliasing"); rt_taa_readback ids
+TAA_OFF, TAA_ON = range(2)
+TAA_DIRECT, TAA_INDIRECT, TAA_HISTORY_LENGTH = range(3)
+
+
+class Taa(C.Structure):  # rt_taa, 32 B; defaults = the library's
+    _fields_ = [("mode", C.c_int32), ("jitterPhases", C.c_int32), ("alpha", C.c_float), ("clipGamma", C.c_float), ("reserved", C.c_int32 * 4)]
+
+    def __init__(self, **kw):
+        d = dict(mode=TAA_OFF, jitterPhases=8, alpha=0.1, clipGamma=1.0)
+        d.update(kw)
+        super().__init__(**d)
 # rt_stage_id
 (STAGE_DIRECT, STAGE_INDIRECT, STAGE_DENOISE_DIRECT, STAGE_DENOISE_INDIRECT, STAGE_COMPOSE, STAGE_DIRECT_GEN, STAGE_DIRECT_REUSE) = range(7)
 # rt_restir_state

@@ -23,6 +23,7 @@
 #include "reference.h"
 #include "svgf.h"
 #include "gi_spatial.h"
+#include "taa.h"
 
 using namespace rt;
 
@@ -106,6 +107,14 @@ struct rt_ctx {
   rt_gi_spatial gis{RT_GI_SPATIAL_OFF, 4, 10, 0.9f, 0.1f, 10.0f, {0, 0}};
   void* gisResv = nullptr;
   bool gisWritten = false;   // a frame with the mode on has been enqueued since gisResv was allocated
+  // rt_set_taa (csrc/taa.hip).  History: [frame parity][direct, indirect, n], allocated by the first frame rendered with the mode on, freed by rt_resize /
+  // rt_destroy.  Frame f reads parity (f + 1) & 1 and writes f & 1.
+  rt_taa taa{RT_TAA_OFF, 8, 0.1f, 1.0f, {0, 0, 0, 0}};
+  void* taaHist[2][3] = {};
+  bool taaValid = false;     // the history of parity taaLast may be read by the next frame (host-side, consumed when a frame is enqueued)
+  int taaLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
+  bool taaHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame taaFrame[parity] (rt_tonemap)
+  int taaFrame[2] = {0, 0};
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -272,6 +281,12 @@ static void freeGiSpatial(rt_ctx* c)
   if(c->gisResv) (void)hipFree(c->gisResv);
   c->gisResv = nullptr; c->gisWritten = false;
 }
+// the TAA history (the caller has drained the context)
+static void freeTaaHistory(rt_ctx* c)
+{
+  for(auto& par : c->taaHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
+  c->taaValid = false; c->taaLast = -1; c->taaHeld[0] = c->taaHeld[1] = false;
+}
 
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
 // default —, 3 filter stream high) or three characters over {-, 0, +} for the main (direct stage) / indirect / filter stream: "+00" = main stream high, "0+-" =
@@ -408,6 +423,7 @@ int rt_destroy(rt_ctx* c)
   if(c->refMean) (void)hipFree(c->refMean);
   freeSvgfHistory(c);
   freeGiSpatial(c);
+  freeTaaHistory(c);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
@@ -476,6 +492,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->haveScene = c->haveAccel = false;
   c->refN = 0;   // a new scene: the reference sums start again
   c->svgfValid = false;
+  c->taaValid = false;
   c->ds = DevScene{};
   c->ds.sky = (c->sunAndSky.in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
   c->primMeshes.assign(d->primMeshes, d->primMeshes + d->numPrimMeshes);
@@ -667,6 +684,7 @@ int rt_build_accel(rt_ctx* c)
   c->haveAccel = false;
   c->refN = 0;
   c->svgfValid = false;
+  c->taaValid = false;
   // Host products (BVH8, alpha records, opacity micro-maps): built once per distinct scene in this process and shared by every context that uploads
   // the same scene — the N ranks of an rt_mgpu context, or an application's contexts on several devices (1.4-1.6 s per build at 2.8 M triangles).
   std::shared_ptr<const HostAccel> ha;
@@ -734,6 +752,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   c->refAcc = nullptr; c->refMean = nullptr; c->refN = 0;
   freeSvgfHistory(c);
   freeGiSpatial(c);
+  freeTaaHistory(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -907,6 +926,38 @@ static GiSpatialArgs giSpatialArgs(const rt_ctx* c, const DevFrame& F)
   return A;
 }
 
+// The TAA history of both parities (rt_render_frame's first frame with the mode on; the caller has drained the context).  Zeroed: nothing reads it before a
+// frame wrote it.
+static int allocTaaHistory(rt_ctx* c)
+{
+  const size_t n = size_t(c->W) * c->H;
+  const size_t bytes[3] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float)};
+  for(auto& par : c->taaHist)
+    for(int k = 0; k < 3; k++) {
+      if(hipMalloc(&par[k], std::max<size_t>(bytes[k], 256)) != hipSuccess) { par[k] = nullptr; freeTaaHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the TAA history failed"); }
+      RT_HIP(c, hipMemset(par[k], 0, std::max<size_t>(bytes[k], 256)));
+    }
+  RT_HIP(c, hipDeviceSynchronize());
+  c->taaValid = false; c->taaLast = -1; c->taaHeld[0] = c->taaHeld[1] = false;
+  return RT_OK;
+}
+
+// the arguments of the TAA resolve of frame `frames`
+static TaaArgs taaArgs(const rt_ctx* c, const DevFrame& F, int frames, bool histValid)
+{
+  TaaArgs A{};
+  const int cur = frames & 1, prev = (frames + 1) & 1;
+  A.thisG = F.thisG; A.lastG = F.lastG;
+  A.curD = F.thisDirectResult; A.curI = F.thisIndirectResult;
+  A.prevD = static_cast<const float4*>(c->taaHist[prev][0]); A.prevI = static_cast<const float4*>(c->taaHist[prev][1]);
+  A.prevN = static_cast<const float*>(c->taaHist[prev][2]);
+  A.outD = static_cast<float4*>(c->taaHist[cur][0]); A.outI = static_cast<float4*>(c->taaHist[cur][1]); A.outN = static_cast<float*>(c->taaHist[cur][2]);
+  A.W = c->W; A.H = c->H;
+  A.histValid = histValid ? 1 : 0;
+  A.alpha = c->taa.alpha; A.clipGamma = c->taa.clipGamma;
+  return A;
+}
+
 static DevFrame makeFrame(rt_ctx* c, int frames)
 {
   selectFrame(c, frames);
@@ -952,6 +1003,8 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
     return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: the denoise stages are the A-Trous chain; this context is in SVGF mode (rt_set_denoiser), which only rt_render_frame runs");
   if(c->gis.mode != RT_GI_SPATIAL_OFF && stage == RT_STAGE_INDIRECT)
     return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has GI spatial reuse on (rt_set_gi_spatial), whose pass after the indirect stage only rt_render_frame runs");
+  if(c->taa.mode != RT_TAA_OFF)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has TAA on (rt_set_taa), whose jittered camera and resolve pass only rt_render_frame runs");
   if(rowBegin < 0 || (rowBegin & 7)) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: rowBegin must be a non-negative multiple of 8");
   {  // levels: the filter chains have 4 / 5, the direct stage its two halves in the spatial modes, every other stage only level 0
     const bool spatial = st->ReSTIRState == RT_RESTIR_SPATIAL || st->ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
@@ -1000,6 +1053,12 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   // GI spatial reuse (rt_set_gi_spatial): a pass right after the indirect stage on its stream in every schedule; its reservoirs are allocated by the first frame that needs them
   const bool gis = c->gis.mode != RT_GI_SPATIAL_OFF;
   if(gis && !c->gisResv) { RT_HIP(c, syncAll(c)); if((rc = allocGiSpatial(c))) return rc; }
+  // TAA (rt_set_taa): frames with debugging_mode == 0 are rendered with the jittered camera and resolved by a pass right after compose on its stream in every
+  // schedule; its history is allocated by the first frame that needs it
+  const bool taa = c->taa.mode == RT_TAA_ON && st->debugging_mode == 0;
+  if(taa && !c->taaHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocTaaHistory(c))) return rc; }
+  rt_scene_camera cam = c->cam;   // the camera of this frame's launches (c->cam stays what rt_set_camera stored)
+  if(taa) (void)rt_taa_jitter_camera(&c->cam, frames, c->taa.jitterPhases, c->W, c->H, &cam);
   const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
@@ -1034,7 +1093,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     return RT_OK;
   };
   auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    hipError_t e = stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, c->cam, stage, level, 0, 0);
+    hipError_t e = stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
     if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     return record(strm, stage);
   };
@@ -1058,7 +1117,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       return RT_OK;
     }
     for(int s = 0; s < svgfSteps(ind); s++) {
-      const hipError_t e = launchSvgfStep(strm, svgfA[ind ? 1 : 0], c->cam, ind, s);
+      const hipError_t e = launchSvgfStep(strm, svgfA[ind ? 1 : 0], cam, ind, s);
       if(e != hipSuccess) { c->err = std::string("launchSvgfStep: ") + hipGetErrorString(e); return RT_ERR_HIP; }
       if((r = record(strm, stage))) return r;
     }
@@ -1069,10 +1128,27 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     int r;
     if((r = run(strm, RT_STAGE_INDIRECT, 0))) return r;
     if(!gis) return RT_OK;
-    const hipError_t e = launchGiSpatial(strm, c->ds, *st, c->cam, giSpatialArgs(c, F));
+    const hipError_t e = launchGiSpatial(strm, c->ds, *st, cam, giSpatialArgs(c, F));
     if(e != hipSuccess) { c->err = std::string("launchGiSpatial: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     c->gisWritten = true;
     return record(strm, RT_STAGE_INDIRECT);
+  };
+  // The TAA history this frame reads is the one the previous resolved frame wrote, if nothing invalidated it and that frame had the other parity.  The history
+  // of this frame's parity becomes valid once the pass is enqueued (resolve); until then, and on every error return, it is not.
+  TaaArgs taaA{};
+  if(taa) taaA = taaArgs(c, F, frames, c->taaValid && c->taaLast == ((frames + 1) & 1));
+  c->taaValid = false;
+  c->taaHeld[frames & 1] = false;
+  // compose, then the TAA resolve when it runs; both timed under RT_STAGE_COMPOSE
+  auto compose = [&](hipStream_t strm) -> int {
+    int r;
+    if((r = run(strm, RT_STAGE_COMPOSE, 0))) return r;
+    if(!taa) return RT_OK;
+    const hipError_t e = launchTaaResolve(strm, taaA, cam);
+    if(e != hipSuccess) { c->err = std::string("launchTaaResolve: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+    if((r = record(strm, RT_STAGE_COMPOSE))) return r;
+    c->taaValid = true; c->taaLast = frames & 1; c->taaHeld[frames & 1] = true; c->taaFrame[frames & 1] = frames;
+    return RT_OK;
   };
   auto mark = [&](hipStream_t strm, int& last) -> hipError_t {  // start-of-chain timestamp on a stream (after its waits)
     hipError_t e = hipEventRecord(E.ev[k], strm);
@@ -1102,6 +1178,12 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     //   it reads G(f) and the indirect reservoirs of f and rewrites IND_A of f; indirect(f+2), the next writer of that reservoir parity and of that IND_A,
     //   runs after it on the same stream; the filters and compose of f, which read IND_A, wait on evI.  Its own reservoir buffer is rewritten by the pass of
     //   f+1, again on indStream; rt_gi_spatial_readback drains the context first.
+    // TAA (rt_set_taa) resolves f on sideStream right after compose(f), before evDone(f) is recorded:
+    //   it reads the result images of f (written by compose on the same stream), G(f) and G(f-1) (lastG).  The first writer of G(f-1) is direct(f+2) (mode 3:
+    //   f+3), which waits for evDone(f) (s >= depth above); G(f) is next written by direct(f+3) / f+4, after evDone(f+1); mode 3's three-deep direct image of f
+    //   is overwritten by direct(f+3) after evDone(f), the indirect image of f by compose(f+2) on sideStream;
+    //   its history is double-buffered by parity: the pass of f reads parity f-1 (written by the pass of f-1, earlier on sideStream) and the parity it writes
+    //   is rewritten only by the pass of f+2, again on sideStream; rt_tonemap and rt_taa_readback join the frames in flight first.
     const uint64_t s = c->seq;
     const int r = int(s & 3);
     const uint64_t depth = (c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) ? 3u : 2u;
@@ -1125,7 +1207,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evI[r], 0));
     RT_HIP(c, mark(c->sideStream, lastSide));
     if(st->denoise > 0 && (rc = filters(c->sideStream, true))) return rc;
-    if((rc = run(c->sideStream, RT_STAGE_COMPOSE, 0))) return rc;
+    if((rc = compose(c->sideStream))) return rc;
     RT_HIP(c, hipEventRecord(c->evDone[r], c->sideStream));
     svgfEnqueued();
     c->seq = s + 1; c->inFlight = true;
@@ -1153,7 +1235,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if((rc = filters(c->stream, true))) return rc;
   }
   if(fork) RT_HIP(c, hipStreamWaitEvent(c->stream, c->evJoin, 0));
-  if((rc = run(c->stream, RT_STAGE_COMPOSE, 0))) return rc;
+  if((rc = compose(c->stream))) return rc;
   svgfEnqueued();
   E.count = k; E.last = lastMain;
   c->evUsed++;
@@ -1354,7 +1436,11 @@ int rt_tonemap(rt_ctx* c, const rt_tonemapper* tm, int debugging_mode, int frame
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, joinInFlight(c));  // the result images of `frames` are complete once compose (side stream) is done
   const int cur = frames & 1;
-  RT_HIP(c, launchTonemap(c->stream, static_cast<const float4*>(c->bufs[RT_BUF_DIRECT_RESULT0 + cur]), static_cast<const float4*>(c->bufs[RT_BUF_INDIRECT_RESULT0 + cur]),
+  // the resolved images when frame `frames` was resolved (rt_set_taa), the plain result images otherwise
+  const bool resolved = c->taaHist[cur][0] && c->taaHeld[cur] && c->taaFrame[cur] == frames;
+  const float4* dImg = static_cast<const float4*>(resolved ? c->taaHist[cur][0] : c->bufs[RT_BUF_DIRECT_RESULT0 + cur]);
+  const float4* iImg = static_cast<const float4*>(resolved ? c->taaHist[cur][1] : c->bufs[RT_BUF_INDIRECT_RESULT0 + cur]);
+  RT_HIP(c, launchTonemap(c->stream, dImg, iImg,
                           c->scratch.postRowSums, c->scratch.postMean, *tm, debugging_mode, c->W, c->H, static_cast<uint32_t*>(c->bufs[RT_BUF_LDR]),
                           c->scratch.postMipD, c->scratch.postMipI));
   return RT_OK;
@@ -1538,6 +1624,80 @@ int rt_gi_spatial_readback(rt_ctx* c, void* dst, size_t bytes)
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   if(bytes) RT_HIP(c, hipMemcpy(dst, c->gisResv, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// ---- rt_set_taa: temporal anti-aliasing (csrc/taa.hip); the settings are host state read when a frame is enqueued
+int rt_set_taa(rt_ctx* c, const rt_taa* t)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!t) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: NULL settings");
+  if(t->mode != RT_TAA_OFF && t->mode != RT_TAA_ON) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: mode must be RT_TAA_OFF or RT_TAA_ON");
+  if(t->jitterPhases < 0 || t->jitterPhases > 16) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: jitterPhases must lie in 0..16");
+  if(!(t->alpha > 0.0f && t->alpha <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: alpha must lie in (0, 1]");
+  if(!(t->clipGamma > 0.0f && std::isfinite(t->clipGamma))) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: clipGamma must be positive and finite");
+  for(int32_t r : t->reserved) if(r != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: reserved fields must be 0");
+  if(std::memcmp(&c->taa, t, sizeof(rt_taa)) == 0) return RT_OK;
+  if(t->mode != c->taa.mode) {   // compose's share of the frame, which the stream priorities were decided on, has changed
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    reopenPriorityDecision(c);
+  }
+  c->taa = *t;
+  c->taaValid = false;
+  return RT_OK;
+}
+
+int rt_get_taa(rt_ctx* c, rt_taa* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->taa;
+  return RT_OK;
+}
+
+int rt_taa_reset(rt_ctx* c)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  c->taaValid = false;
+  return RT_OK;
+}
+
+int rt_taa_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(which < 0 || which > 2) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_readback: which must be 0 (direct), 1 (indirect) or 2 (history length)");
+  if(!c->taaHist[0][0] || c->taaLast < 0) return fail(c, RT_ERR_NO_TARGET, "rt_taa_readback: no frame has been resolved since the last rt_resize");
+  const size_t px = size_t(c->W) * c->H;
+  if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float))) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, c->taaHist[c->taaLast][which], bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+// radical inverse of k in `base` as the exact fraction num / base^digits, divided once in IEEE double
+static double radicalInverse(int k, int base)
+{
+  long long num = 0, den = 1;
+  for(; k > 0; k /= base) { num = num * base + k % base; den *= base; }
+  return double(num) / double(den);
+}
+
+int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out)
+{
+  if(!in || !out || jitterPhases < 0 || jitterPhases > 16 || width < 1 || height < 1) return RT_ERR_INVALID_ARG;
+  rt_scene_camera cam = *in;
+  if(jitterPhases > 0) {
+    const int k = ((frames % jitterPhases) + jitterPhases) % jitterPhases + 1;
+    const float dx = float(radicalInverse(k, 2) - 0.5), dy = float(radicalInverse(k, 3) - 0.5);
+    const float ox = (2.0f * dx) / float(width), oy = (2.0f * dy) / float(height);
+    float* m = cam.projInverse.m;
+    for(int r = 0; r < 4; r++) {
+      const float a = m[0 + r] * ox, b = m[4 + r] * oy;   // (-ffp-contract=off: no fused multiply-add)
+      m[12 + r] = (m[12 + r] + a) + b;
+    }
+  }
+  *out = cam;
   return RT_OK;
 }
 

@@ -135,6 +135,32 @@ class Renderer {
     }
     return true;
   }
+  // Temporal anti-aliasing (include/rt_abi.h): off by default.  With RT_TAA_ON the context jitters the camera it renders each frame with (keep passing
+  // unjittered matrices to setCamera) and resolves the frame into a history after compose; RenderOutput::run then shows the resolved frame.
+  bool setTaa(const rt_taa& t)
+  {
+    if(rt_set_taa(m_ctx, &t) != RT_OK) { fprintf(stderr, "Renderer::setTaa: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_taa getTaa()
+  {
+    rt_taa t{};
+    rt_get_taa(m_ctx, &t);
+    return t;
+  }
+  bool taaReset() { return rt_taa_reset(m_ctx) == RT_OK; }
+  // the last resolved frame: direct and indirect RGBA32F (W x H).  False before the first resolved frame after a resize.
+  bool readTaaResult(std::vector<float>& direct, std::vector<float>& indirect)
+  {
+    direct.resize(size_t(m_width) * m_height * 4);
+    indirect.resize(direct.size());
+    if(rt_taa_readback(m_ctx, 0, direct.data(), direct.size() * sizeof(float)) != RT_OK ||
+       rt_taa_readback(m_ctx, 1, indirect.data(), indirect.size() * sizeof(float)) != RT_OK) {
+      fprintf(stderr, "Renderer::readTaaResult: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
   rt_ctx* context() { return m_ctx; }
  private:
   rt_ctx* m_ctx = nullptr;

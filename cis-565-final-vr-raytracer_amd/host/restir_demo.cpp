@@ -2,9 +2,10 @@
 //   loadEnvironmentHdr -> loadScene (Scene::load + AccelStructure::create) -> createRender -> per frame:
 //   updateFrame / Scene::updateCamera -> Renderer::run -> (post.frag's sum of the two HDR images, written to disk)
 // Usage mirrors main.cpp:52-54:  restir_demo [-f scene.gltf | -p cornell|helmet|sponza|bistro|interior] [-e env.hdr]
-//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf] [-g off|on|vis]
+//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf] [-g off|on|vis] [-t off|on]
 // -d svgf: the variance-guided spatiotemporal denoiser (rt_set_denoiser, default settings) instead of the reference's A-Trous chain.
 // -g on|vis: ReSTIR GI spatial reuse (rt_set_gi_spatial, default settings; vis = with a visibility ray per accepted neighbour).
+// -t on: temporal anti-aliasing (rt_set_taa, default settings): the PFM and PNG show the resolved frame.  (-a is taken by autoExposure.)
 // -r N: after the real-time frames, N samples per pixel of the reference mode (rt_reference_render: the converged image the frame estimates)
 //       at the last frame's camera, tonemapped like the frame into <out>_reference.png.
 #include <algorithm>
@@ -78,6 +79,14 @@ int main(int argc, char** argv)
     if(!render.setGiSpatial(g)) return 12;
   }
 
+  const std::string taaMode = arg(argc, argv, "-t", "off");
+  if(taaMode != "off" && taaMode != "on") { fprintf(stderr, "-t must be off or on\n"); return 13; }
+  if(taaMode == "on") {
+    rt_taa t = render.getTaa();
+    t.mode = RT_TAA_ON;
+    if(!render.setTaa(t)) return 13;
+  }
+
   auto t0 = std::chrono::steady_clock::now();
   for(int f = 0; f < frames; f++) {
     scene.updateCamera(W, H);
@@ -90,7 +99,7 @@ int main(int argc, char** argv)
   printf("%d frames %dx%d: %.3f ms/frame\n", frames, W, H, ms / frames);
 
   std::vector<float> d, i;
-  if(!render.readResult(frames - 1, d, i)) return 6;
+  if(taaMode == "on" ? !render.readTaaResult(d, i) : !render.readResult(frames - 1, d, i)) return 6;
   {  // PFM (bottom-up scanlines, little endian) of direct + indirect = the HDR frame
     std::ofstream pfm(out + ".pfm", std::ios::binary);
     pfm << "PF\n" << W << " " << H << "\n-1.0\n";

@@ -20,6 +20,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_reference_render", "rt_reference_reset", "rt_reference_samples", "rt_reference_readback", "rt_reference_tonemap",
                "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
+               "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -107,6 +108,12 @@ def hip_lib():
             L.rt_set_gi_spatial.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_get_gi_spatial.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_gi_spatial_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        if hasattr(L, "rt_set_taa"):   # temporal anti-aliasing (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_set_taa.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_get_taa.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_taa_reset.argtypes = [C.c_void_p]
+            L.rt_taa_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.rt_taa_jitter_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -362,6 +369,36 @@ class Renderer:
         W, H = self.size
         out = np.empty((W // 2) * (H // 2) * 76, dtype=np.uint8)
         self._chk(hip_lib().rt_gi_spatial_readback(self._h, out.ctypes.data, out.nbytes), "rt_gi_spatial_readback")
+        return out
+
+    # ---- temporal anti-aliasing (include/rt_abi.h)
+    def set_taa(self, t=None, **kw):
+        """rt_set_taa with an abi.Taa, or the library defaults overridden by keywords (set_taa(mode=abi.TAA_ON))"""
+        t = t if t is not None else abi.Taa(**kw)
+        self._chk(hip_lib().rt_set_taa(self._h, C.byref(t)), "rt_set_taa")
+
+    def get_taa(self):
+        t = abi.Taa()
+        self._chk(hip_lib().rt_get_taa(self._h, C.byref(t)), "rt_get_taa")
+        return t
+
+    def taa_reset(self):
+        self._chk(hip_lib().rt_taa_reset(self._h), "rt_taa_reset")
+
+    def taa_readback(self, which):
+        """the last resolved frame: abi.TAA_DIRECT / TAA_INDIRECT -> (H, W, 4) float32; abi.TAA_HISTORY_LENGTH -> (H, W) float32 n"""
+        W, H = self.size
+        out = np.empty((H, W, 4) if which in (abi.TAA_DIRECT, abi.TAA_INDIRECT) else (H, W), dtype=np.float32)
+        self._chk(hip_lib().rt_taa_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_taa_readback")
+        return out
+
+    @staticmethod
+    def taa_jitter_camera(cam, frames, jitter_phases, width, height):
+        """rt_taa_jitter_camera (no context, no GPU): the camera the context renders frame `frames` with when TAA is on"""
+        out = abi.SceneCamera()
+        rc = hip_lib().rt_taa_jitter_camera(C.byref(cam), int(frames), int(jitter_phases), int(width), int(height), C.byref(out))
+        if rc != 0:
+            raise RtError(f"rt_taa_jitter_camera failed ({rc})")
         return out
 
     def accel_stats(self):

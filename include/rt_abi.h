@@ -624,11 +624,58 @@ int rt_get_gi_spatial(rt_ctx* ctx, rt_gi_spatial* out);
 /* the spatially resampled reservoirs of the last frame rendered with the mode on: rt_indirect_reservoir, (W/2) * (H/2) * 76 B; synchronous;
  * RT_ERR_NO_TARGET before the first such frame since rt_resize */
 int rt_gi_spatial_readback(rt_ctx* ctx, void* dst, size_t bytes);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Temporal anti-aliasing (added within ABI 2.4, no version bump): sub-pixel camera jitter plus one resolve pass per frame after compose.
+ * Jitter (host side; the traced kernels are unchanged): a frame with debugging_mode == 0 is rendered with rt_taa_jitter_camera(&cam, frames, jitterPhases,
+ * W, H) in place of the camera rt_set_camera stored (debug-view frames are neither jittered nor resolved):
+ *   k = (frames mod jitterPhases) + 1 (frames < 0 taken modulo like a non-negative number); delta = (h2(k) - 0.5, h3(k) - 0.5) pixels, h2 / h3 the base-2 /
+ *   base-3 radical inverses evaluated in IEEE double, each component rounded once to float (|delta| <= 0.469 per component for jitterPhases <= 16);
+ *   ox = (2 * delta.x) / W, oy = (2 * delta.y) / H in fp32; the projInverse translation column becomes, per row r (fp32, no contraction, this order):
+ *       m[12 + r] = (m[12 + r] + m[0 + r] * ox) + m[4 + r] * oy
+ *   so that projInverse · (x, y, z, 1) becomes projInverse · (x + ox, y + oy, z, 1).  Every other field is copied bit for bit; jitterPhases = 0 returns the
+ *   input bits.  projView, lastProjView, lastView and lastPosition stay unjittered, so motion vectors do not carry the jitter.  The context jitters the copy of
+ *   the camera each frame's launches receive; rt_set_camera's stored camera, rt_pick and rt_reference_* never see the jitter.
+ * Resolve (csrc/taa.hip), per full-resolution pixel p of frame f, for the two components D = RT_BUF_DIRECT_RESULT and I = RT_BUF_INDIRECT_RESULT after compose:
+ *   no valid material in G(f) at p: D and I pass through unchanged, n = 1.
+ *   x = cameraPosDenoise(jittered camera, p, G-buffer distance) (denoise_common.glsl:27-40); s = (ndc(lastProjView · (x, 1)).xy · 0.5 + 0.5) · (W, H);
+ *   q = floor(s).  The history is consistent when the previous history is valid, q lies in the image and G(f-1) at q has the same material hash,
+ *   dot(n, n_prev) > 0.9 and |lastPosition - x| < depth_prev · 1.05 (the direct stage's temporal test).  Inconsistent: out = (c.rgb, 1), n = 1.
+ *   Consistent: n = min(n_prev(q) + 1, 1024); h = the 4 x 4 Catmull-Rom sample of the previous resolved image around s - 0.5 (taps clamped to the image,
+ *   weights w0 = t(-0.5 + t(1 - 0.5t)), w1 = 1 + t²(-2.5 + 1.5t), w2 = t(0.5 + t(2 - 1.5t)), w3 = t²(-0.5 + 0.5t)); in YCoCg (Y = (r/4 + g/2) + b/4,
+ *   Co = r/2 - b/2, Cg = (-r/4 + g/2) - b/4) mu and sigma = sqrt(max(0, E[v²] - mu²)) of c over the in-image 3 x 3 neighbourhood; d = h - mu, e = clipGamma ·
+ *   sigma, t = max(1, max over channels with |d| > e of |d| / e), h = mu + d / t (a clip along the segment towards mu, not a per-channel clamp), back to RGB;
+ *   a = max(alpha, 1/n); out = (h (1 - a) + c a, 1).  The outputs and n form the history of parity f.
+ * History: two RGBA32F images + one f32 n per parity (W * H * 36 B each), allocated by the first frame rendered with the mode on and freed by rt_resize /
+ * rt_destroy.  It is invalid after rt_resize, rt_upload_scene, rt_build_accel, an rt_set_taa that changes anything, rt_taa_reset, a frame with
+ * debugging_mode != 0 (which skips the pass) and a frame whose parity does not follow the previous resolved frame's.
+ * Schedule: the pass runs right after compose on compose's stream in every schedule and is timed under RT_STAGE_COMPOSE (rt_counters keeps its layout).
+ * rt_tonemap(frames) reads the resolved images when frame `frames` was resolved, the plain result images otherwise.  The frame buffers (G-buffers, reservoirs,
+ * result images, ...) are what the frame computes with the jittered camera; the pass writes only its history.  rt_run_stage on a context with the mode on is
+ * RT_ERR_INVALID_ARG (the row-tiled hosts have no TAA); the reference mode ignores it.  A change of mode re-opens the stream-priority decision.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_TAA_OFF = 0 /* default */, RT_TAA_ON = 1 };
+typedef struct {
+  int32_t mode;          /* RT_TAA_*; default OFF */
+  int32_t jitterPhases;  /* 0..16; default 8.  0 = no jitter (temporal accumulation only, for A/B) */
+  float   alpha;         /* (0, 1]: blend-factor floor; default 0.1 */
+  float   clipGamma;     /* > 0, finite: width of the colour box in standard deviations; default 1.0 */
+  int32_t reserved[4];   /* must be 0 */
+} rt_taa;                /* 32 B */
+/* validates every field (bad values: RT_ERR_INVALID_ARG, the settings in use stay) */
+int rt_set_taa(rt_ctx* ctx, const rt_taa* t);
+int rt_get_taa(rt_ctx* ctx, rt_taa* out);
+/* the next resolved frame starts without history */
+int rt_taa_reset(rt_ctx* ctx);
+/* the last resolved frame: which = 0 direct, 1 indirect (RGBA32F, W * H * 16 B), 2 history length n (f32, W * H * 4 B).  Synchronous.
+ * RT_ERR_NO_TARGET before the first resolved frame since rt_resize. */
+int rt_taa_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+/* pure function, no context, callable without a GPU: the camera the context renders frame `frames` with (jitterPhases 0..16, width, height >= 1) */
+int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
+/* ABI version: (major<<16)|minor.  2.4: + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
  * (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; opt-in additions that change no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
@@ -652,6 +699,7 @@ static_assert(sizeof(rt_tonemapper) == 48, "Tonemapper host_device.h:336-351");
 static_assert(sizeof(rt_sun_and_sky) == 96, "SunAndSky host_device.h:353-377");
 static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
 static_assert(sizeof(rt_gi_spatial) == 32, "rt_gi_spatial");
+static_assert(sizeof(rt_taa) == 32, "rt_taa");
 #endif
 
 #endif /* RT_ABI_H */

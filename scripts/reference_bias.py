@@ -12,6 +12,11 @@ the pixels whose primary ray hits a surface (G-buffer depth < infinity):
                luminance of the reference
 --denoiser selects the filter of the real-time frames (rt_set_denoiser), one JSON line per entry: `atrous` (the default), `svgf` (library defaults) or
 `svgf:key=value:...` with rt_denoiser fields (alphaColor, alphaMoments, historyCap, phiLumDirect, phiLumIndirect) — the reference is taken once per configuration.
+--taa selects temporal anti-aliasing (rt_set_taa), one JSON line per entry: `off` (the default), `on` (library defaults) or `on:key=value:...` with rt_taa fields
+(jitterPhases, alpha, clipGamma); with TAA on the frame average is taken over the resolved images (rt_taa_readback).  --ref-supersample S renders the reference
+at S·W × S·H in a context of its own and averages S×S blocks: the box-filtered pixel a jittered TAA frame estimates (the plain reference is point-sampled at
+pixel centres).  Every line also reports the metrics over the edge pixels: pixels whose 3×3 G-buffer neighbourhood (an unjittered frame) holds another
+material hash or a relative depth step above 10 %.
 The reference ignores the real-time state (its sums are taken once per configuration); every frame of the average uses the same camera (its history matrices
 advanced per frame, as SampleExample::updateFrame does), time = 1000 + f.
 Config 2 runs the whole frame here (bench.py times the direct stage alone for it).
@@ -19,6 +24,7 @@ Config 2 runs the whole frame here (bench.py times the direct stage alone for it
   python scripts/reference_bias.py [--configs 2 3 4] [--frames 64] [--warmup 8] [--spp 256] [--batches 8] [--out profiles/reference_bias.jsonl]
   python scripts/reference_bias.py --denoiser atrous svgf --variants default [--out profiles/denoiser_svgf.jsonl]      # the denoiser A/B
   python scripts/reference_bias.py --gi-spatial off on vis --denoiser atrous svgf --variants default [--out profiles/gi_spatial.jsonl]
+  python scripts/reference_bias.py --taa off on on:jitterPhases=0 --denoiser atrous svgf --variants default --ref-supersample 4 [--out profiles/taa.jsonl]   # §16
   python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]      # reference time per sample at the configuration's size (host-timed, synchronised)
   python scripts/reference_bias.py --rays-per-path [--configs 4 2]         # CPU only: ray queries per path of the CPU restatement (tests/refpt_checker.cpp)
 """
@@ -105,7 +111,49 @@ def gi_spatial_settings(spec):
     return spec, abi.GiSpatial(mode=modes[parts[0]], **kw)
 
 
-def realtime_average(r, sc, st, frames, warmup):
+def taa_settings(spec):
+    """`off` | `on` | `on:key=value:...` with rt_taa fields (jitterPhases, alpha, clipGamma) -> (label, abi.Taa)"""
+    parts = spec.split(":")
+    if parts[0] not in ("off", "on"):
+        raise SystemExit(f"--taa {spec}: off or on[:key=value...]")
+    kw = {}
+    for p in parts[1:]:
+        k, v = p.split("=")
+        kw[k] = int(v) if k == "jitterPhases" else float(v)
+    return spec, abi.Taa(mode=abi.TAA_ON if parts[0] == "on" else abi.TAA_OFF, **kw)
+
+
+def edge_pixels(g):
+    """pixels whose 3x3 neighbourhood in the G-buffer g (H, W, 4 u32) has another material hash or a relative depth step above 10 %"""
+    H, W = g.shape[:2]
+    mat = g[..., 3] & np.uint32(0xFF000000)
+    depth = g[..., 0].view(np.float32).astype(np.float64)
+    edge = np.zeros((H, W), bool)
+    for j in (-1, 0, 1):
+        for i in (-1, 0, 1):
+            yy, xx = np.clip(np.arange(H) + j, 0, H - 1), np.clip(np.arange(W) + i, 0, W - 1)
+            mq, dq = mat[yy][:, xx], depth[yy][:, xx]
+            with np.errstate(invalid="ignore", over="ignore"):
+                step = np.abs(dq - depth) > 0.1 * np.minimum(dq, depth)
+            edge |= (mq != mat) | step
+    return edge
+
+
+def supersampled_reference(desc, config, W, H, S, spp, batches):
+    """the reference at S*W x S*H in a context of its own, averaged over S x S blocks (the box-filtered pixel); sigma of the sum's luminance likewise"""
+    from restir_amd.renderer import Renderer
+    sc, env, st, _, _ = setup(config, W * S, H * S)
+    r = Renderer().setup(0)
+    r.load_scene(desc)
+    r.update(W * S, H * S)
+    r.set_camera(sc.getCamera())
+    ref, sigma, secs = reference(r, st, spp, batches)
+    r.destroy()
+    box = lambda a: a.reshape(H, S, W, S, *a.shape[2:]).mean(axis=(1, 3))  # noqa: E731
+    return [box(c) for c in ref], np.sqrt(box(sigma ** 2) / (S * S)), secs
+
+
+def realtime_average(r, sc, st, frames, warmup, taa_on=False):
     """the mean of each component over the frames after warm-up, the per-pixel standard deviation of each component's luminance over those frames,
     and the pixels that hit a surface"""
     acc = [None, None, None]
@@ -119,8 +167,11 @@ def realtime_average(r, sc, st, frames, warmup):
         r.run(st, f)
         if f >= warmup:
             cur = f & 1
-            imgs = [r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
-                    for buf in (abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)]
+            if taa_on:
+                imgs = [r.taa_readback(w)[..., :3].astype(np.float64) for w in (abi.TAA_DIRECT, abi.TAA_INDIRECT)]
+            else:
+                imgs = [r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
+                        for buf in (abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)]
             imgs.append(imgs[0] + imgs[1])
             for k, img in enumerate(imgs):
                 acc[k] = img if acc[k] is None else acc[k] + img
@@ -155,25 +206,37 @@ def bias(args):
         r.load_scene(desc)
         r.update(W, H)
         r.set_camera(sc.getCamera())
-        ref, sigma, secs = reference(r, st0, args.spp, args.batches)
-        runs = [(v, d, g) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)
-                for g in map(gi_spatial_settings, args.gi_spatial)]
-        for (vname, over), (dname, den), (gname, gis) in runs:
+        if args.ref_supersample > 1:
+            ref, sigma, secs = supersampled_reference(desc, config, W, H, args.ref_supersample, args.spp, args.batches)
+            sc.updateCamera(W, H)
+        else:
+            ref, sigma, secs = reference(r, st0, args.spp, args.batches)
+        # the edge pixels, from one unjittered frame
+        r.set_camera(sc.getCamera())
+        r.run(st0, 0)
+        edge = edge_pixels(r.readback(abi.BUF_GBUFFER0).view(np.uint32).reshape(H, W, 4))
+        runs = [(v, d, g, t) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)
+                for g in map(gi_spatial_settings, args.gi_spatial) for t in map(taa_settings, args.taa)]
+        for (vname, over), (dname, den), (gname, gis), (tname, taa) in runs:
             st = abi.RtxState.from_buffer_copy(st0)
             for k, v in over.items():
                 setattr(st, k, v)
             r.update(W, H)                                      # fresh history for every variant
             r.set_denoiser(den)
             r.set_gi_spatial(gis)
+            r.set_taa(taa)
             r.set_camera(sc.getCamera())
-            frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup)
+            frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup, taa.mode == abi.TAA_ON)
             out = {"config": config, "variant": vname, "denoiser": dname, **({"gi_spatial": gname} if args.gi_spatial != ["off"] else {}),
+                   **({"taa": tname, "ref_supersample": args.ref_supersample, "edge_share": round(float(edge.mean()), 4)} if args.taa != ["off"] else {}),
                    "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
                    "ref_batches": args.batches, "ref_seconds": round(secs, 2), "surface_share": round(float(surface.mean()), 4)}
             everything = np.ones_like(surface)
             for name, c in (("direct", 0), ("indirect", 1), ("sum", 2)):
                 out[name] = {"all": metrics(frame[c], ref[c], sigma if c == 2 else None, everything, std[c]),
                              "surface": metrics(frame[c], ref[c], sigma if c == 2 else None, surface, std[c])}
+                if args.taa != ["off"]:
+                    out[name]["edge"] = metrics(frame[c], ref[c], sigma if c == 2 else None, edge, std[c])
             line = json.dumps(out)
             print(line, flush=True)
             if args.out:
@@ -233,6 +296,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--denoiser", nargs="+", default=["atrous"], help="atrous | svgf | svgf:key=value:... (one run of the real-time frames per entry)")
     ap.add_argument("--gi-spatial", nargs="+", default=["off"], help="off | on | vis | on:key=value:... (ReSTIR GI spatial reuse; one run per entry)")
+    ap.add_argument("--taa", nargs="+", default=["off"], help="off | on | on:key=value:... (temporal anti-aliasing; one run per entry)")
+    ap.add_argument("--ref-supersample", type=int, default=1, help="S: the reference at S*W x S*H, averaged over S x S blocks")
     ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=list(VARIANTS))
     ap.add_argument("--timing", action="store_true")
     ap.add_argument("--rays-per-path", action="store_true")
