@@ -127,7 +127,9 @@ int orc_readback(void* p, int id, void* dst, size_t bytes)
 {
   size_t b; void* src = bufPtr(static_cast<Ctx*>(p), id, b);
   b = orc_buffer_bytes(p, id);
-  if(!src || bytes != b) return RT_ERR_INVALID_ARG;
+  if(id < 0 || id >= RT_BUF_COUNT || bytes != b) return RT_ERR_INVALID_ARG;
+  if(b == 0) return RT_OK;   // a half-resolution buffer of a one-pixel-wide image: nothing to copy, like rt_readback
+  if(!src) return RT_ERR_INVALID_ARG;
   memcpy(dst, src, b);
   return RT_OK;
 }
@@ -135,7 +137,9 @@ int orc_upload_history(void* p, int id, const void* src, size_t bytes)
 {
   size_t b; void* dst = bufPtr(static_cast<Ctx*>(p), id, b);
   b = orc_buffer_bytes(p, id);
-  if(!dst || bytes != b) return RT_ERR_INVALID_ARG;
+  if(id < 0 || id >= RT_BUF_COUNT || bytes != b) return RT_ERR_INVALID_ARG;
+  if(b == 0) return RT_OK;
+  if(!dst) return RT_ERR_INVALID_ARG;
   memcpy(dst, src, b);
   return RT_OK;
 }

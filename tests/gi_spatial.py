@@ -13,6 +13,7 @@ SRC = os.path.join(ROOT, "tests", "gi_spatial_checker.cpp")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared"]
 RESV_BYTES = 76
 _lib = None
+lib_path = None   # where build() put the library (tests/optin.py hands it to child processes, which load() it instead of compiling again)
 
 
 def build(out_dir):
@@ -22,6 +23,14 @@ def build(out_dir):
         return _lib
     so = os.path.join(str(out_dir), "libgischk.so")
     subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [SRC, os.path.join(ROOT, "oracle", "orc_scene.cpp"), "-o", so])
+    return load(so)
+
+
+def load(so):
+    """load a library build() compiled (once per process)"""
+    global _lib, lib_path
+    if _lib is not None:
+        return _lib
     L = C.CDLL(so)
     L.gis_create.restype = C.c_void_p
     L.gis_create.argtypes = [C.c_void_p]
@@ -29,7 +38,7 @@ def build(out_dir):
     L.gis_jacobian.restype = C.c_float
     L.gis_jacobian.argtypes = [C.c_void_p] * 4 + [C.c_float, C.POINTER(C.c_int)]
     L.gis_run.argtypes = [C.c_void_p] * 9
-    _lib = L
+    _lib, lib_path = L, so
     return L
 
 

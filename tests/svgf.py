@@ -12,6 +12,7 @@ from helpers import ROOT, abi
 SRC = os.path.join(ROOT, "tests", "svgf_checker.cpp")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared"]
 _lib = None
+lib_path = None   # where build() put the library (tests/optin.py hands it to child processes, which load() it instead of compiling again)
 
 
 def build(out_dir):
@@ -21,6 +22,14 @@ def build(out_dir):
         return _lib
     so = os.path.join(str(out_dir), "libsvgfchk.so")
     subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [SRC, os.path.join(ROOT, "oracle", "orc_scene.cpp"), "-o", so])
+    return load(so)
+
+
+def load(so):
+    """load a library build() compiled (once per process)"""
+    global _lib, lib_path
+    if _lib is not None:
+        return _lib
     L = C.CDLL(so)
     L.svgf_create.restype = C.c_void_p
     L.svgf_create.argtypes = [C.c_int, C.c_int]
@@ -29,7 +38,7 @@ def build(out_dir):
     L.svgf_reset.argtypes = [C.c_void_p]
     L.svgf_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     L.svgf_history.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    _lib = L
+    _lib, lib_path = L, so
     return L
 
 

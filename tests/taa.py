@@ -11,6 +11,7 @@ from helpers import ROOT, abi
 SRC = os.path.join(ROOT, "tests", "taa_checker.cpp")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-mfma", "-ffp-contract=off", "-fno-fast-math", "-pthread", "-shared"]
 _lib = None
+lib_path = None   # where build() put the library (tests/optin.py hands it to child processes, which load() it instead of compiling again)
 
 
 def build(out_dir):
@@ -20,12 +21,20 @@ def build(out_dir):
         return _lib
     so = os.path.join(str(out_dir), "libtaachk.so")
     subprocess.check_call([os.environ.get("CXX", "g++")] + FLAGS + [SRC, os.path.join(ROOT, "oracle", "orc_scene.cpp"), "-o", so])
+    return load(so)
+
+
+def load(so):
+    """load a library build() compiled (once per process)"""
+    global _lib, lib_path
+    if _lib is not None:
+        return _lib
     L = C.CDLL(so)
     L.taa_resolve.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 11
     L.taa_catmull_rom.argtypes = [C.c_float, C.c_void_p]
     L.taa_clip.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
     L.taa_ycocg.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    _lib = L
+    _lib, lib_path = L, so
     return L
 
 

@@ -208,14 +208,14 @@ def _close(got, want, what):
     assert (err <= 0).all(), (what, float(err.max()), np.unravel_index(err.argmax(), err.shape))
 
 
-def test_checker_matches_an_independent_model(lib):
-    W, H = 48, 32
+def check_model(lib, W, H, s=None):
+    """the checker against `model` over four frames of a moving camera at W x H (settings `s`); returns what the frames exercised"""
     sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, (64, 32))
     st = host.default_state(W, H, sc, env)
     desc = sc.desc(env)
     o = Oracle(0); o.upload_scene(desc); o.resize(W, H)
     k = gi_spatial.GiSpatialChecker(lib, desc)
-    s = abi.GiSpatial(mode=abi.GI_SPATIAL_ON, samples=6, radius=5)
+    s = s if s is not None else abi.GiSpatial(mode=abi.GI_SPATIAL_ON, samples=6, radius=5)
     eye, center, up, fov = sc.cameraPose()
     merged = moved = 0
     for f in range(4):   # the camera moves every frame; the reservoirs carry temporal history from frame 1 on
@@ -247,7 +247,12 @@ def test_checker_matches_an_independent_model(lib):
         ia = ind_a.view(np.float32)[:W * H * 4].reshape(H, W, 4)[:H // 2, :W // 2]
         assert np.array_equal(img[:H // 2, :W // 2][~valid], ia[~valid])
         merged += int((num[valid] > rv["num"][valid]).sum()); moved += int(mv.sum())
-    assert merged > valid.sum() // 4 and moved > 20, (merged, moved)   # the taps merge, and neighbours' samples win
+    return dict(merged=merged, moved=moved, surface=int(valid.sum()))
+
+
+def test_checker_matches_an_independent_model(lib):
+    got = check_model(lib, 48, 32)
+    assert got["merged"] > got["surface"] // 4 and got["moved"] > 20, got   # the taps merge, and neighbours' samples win
 
 
 def test_zero_samples_reproduce_the_indirect_stage(lib):

@@ -160,8 +160,8 @@ def _close(got, want, what):
     assert (err <= 0).all(), (what, float(err.max()), np.unravel_index(err.argmax(), err.shape))
 
 
-def test_checker_matches_an_independent_model(lib):
-    W, H = 48, 32
+def check_model(lib, W, H):
+    """the checker against `Model` over five frames of a moving camera at W x H; returns what the frames exercised"""
     sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, (64, 32))
     st = host.default_state(W, H, sc, env)
     o = Oracle(0); o.upload_scene(sc.desc(env)); o.resize(W, H)
@@ -194,6 +194,13 @@ def test_checker_matches_an_independent_model(lib):
         n = models[0].n
         if f > 0:
             accepted += int((n > 1).sum()); rejected += int((n == 1).sum())
-    assert accepted > 0 and rejected > 0
-    assert (models[0].n >= 4).sum() > W * H // 4       # the temporal-variance branch is exercised
-    assert out_d[..., :3].max() > 0 and out_i[..., :3].max() > 0
+    return dict(accepted=accepted, rejected=rejected, long_history=int((models[0].n >= 4).sum()), long_history_indirect=int((models[1].n >= 4).sum()),
+                peak_direct=float(out_d[..., :3].max()), peak_indirect=float(out_i[:H // 2, :W // 2, :3].max()) if (W // 2) * (H // 2) else 0.0)
+
+
+def test_checker_matches_an_independent_model(lib):
+    W, H = 48, 32
+    got = check_model(lib, W, H)
+    assert got["accepted"] > 0 and got["rejected"] > 0
+    assert got["long_history"] > W * H // 4       # the temporal-variance branch is exercised
+    assert got["peak_direct"] > 0 and got["peak_indirect"] > 0

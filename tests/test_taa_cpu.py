@@ -215,8 +215,9 @@ def model_resolve(cam, taa_s, hist_ok, g, gl, cd, ci, pD, pI, pN):
     return outs[0], outs[1], np.where(valid, n, 1), cons, border
 
 
-def test_checker_matches_an_independent_model(lib):
-    W, H = 48, 32
+def check_model(lib, W, H, border_pixels=None):
+    """the checker against model_resolve over five frames of a moving camera at W x H; returns what the frames exercised.  The cap on the pixels left out as
+    borderline is 5 % of the image, or `border_pixels` (an absolute count, for images of a few pixels: tests/test_optin_shapes_cpu.py)"""
     sc, env = make_scene(abi.PROC_SPONZA, 0.01, 1, (64, 32))
     st = host.default_state(W, H, sc, env)
     o = Oracle(0); o.upload_scene(sc.desc(env)); o.resize(W, H)
@@ -238,7 +239,10 @@ def test_checker_matches_an_independent_model(lib):
         ci = o.readback(abi.BUF_INDIRECT_RESULT0 + cur).view(np.float32).reshape(H, W, 4).astype(np.float64)
         mD, mI, mn, cons, border = model_resolve(jc, t, hist_ok, g, gl, cd, ci, *[p.astype(np.float64) for p in prev])
         ok = ~border
-        assert border.mean() < 0.05, f
+        if border_pixels is None:
+            assert border.mean() < 0.05, f
+        else:
+            assert border.sum() <= border_pixels, (f, int(border.sum()))
         assert np.array_equal(k.consistent[ok], cons[ok]), (f, int((k.consistent[ok] != cons[ok]).sum()))
         assert np.array_equal(n[ok], mn[ok].astype(np.float32)), f
         for got, want, what in ((d, mD, "direct"), (i, mI, "indirect")):
@@ -249,8 +253,14 @@ def test_checker_matches_an_independent_model(lib):
             accepted += int((n > 1).sum()); rejected += int((n == 1).sum())
             box = np.abs(d[..., :3] - cd[..., :3]).sum(-1) > 0
             clipped += int(box.sum())
-    assert accepted > W * H and rejected > 0 and clipped > 0
-    assert d[..., :3].max() > 0
+    return dict(accepted=accepted, rejected=rejected, clipped=clipped, peak=float(d[..., :3].max()))
+
+
+def test_checker_matches_an_independent_model(lib):
+    W, H = 48, 32
+    got = check_model(lib, W, H)
+    assert got["accepted"] > W * H and got["rejected"] > 0 and got["clipped"] > 0
+    assert got["peak"] > 0
 
 
 def _flat_frame(W, H, hash_=0x01000000, depth=1.0):
