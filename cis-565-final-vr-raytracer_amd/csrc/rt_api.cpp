@@ -153,7 +153,8 @@ static hipError_t joinInFlight(rt_ctx* c)
 }
 
 typedef hipError_t (*StageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const rt_state&, const rt_scene_camera&, int, int, int, int);
-// Which build of stages.hip runs a launch.  The traced kernels exist twice: the throughput build (one ray per lane, majority-vote rounds, 4-5 waves per
+// What runs a launch: the filter chains and compose exist once (csrc/filters.hip); every other stage comes from one of the six builds of stages.hip.
+// The traced kernels exist twice: the throughput build (one ray per lane, majority-vote rounds, 4-5 waves per
 // SIMD: full frames are bound by instruction issue) and the latency build (csrc/stages_lat.hip: eight lanes per ray, a workgroup of eight waves per tile:
 // a row band of a multi-GPU frame or a small image is bound by the dependent steps of its slowest rays, and the latency build shortens the step).
 // RT_TRAVERSAL_AUTO decides by the number of 8x8 tiles of the launch; the thresholds are where the two builds measured equal on the benchmark scene
@@ -174,8 +175,11 @@ static int latTilesIndirect(bool shared)
   static const int alone = envInt("RESTIR_LAT_TILES_IND"), sh = envInt("RESTIR_LAT_TILES_IND_SHARED");
   return shared ? (sh >= 0 ? sh : (alone >= 0 ? alone : 640)) : (alone >= 0 ? alone : 2000);
 }
+static hipError_t filterLauncher(hipStream_t stream, const DevScene&, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int r0, int r1)
+{ return rt::launchFilterStage(stream, F, st, cam, stage, level, r0, r1); }
 static StageLauncher stageLauncher(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
 {
+  if(stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT || stage == RT_STAGE_COMPOSE) return filterLauncher;
   bool lat = false;
   if(!c->counting && (stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT)) {
     if(c->traversal == RT_TRAVERSAL_LATENCY) lat = true;

@@ -3,10 +3,11 @@
 #include "dev_scene.h"
 namespace rt {
 constexpr int STACK_MAX = 64;  // LDS traversal stack entries per lane (8 B each) upper bound; rt_build_accel rejects deeper trees
-// one entry of Renderer::run's dispatch list (renderer.cpp:163-205) on `stream`.  stages.hip is compiled six times:
+// one entry of Renderer::run's dispatch list (renderer.cpp:163-205) on `stream`.
+// The stages that trace rays or shade (direct, direct_gen, direct_reuse, indirect): stages.hip, compiled six times
 //   base / sky          HDR environment only / sun & sky code paths compiled in
 //   base_cnt / sky_cnt  the same with the counters of rt_set_counting flushed
-//   base_lat / sky_lat  the traced kernels for small launches (latency-mode traversal); every other stage forwards to base / sky
+//   base_lat / sky_lat  k_direct_stage and k_indirect_stage for small launches (latency-mode traversal); the direct stage's rayless half forwards to base / sky
 #define RT_DECL_LAUNCH(ns)                                                                                                                              \
   namespace ns {                                                                                                                                        \
   hipError_t launchStage(hipStream_t stream, const DevScene& S, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, \
@@ -19,6 +20,10 @@ RT_DECL_LAUNCH(sky_cnt)
 RT_DECL_LAUNCH(base_lat)
 RT_DECL_LAUNCH(sky_lat)
 #undef RT_DECL_LAUNCH
+// filters.hip, compiled once: every other stage (both A-Trous chains, compose; hipErrorInvalidValue for a level outside the chain or any other stage), and the
+// tile-order pass that every build of the indirect stage launches ahead of k_indirect_stage
+hipError_t launchFilterStage(hipStream_t stream, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int rowBegin, int rowEnd);
+hipError_t launchIndTileOrder(hipStream_t stream, const rt_state& st, int rowBegin, int tilesX, int tilesY, int cap, uint32_t* lists, uint32_t* counts);
 
 // uniform-only terms of sun_and_sky() (sky.h), one thread
 struct SkyPre;

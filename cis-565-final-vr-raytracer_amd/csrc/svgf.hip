@@ -22,29 +22,11 @@
 // evaluation of k_denoise_lds does not apply.
 // Launch shape: one wave64 per 8 x 8 tile, the XCD-striped tile order of the stages (tileOf).
 #define RT_COUNT 0
-#include "stage_common.h"
+#include "filter_common.h"
 #include "svgf.h"
 
 namespace rt {
 namespace {
-
-__device__ constexpr float kSvgfGauss[5][5] = {{.0030f, .0133f, .0219f, .0133f, .0030f},
-                                               {.0133f, .0596f, .0983f, .0596f, .0133f},
-                                               {.0219f, .0983f, .1621f, .0983f, .0219f},
-                                               {.0133f, .0596f, .0983f, .0596f, .0133f},
-                                               {.0030f, .0133f, .0219f, .0133f, .0030f}};  // denoise_common.glsl:15-21
-
-// denoise_common.glsl:27-40 (the A-Trous chain's k_denoise_geom decode, same expressions): the direction is not re-normalised after the view transform
-RT_DEV f3 svgfCameraPos(const rt_scene_camera& cam, i2 coord, float dist, i2 imageSize)
-{
-  const f2 pixelCenter = mk2(float(coord.x), float(coord.y)) + 0.5f;
-  const f2 inUV = pixelCenter / mk2(float(imageSize.x), float(imageSize.y));
-  const f2 d = inUV * 2.0f - 1.0f;
-  const f4 origin = mul(cam.viewInverse, mk4(0, 0, 0, 1));
-  const f4 target = mul(cam.projInverse, mk4(d.x, d.y, 1, 1));
-  const f4 direction = mul(cam.viewInverse, mk4(normalize(xyz(target)), 0));
-  return xyz(origin) + xyz(direction) * dist;
-}
 
 RT_DEV float svgfMix(float x, float y, float t) { return x * (1.0f - t) + y * t; }
 RT_DEV float svgfNormW(f3 n, f3 nq, float sigN) { return rt_min(1.0f, rt_exp(-(dot(n - nq, n - nq) / sigN))); }
@@ -71,7 +53,7 @@ __global__ __launch_bounds__(64) void k_svgf_temporal(SvgfArgs A, rt_scene_camer
   const i2 gc = IND ? i2{P.p.x * 2, P.p.y * 2} : P.p;
   const uint4 g = A.thisG[size_t(gc.y) * A.W + gc.x];
   const f3 norm = decompress_unit_vec(g.y);
-  const f3 pos = svgfCameraPos(cam, gc, rt_u2f(g.x), bound);
+  const f3 pos = cameraPosDenoise(cam, gc, rt_u2f(g.x), bound);
   const uint32_t hash = g.w & 0xFF000000u;
   A.geomN[P.idx] = make_float4(norm.x, norm.y, norm.z, rt_u2f(hash));
   A.geomP[P.idx] = make_float4(pos.x, pos.y, pos.z, 0.f);
@@ -183,7 +165,7 @@ __global__ __launch_bounds__(64) void k_svgf_atrous(SvgfArgs A, const float4* sr
         const float4 qp = A.geomP[qi];
         const float4 cq = src[size_t(q.y) * A.W + q.x];
         const float wL = rt_exp(-(rt_abs(lp - luminance(mk3(cq.x, cq.y, cq.z))) / denom));
-        const float w = ((wL * svgfNormW(norm, mk3(qn.x, qn.y, qn.z), A.sigN)) * svgfDepthW(pos, mk3(qp.x, qp.y, qp.z), A.sigD)) * kSvgfGauss[i + 2][j + 2];
+        const float w = ((wL * svgfNormW(norm, mk3(qn.x, qn.y, qn.z), A.sigN)) * svgfDepthW(pos, mk3(qp.x, qp.y, qp.z), A.sigD)) * kGauss[i + 2][j + 2];
         sum += mk3(cq.x, cq.y, cq.z) * w;
         sumV += (w * w) * cq.w;
         sumW += w;

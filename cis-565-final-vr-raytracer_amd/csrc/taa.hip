@@ -16,23 +16,11 @@
 // Numerics (include/rt_detmath.h): IEEE divisions and square roots, no contraction — tests/taa_checker.cpp restates every expression on the CPU and the
 // GPU tests compare word for word.  Launch shape: one wave64 per 8 x 8 tile, the XCD-striped tile order of the stages (tileOf).
 #define RT_COUNT 0
-#include "stage_common.h"
+#include "filter_common.h"
 #include "taa.h"
 
 namespace rt {
 namespace {
-
-// denoise_common.glsl:27-40 (svgf.hip's svgfCameraPos, the same expressions)
-RT_DEV f3 taaCameraPos(const rt_scene_camera& cam, i2 coord, float dist, i2 imageSize)
-{
-  const f2 pixelCenter = mk2(float(coord.x), float(coord.y)) + 0.5f;
-  const f2 inUV = pixelCenter / mk2(float(imageSize.x), float(imageSize.y));
-  const f2 d = inUV * 2.0f - 1.0f;
-  const f4 origin = mul(cam.viewInverse, mk4(0, 0, 0, 1));
-  const f4 target = mul(cam.projInverse, mk4(d.x, d.y, 1, 1));
-  const f4 direction = mul(cam.viewInverse, mk4(normalize(xyz(target)), 0));
-  return xyz(origin) + xyz(direction) * dist;
-}
 
 RT_DEV f3 toYCoCg(f3 c)
 {
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(64) void k_taa_resolve(TaaArgs A, rt_scene_camera c
   f2 s = mk2(0.0f, 0.0f);
   int qx = 0, qy = 0;
   if(A.histValid) {
-    const f3 x = taaCameraPos(cam, p, rt_u2f(g.x), i2{A.W, A.H});
+    const f3 x = cameraPosDenoise(cam, p, rt_u2f(g.x), i2{A.W, A.H});
     const f4 clip = mul(cam.lastProjView, mk4(x, 1.0f));
     const f3 ndc = xyz(clip) / clip.w;
     const f2 mv = mk2(ndc.x, ndc.y) * 0.5f + 0.5f;

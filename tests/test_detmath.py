@@ -53,8 +53,8 @@ def test_pow_srgb():
 
 
 def test_uniform_divisor_shortcut_is_ieee_division():
-    """csrc/stages.hip divUniform (A-Trous weights: distance / sigma): q' = fma(a - b*q, 1/b, q) equals RN(a/b) for every tested
-    numerator, for divisors in the range launchStage accepts (1e-6 .. 1e6)."""
+    """csrc/filters.hip divUniform (A-Trous weights: distance / sigma): q' = fma(a - b*q, 1/b, q) equals RN(a/b) for every tested
+    numerator, for divisors in the range launchDenoiseLevel accepts (1e-6 .. 1e6)."""
     rng = np.random.default_rng(5)
     sig = np.concatenate([[0.4, 0.1, 0.02, 4.0, 1.0, 1e-6, 1e6, 0.3333333, 0.99999994, 1.9999999], np.exp(rng.uniform(np.log(1e-6), np.log(1e6), 90))]).astype(np.float32)
     for b in sig:

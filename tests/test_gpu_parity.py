@@ -289,3 +289,95 @@ def test_large_launch_indirect_bit_exact():
     _run(sc, st, o, r, W, H, 3, moving=True, stages=stages, buffers=bufs)
     img = r.readback(abi.BUF_DENOISE_IND_A).view(np.float32)
     assert np.isfinite(img).all() and img.max() > 0.0
+
+
+# ---- which code runs a stage: csrc/rt_api.cpp stageLauncher picks one of the six builds of csrc/stages.hip for the traced stages and csrc/filters.hip for the
+# filter chains and compose, whatever the selection is
+SELECTIONS = [(sky, mode) for sky in (False, True) for mode in ("throughput", "counting", "latency")]
+SELECT_SIZES = [(101, 51), (1, 1)]   # ragged tiles + an odd 50 x 25 half resolution (whose last row is a band of its own below); the smallest size test_gpu_optin_shapes.py renders
+SELECT_FRAMES = 2
+_select_refs = {}
+
+
+def _select_state(sc, W, H, sky, slow_filter):
+    st = host.default_state(W, H, sc, None)
+    st.environmentProb = 0.5 if sky else 0.0; st.fireflyClampThreshold = 100.0
+    st.ReSTIRState = abi.RESTIR_SPATIOTEMPORAL   # the direct stage has its levels 1 / 2 (the latency builds forward level 2 to a throughput build)
+    if slow_filter:
+        st.sigLuminDirect = 1e-7                 # below divUniform's range: k_denoise_lds<false, false>
+    assert st.denoise > 0
+    return st
+
+
+def _select_reference(sky, W, H, slow_filter):
+    """The oracle's frames (camera, {buffer: words}) of one (sky, size, filter) setting, rendered once for the three selections that share them"""
+    key = (sky, W, H, slow_filter)
+    if key not in _select_refs:
+        from oracle.binding import Oracle
+        sc, _ = make_scene(abi.PROC_CORNELL)
+        st = _select_state(sc, W, H, sky, slow_filter)
+        o = Oracle(0); o.upload_scene(sc.desc(None)); o.resize(W, H)
+        if sky:
+            o.set_sun_and_sky(abi.SunAndSky(in_use=1))
+        eye, center, up, fov = sc.cameraPose()
+        sc.updateCamera(W, H)
+        frames = []
+        for f in range(SELECT_FRAMES):
+            st.time = 1000 + f
+            sc.setCamera(eye + np.array([0.04 * f, 0.01 * f, -0.03 * f], dtype=np.float32), center, up, fov)
+            sc.updateCamera(W, H)
+            cam = sc.getCamera(); cam = type(cam).from_buffer_copy(cam)
+            o.set_camera(cam); o.render_frame(st, f)
+            frames.append((cam, {b: o.readback(b).view(np.uint32).copy() for b in frame_buffers(f) + [abi.BUF_DIRECT_RESV_TEMP]}))
+        _select_refs[key] = (sc, frames)
+    return _select_refs[key]
+
+
+def _select_render(sky, mode, W, H, slow_filter, staged):
+    """SELECT_FRAMES frames on a fresh context against the oracle's: through rt_render_frame, or stage by stage with the filter and compose stages in two row bands"""
+    from restir_amd.renderer import Renderer
+    sc, frames = _select_reference(sky, W, H, slow_filter)
+    st = _select_state(sc, W, H, sky, slow_filter)
+    r = Renderer().setup(0); r.load_scene(sc.desc(None)); r.update(W, H)
+    try:
+        if sky:
+            r.set_sun_and_sky(abi.SunAndSky(in_use=1))
+        r.set_traversal(abi.TRAVERSAL_LATENCY if mode == "latency" else abi.TRAVERSAL_THROUGHPUT)
+        r.set_counting(mode == "counting")
+        for f, (cam, want) in enumerate(frames):
+            st.time = 1000 + f
+            r.set_camera(cam)
+            if not staged:
+                r.run(st, f)
+            else:
+                r.run_stage(st, f, abi.STAGE_DIRECT, 1); r.run_stage(st, f, abi.STAGE_DIRECT, 2)
+                r.run_stage(st, f, abi.STAGE_INDIRECT, 0)
+                for stage, levels in ((abi.STAGE_DENOISE_DIRECT, 4), (abi.STAGE_DENOISE_INDIRECT, 5), (abi.STAGE_COMPOSE, 1)):
+                    for level in range(levels):
+                        for r0, r1 in ((0, 24), (24, H)):     # (rows of the stage's own grid: the half-resolution chain clamps the second band to H / 2)
+                            r.run_stage(st, f, stage, level, r0, r1)
+            bad = {abi.BUFFER_NAMES[b]: int((r.readback(b).view(np.uint32) != w).sum()) for b, w in want.items()}
+            bad = {k: v for k, v in bad.items() if v}
+            assert not bad, f"sky {sky} {mode} {W}x{H} slow_filter {slow_filter} staged {staged} frame {f}: {bad}"
+        img = r.readback(abi.BUF_DIRECT_RESULT0 + ((SELECT_FRAMES - 1) & 1)).view(np.float32)
+        print(f"sky {sky} {mode} {W}x{H} slow_filter {slow_filter} staged {staged}: max {img.max()}", flush=True)
+        assert np.isfinite(img).all() and img.max() > 0.01       # not comparing two empty frames
+        if staged:   # the filter chains have 4 / 5 levels and compose one, in every selection
+            from restir_amd.renderer import RtError
+            for stage, level in ((abi.STAGE_DENOISE_DIRECT, 4), (abi.STAGE_COMPOSE, 1)):
+                with pytest.raises(RtError, match=rf"\({abi.ERR_INVALID_ARG}\).*level out of range"):
+                    r.run_stage(st, SELECT_FRAMES - 1, stage, level)
+    finally:
+        r.destroy()
+
+
+@pytest.mark.parametrize("W,H", SELECT_SIZES, ids=lambda v: str(v))
+@pytest.mark.parametrize("sky,mode", SELECTIONS, ids=[("sky-" if s else "") + m for s, m in SELECTIONS])
+def test_filter_stages_in_every_selection(sky, mode, W, H):
+    """Sun & sky on / off crossed with the throughput, counting and latency builds of the traced kernels: the filter chains and compose are the same code in all six,
+    and every buffer of two moving-camera Cornell frames equals the oracle's word for word — through rt_render_frame, and stage by stage through rt_run_stage with the
+    two halves of the direct stage, all 4 + 5 filter levels and compose, the filter and compose stages as the row bands [0, 24) and [24, H) band after band within
+    each level; the stage-by-stage frames once more with a luminance sigma that takes the filter without the uniform-divisor shortcut."""
+    _select_render(sky, mode, W, H, slow_filter=False, staged=False)
+    _select_render(sky, mode, W, H, slow_filter=False, staged=True)
+    _select_render(sky, mode, W, H, slow_filter=True, staged=True)
