@@ -131,3 +131,11 @@ class Taa(C.Structure):  # rt_taa, 32 B; defaults = the library's
 RESTIR_NONE, RESTIR_RIS, RESTIR_SPATIAL, RESTIR_TEMPORAL, RESTIR_SPATIOTEMPORAL = range(5)
 # ProcScene (host/scene.hpp)
 PROC_CORNELL, PROC_HELMET, PROC_SPONZA, PROC_BISTRO_EXT, PROC_BISTRO_INT, PROC_BISTRO_EXT_REAL, PROC_SPONZA_1K = range(7)
+# rt_accel_readback ids; record sizes of the device tree (csrc/bvh8.h, csrc/dev_scene.h)
+ACCEL_NODES, ACCEL_TRIS, ACCEL_INSTANCES = range(3)
+ACCEL_RECORD_BYTES = (80, 64, 112)
+
+
+class RefitStats(C.Structure):  # rt_refit_stats, 32 B
+    _fields_ = [("instances", C.c_uint32), ("leafRecords", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("fullRefit", C.c_uint32),
+                ("ms", C.c_float), ("triPad", C.c_float), ("treePad", C.c_float)]

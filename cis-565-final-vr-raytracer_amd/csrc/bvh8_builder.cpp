@@ -708,7 +708,7 @@ inline int slotSign(int slot, int axis) { return (slot >> axis) & 1 ? 1 : -1; }
 }  // namespace
 
 // 3x4 affine inverse: adjugate / determinant for the 3x3 block, then -inv3*t  (same expression order as DESIGN.md §Numerics)
-static void inverseAffine(const float* M, float* R, float* detOut)
+void inverseAffine(const float* M, float* R, float* detOut)
 {
   float a = M[0], b = M[1], c = M[2], d = M[4], e = M[5], f = M[6], g = M[8], h = M[9], i = M[10];
   float A = e * i - f * h, B = f * g - d * i, C = d * h - e * g;

@@ -27,5 +27,8 @@ struct BuildOutput {
 // plainTree: object splits only, no rotations / reinsertion — the tree of rounds 1-4, whatever the environment says (rt_build_accel's fallback when the quality passes
 // made a tree deeper than the traversal stack).
 bool buildBvh8(const rt_scene_desc& scene, BuildOutput& out, int threads, bool plainTree = false);
+// 3x4 affine inverse of an instance matrix (R = world-to-object, *detOut = the determinant of the 3x3 block): the builder's, shared with rt_update_instances so that a
+// moved instance's w2o bits equal a fresh build's
+void inverseAffine(const float* M, float* R, float* detOut);
 
 }  // namespace rt

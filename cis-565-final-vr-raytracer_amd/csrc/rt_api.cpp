@@ -24,6 +24,8 @@
 #include "svgf.h"
 #include "gi_spatial.h"
 #include "taa.h"
+#include "refit.h"
+#include "dev_math.h"
 
 using namespace rt;
 
@@ -115,6 +117,19 @@ struct rt_ctx {
   int taaLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
   bool taaHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame taaFrame[parity] (rt_tonemap)
   int taaFrame[2] = {0, 0};
+  // rt_update_instances (csrc/refit.hip).  Made by the first update after a build from the device tree (ensureRefitState) and dropped with the tree: the record -> node
+  // map, the contiguous node range of every level, per instance its largest |world coordinate| (the pad is a reduction over instances) and its leaf-record count.
+  // The device arrays live in accelAllocs.
+  struct Refit {
+    bool ready = false;
+    std::vector<DevInstance> inst;               // host copy of the device instance rows
+    std::vector<float> instMax;                  // largest |world coordinate| of every instance's triangles
+    std::vector<std::pair<uint32_t, uint32_t>> levels;   // (first node, count), root level first
+    uint32_t* dDirty = nullptr; uint32_t* dFlip = nullptr; uint32_t* dRecNode = nullptr; uint32_t* dNodeDirty = nullptr; uint32_t* dCounters = nullptr;
+    float treePad = 0.f;                         // the pad the tree's boxes were last computed with
+    rt_refit_stats stats{};
+  } refit;
+  hipEvent_t evRefit[2] = {nullptr, nullptr};    // timing of the last update (created by the first one)
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -433,6 +448,7 @@ int rt_destroy(rt_ctx* c)
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
   if(c->evFork) (void)hipEventDestroy(c->evFork);
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
+  for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -493,6 +509,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   RT_HIP(c, syncAll(c));
   LoadTimer lt;
   freePool(c->sceneAllocs); freePool(c->accelAllocs);
+  c->refit = rt_ctx::Refit{};
   c->haveScene = c->haveAccel = false;
   c->refN = 0;   // a new scene: the reference sums start again
   c->svgfValid = false;
@@ -685,6 +702,7 @@ int rt_build_accel(rt_ctx* c)
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   freePool(c->accelAllocs);
+  c->refit = rt_ctx::Refit{};
   c->haveAccel = false;
   c->refN = 0;
   c->svgfValid = false;
@@ -1771,6 +1789,199 @@ int rt_get_stream_layout(rt_ctx* c, int* created, int index[3])
   if(!c) return RT_ERR_INVALID_ARG;
   if(created) *created = g_streamsCreated.load();
   if(index) { index[0] = c->mainIdx; index[1] = c->indStream ? c->indIdx[c->prio[1] + 1] : -1; index[2] = c->sideStream ? c->sideIdx[c->prio[2] + 1] : -1; }
+  return RT_OK;
+}
+
+/* ---- moving instances: leaf-record rewrite + BVH8 refit (include/rt_abi.h "Moving instances", csrc/refit.hip) ---- */
+}  // extern "C"
+
+// largest |world coordinate| over the triangles of instance i under matrix m: the builder's expression (buildBvh8, flatten), per instance
+static float instanceCoordMax(const rt_ctx* c, uint32_t i, const float* m)
+{
+  const rt_prim_mesh& pm = c->primMeshes[c->instances[i].primMesh];
+  float sm = 0.f;
+  for(uint32_t k = 0; k < pm.indexCount; k++) {
+    const rt_vec3& q = c->vertices[pm.vertexOffset + c->indices[pm.firstIndex + k]].position;
+    float w[3];
+    xformPointRaw(m, q.x, q.y, q.z, w);
+    for(int a = 0; a < 3; a++) sm = std::max(sm, std::fabs(w[a]));
+  }
+  return sm;
+}
+
+// what every update needs and no frame does, derived once per tree from the device arrays: the record -> node map, the level ranges, the per-instance maxima
+static int ensureRefitState(rt_ctx* c)
+{
+  rt_ctx::Refit& R = c->refit;
+  if(R.ready) return RT_OK;
+  const size_t nNodes = c->ds.numNodes, nRecs = c->ds.numTris, nInst = c->instances.size();
+  std::vector<Node8> nodes(nNodes);
+  RT_HIP(c, hipMemcpy(nodes.data(), c->ds.nodes, nNodes * sizeof(Node8), hipMemcpyDeviceToHost));
+  R.inst.resize(nInst);
+  if(nInst) RT_HIP(c, hipMemcpy(R.inst.data(), c->ds.instances, nInst * sizeof(DevInstance), hipMemcpyDeviceToHost));
+  // the builder emits wide nodes breadth-first: the nodes of a level are a contiguous range that starts where the level above ends
+  R.levels.clear();
+  std::vector<uint32_t> recNode(std::max<size_t>(nRecs, 1), 0u);
+  uint32_t first = 0, count = 1;
+  while(count > 0 && size_t(first) + count <= nNodes) {
+    R.levels.push_back({first, count});
+    uint32_t next = 0;
+    for(uint32_t n = first; n < first + count; n++) {
+      const Node8& N = nodes[n];
+      next += uint32_t(__builtin_popcount(N.imask));
+      for(int s = 0; s < 8; s++) {
+        if(N.meta[s] == 0 || ((N.imask >> s) & 1u)) continue;
+        const uint32_t cnt = uint32_t(__builtin_popcount(uint32_t(N.meta[s]) >> 5)), off = uint32_t(N.meta[s]) & 31u;
+        for(uint32_t q = 0; q < cnt; q++) if(size_t(N.triBase) + off + q < nRecs) recNode[size_t(N.triBase) + off + q] = n;
+      }
+    }
+    first += count; count = next;
+  }
+  if(size_t(first) != nNodes) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: the tree's levels are not contiguous node ranges");
+  R.instMax.resize(nInst);
+  for(uint32_t i = 0; i < nInst; i++) R.instMax[i] = instanceCoordMax(c, i, c->instances[i].objectToWorld);
+  const size_t words = (nInst + 31) / 32 + 1;
+  int rc;
+  const uint32_t* up = nullptr;
+  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, words, &up))) return rc;
+  R.dDirty = const_cast<uint32_t*>(up);
+  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, words, &up))) return rc;
+  R.dFlip = const_cast<uint32_t*>(up);
+  if((rc = upload(c, c->accelAllocs, recNode.data(), recNode.size(), &up))) return rc;
+  R.dRecNode = const_cast<uint32_t*>(up);
+  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, std::max<size_t>(nNodes, 1), &up))) return rc;
+  R.dNodeDirty = const_cast<uint32_t*>(up);
+  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, 4, &up))) return rc;
+  R.dCounters = const_cast<uint32_t*>(up);
+  for(hipEvent_t& e : c->evRefit) if(!e) RT_HIP(c, hipEventCreate(&e));
+  R.treePad = c->ds.triPad;
+  R.ready = true;
+  return RT_OK;
+}
+
+extern "C" {
+
+int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const float* xf)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_instances: no scene uploaded");
+  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_instances: rt_build_accel has not run");
+  if(count && (!ids || !xf)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: NULL ids / matrices");
+  const size_t nInst = c->instances.size();
+  // the whole call is checked before anything changes
+  std::vector<DevInstance> rows(count);
+  std::vector<uint8_t> flip(count, 0);
+  {
+    std::vector<bool> seen(nInst, false);
+    for(uint32_t k = 0; k < count; k++) {
+      if(ids[k] >= nInst) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: instance id out of range");
+      if(seen[ids[k]]) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: duplicate instance id");
+      seen[ids[k]] = true;
+      for(int a = 0; a < 12; a++) if(!std::isfinite(xf[12 * k + a])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: non-finite matrix entry");
+      DevInstance& di = rows[k];
+      memcpy(di.o2w, xf + 12 * k, sizeof(di.o2w));
+      float det;
+      inverseAffine(di.o2w, di.w2o, &det);
+      if(!(det != 0.0f) || !std::isfinite(det)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: singular matrix");
+      for(int a = 0; a < 12; a++) if(!std::isfinite(di.w2o[a])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: the matrix has no finite inverse");
+      di.primMesh = c->instances[ids[k]].primMesh; di.flags = c->instances[ids[k]].flags; di.pad[0] = di.pad[1] = 0;
+      flip[k] = det < 0.0f;
+    }
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // v1: joins the frames in flight
+  int rc;
+  if((rc = ensureRefitState(c))) return rc;
+  rt_ctx::Refit& R = c->refit;
+  const size_t words = (nInst + 31) / 32 + 1;
+  std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
+  for(uint32_t k = 0; k < count; k++) {
+    const uint32_t i = ids[k];
+    memcpy(c->instances[i].objectToWorld, rows[k].o2w, sizeof(rows[k].o2w));
+    R.inst[i] = rows[k];
+    R.instMax[i] = instanceCoordMax(c, i, rows[k].o2w);
+    dirty[i >> 5] |= 1u << (i & 31u);
+    if(flip[k]) flipBits[i >> 5] |= 1u << (i & 31u);
+  }
+  float scale = 1e-3f;
+  for(float v : R.instMax) scale = std::max(scale, v);
+  const float triPad = 2e-5f * scale;
+  const bool full = triPad > R.treePad && c->ds.numTris > 0;
+  if(triPad > R.treePad) R.treePad = triPad;
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evRefit[0], s));
+  DevInstance* dInst = const_cast<DevInstance*>(c->ds.instances);
+  if(count * 4 > nInst) RT_HIP(c, hipMemcpyAsync(dInst, R.inst.data(), nInst * sizeof(DevInstance), hipMemcpyHostToDevice, s));
+  else for(uint32_t k = 0; k < count; k++) RT_HIP(c, hipMemcpyAsync(dInst + ids[k], &rows[k], sizeof(DevInstance), hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemcpyAsync(R.dDirty, dirty.data(), words * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemsetAsync(R.dNodeDirty, 0, std::max<size_t>(c->ds.numNodes, 1) * 4, s));
+  RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
+  uint32_t counters[4] = {0, 0, 0, 0};
+  if(c->ds.numTris > 0 && (count > 0 || full)) {
+    RefitArgs a{};
+    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
+    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
+    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
+    RT_HIP(c, launchRefitTris(s, a));
+    for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
+    RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
+  }
+  RT_HIP(c, hipEventRecord(c->evRefit[1], s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  c->ds.triPad = triPad;
+  c->refN = 0;   // the scene changed: the reference sums start again
+  R.stats = rt_refit_stats{};
+  R.stats.instances = count; R.stats.leafRecords = counters[0]; R.stats.nodes = counters[1]; R.stats.levels = uint32_t(R.levels.size());
+  R.stats.fullRefit = full ? 1u : 0u; R.stats.triPad = triPad; R.stats.treePad = R.treePad;
+  (void)hipEventElapsedTime(&R.stats.ms, c->evRefit[0], c->evRefit[1]);
+  return RT_OK;
+}
+
+int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, const rt_punc_light* punc, uint32_t numPunc, const rt_light_buf_info* info)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_lights: no scene uploaded");
+  if(!info || numTrig != c->ds.lightInfo.trigLightSize || numPunc != c->ds.lightInfo.puncLightSize || info->trigLightSize != numTrig || info->puncLightSize != numPunc)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_update_lights: the light counts must equal the uploaded ones");
+  if((numTrig && !trig) || (numPunc && !punc)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_lights: NULL light array");
+  for(uint32_t i = 0; i < numTrig; i++)
+    if(trig[i].matIndex >= c->materials.size() || trig[i].impSamp.alias < 0 || uint32_t(trig[i].impSamp.alias) >= numTrig)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_update_lights: triangle light with a bad material or alias index");
+  for(uint32_t i = 0; i < numPunc; i++)
+    if(punc[i].impSamp.alias < 0 || uint32_t(punc[i].impSamp.alias) >= numPunc) return fail(c, RT_ERR_INVALID_ARG, "rt_update_lights: punctual light with a bad alias index");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(numTrig) RT_HIP(c, hipMemcpy(const_cast<rt_trig_light*>(c->ds.trigLights), trig, numTrig * sizeof(rt_trig_light), hipMemcpyHostToDevice));
+  if(numPunc) RT_HIP(c, hipMemcpy(const_cast<rt_punc_light*>(c->ds.puncLights), punc, numPunc * sizeof(rt_punc_light), hipMemcpyHostToDevice));
+  c->ds.lightInfo.trigSampProb = info->trigSampProb;
+  c->refN = 0;
+  return RT_OK;
+}
+
+int rt_get_refit_stats(rt_ctx* c, rt_refit_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->refit.stats;
+  return RT_OK;
+}
+
+int rt_accel_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_accel_readback: rt_build_accel has not run");
+  const void* src = nullptr; size_t want = 0;
+  switch(which) {
+    case RT_ACCEL_NODES: src = c->ds.nodes; want = size_t(c->ds.numNodes) * sizeof(Node8); break;
+    case RT_ACCEL_TRIS: src = c->ds.tris; want = size_t(c->ds.numTris) * sizeof(Tri48); break;
+    case RT_ACCEL_INSTANCES: src = c->ds.instances; want = c->instances.size() * sizeof(DevInstance); break;
+    default: return fail(c, RT_ERR_INVALID_ARG, "rt_accel_readback: which must be RT_ACCEL_NODES / _TRIS / _INSTANCES");
+  }
+  if(bytes != want || (want && !dst)) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(want) RT_HIP(c, hipMemcpy(dst, src, want, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 

@@ -29,6 +29,7 @@ def host_lib():
             "rth_scene_set_camera": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float],
             "rth_scene_get_camera_pose": [C.c_void_p, C.c_void_p], "rth_scene_update_camera": [C.c_void_p, C.c_int, C.c_int],
             "rth_scene_get_camera": [C.c_void_p, C.c_void_p], "rth_scene_light_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
+            "rth_scene_update_instances": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_env_destroy": [C.c_void_p], "rth_env_load": [C.c_void_p, C.c_char_p], "rth_env_set": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
             "rth_env_make_sky": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint32], "rth_env_integral": [C.c_void_p], "rth_env_average": [C.c_void_p],
@@ -104,6 +105,14 @@ class Scene:
         p, t = C.c_float(), C.c_float()
         host_lib().rth_scene_light_weights(self._h, C.byref(p), C.byref(t))
         return p.value, t.value
+    def updateInstances(self, ids, transforms):
+        """Scene::updateInstances: move drawable nodes (transforms: (n, 12) float32, 3 x 4 row-major) and recompute the triangle-light records; desc() afterwards
+        describes the moved scene"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        xf = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 12)
+        assert xf.shape[0] == ids.size
+        if host_lib().rth_scene_update_instances(self._h, ids.ctypes.data, xf.ctypes.data, ids.size) != 0:
+            raise ValueError("Scene.updateInstances: instance id out of range")
     def desc(self, env=None):
         d = abi.SceneDesc()
         host_lib().rth_scene_desc(self._h, env._h if env is not None else None, C.byref(d))

@@ -68,6 +68,10 @@ void rth_scene_stats(void* s, uint64_t* out9)
   out9[0] = st.triangles; out9[1] = st.instancedTriangles; out9[2] = st.vertices; out9[3] = st.primMeshes; out9[4] = st.nodes;
   out9[5] = st.materials; out9[6] = st.textures; out9[7] = st.puncLights; out9[8] = st.trigLights;
 }
+int rth_scene_update_instances(void* s, const uint32_t* ids, const float* transforms, uint32_t count)
+{
+  return static_cast<Scene*>(s)->updateInstances(ids, transforms, count) ? 0 : -1;
+}
 void rth_scene_desc(void* s, void* env, rt_scene_desc* out) { *out = static_cast<Scene*>(s)->getDesc(static_cast<HdrSampling*>(env)); }
 
 void* rth_env_create() { return new(std::nothrow) HdrSampling(); }

@@ -21,6 +21,25 @@ class AccelStructure {
     if(rt_upload_scene(m_ctx, &d) != RT_OK || rt_build_accel(m_ctx) != RT_OK) { fprintf(stderr, "AccelStructure::create: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
+  // Move instances without a rebuild (include/rt_abi.h "Moving instances"): ids + count x 12 floats (3 x 4 row-major).  The reference rebuilds its TLAS per frame
+  // (accelstruct.cpp:132-162); here the moved instances' leaf records are rewritten and the BVH8 above them refitted on the GPU.
+  bool update(const uint32_t* ids, const float* transforms, uint32_t count)
+  {
+    if(rt_update_instances(m_ctx, count, ids, transforms) != RT_OK) { fprintf(stderr, "AccelStructure::update: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  // Scene::updateInstances (host side: instance table, triangle-light records) + update() + rt_update_lights with the records the scene recomputed
+  bool update(Scene& scene, const uint32_t* ids, const float* transforms, uint32_t count)
+  {
+    if(!scene.updateInstances(ids, transforms, count)) { fprintf(stderr, "AccelStructure::update: instance id out of range\n"); return false; }
+    if(!update(ids, transforms, count)) return false;
+    const rt_scene_desc d = scene.getDesc(nullptr);
+    if(rt_update_lights(m_ctx, d.trigLights, d.trigLights ? d.lightInfo.trigLightSize : 0, d.puncLights, d.puncLights ? d.lightInfo.puncLightSize : 0, &d.lightInfo) != RT_OK) {
+      fprintf(stderr, "AccelStructure::update: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
   void destroy() {}  // owned by the context
  private:
   rt_ctx* m_ctx = nullptr;

@@ -4,6 +4,7 @@
 #include "pack.h"
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 
 namespace rth {
 
@@ -252,6 +253,21 @@ void Scene::updateCamera(int width, int height)  // scene.cpp:777-795
   m_camera.lastPosition = R3(m_lastEye);  // `static eye` starts at 0 (scene.cpp:780)
   m_lastEye = m_eye;
   m_cameraInit = true;
+}
+
+bool Scene::updateInstances(const uint32_t* ids, const float* transforms, uint32_t count)
+{
+  for(uint32_t k = 0; k < count; k++) if(ids[k] >= m_gltf.nodes.size()) return false;
+  for(uint32_t k = 0; k < count; k++) {
+    M4 m = M4::identity();
+    for(int r = 0; r < 3; r++) for(int c = 0; c < 4; c++) m.at(r, c) = transforms[12 * k + r * 4 + c];
+    m_gltf.nodes[ids[k]].worldMatrix = m;
+    memcpy(m_instances[ids[k]].objectToWorld, transforms + 12 * k, 12 * sizeof(float));
+  }
+  createTrigLightBuffer();   // (every emissive node: the records keep their order, and the alias table depends on the materials only)
+  if(m_lightBufInfo.puncLightSize > 0 || m_lightBufInfo.trigLightSize > 0)
+    m_lightBufInfo.trigSampProb = m_trigLightWeight / (m_trigLightWeight + m_puncLightWeight);
+  return true;
 }
 
 rt_scene_desc Scene::getDesc(const HdrSampling* env) const

@@ -83,6 +83,12 @@ class Scene {
   const GltfScene& getScene() const { return m_gltf; }
   // The upload payload; `env` may be null (=> 1x1 black environment).  Pointers stay valid until destroy()/load().
   rt_scene_desc getDesc(const HdrSampling* env) const;
+  // Move drawable nodes: transforms = count x 12 floats, 3 rows x 4 columns, row-major (rt_instance::objectToWorld).  Rewrites the nodes' world matrices and the
+  // instance table, and recomputes the triangle-light records and their alias table (createTrigLightBuffer) so that a moved emitter lights from its new place; the
+  // number of lights does not change.  False (nothing changed) for an id out of range.  AccelStructure::update hands the same arrays to the device tree;
+  // getDesc() afterwards describes the moved scene (rt_update_lights takes trigLights / puncLights / lightInfo from it).  The reference moves a node by editing
+  // nvh::GltfScene::m_nodes and rebuilding its TLAS (src/accelstruct.cpp:132-162).
+  bool updateInstances(const uint32_t* ids, const float* transforms, uint32_t count);
 
   float m_puncLightWeight = 0.f, m_trigLightWeight = 0.f;  // scene.hpp:79-80
   rt_light_buf_info m_lightBufInfo{};                      // scene.hpp:113 (zero-initialised here: quirk 10)

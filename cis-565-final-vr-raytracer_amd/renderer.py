@@ -21,6 +21,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
+               "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -114,6 +115,11 @@ def hip_lib():
             L.rt_taa_reset.argtypes = [C.c_void_p]
             L.rt_taa_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
             L.rt_taa_jitter_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if hasattr(L, "rt_update_instances"):   # moving instances (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_update_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rt_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+            L.rt_get_refit_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_accel_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -399,6 +405,35 @@ class Renderer:
         rc = hip_lib().rt_taa_jitter_camera(C.byref(cam), int(frames), int(jitter_phases), int(width), int(height), C.byref(out))
         if rc != 0:
             raise RtError(f"rt_taa_jitter_camera failed ({rc})")
+        return out
+
+    # ---- moving instances (include/rt_abi.h "Moving instances")
+    def update_instances(self, ids, transforms):
+        """rt_update_instances: ids (n,) and transforms (n, 12) float32, 3 x 4 row-major like rt_instance::objectToWorld.  Rewrites the moved instances' leaf records
+        and refits the BVH8 above them on the GPU; drains the frames in flight"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        xf = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1)
+        if xf.size != 12 * ids.size:
+            raise ValueError("update_instances: 12 floats per id")
+        self._chk(hip_lib().rt_update_instances(self._h, ids.size, ids.ctypes.data, xf.ctypes.data), "rt_update_instances")
+
+    def update_lights(self, desc):
+        """rt_update_lights with the light records of a scene description (Scene.updateInstances recomputes them for moved emitters)"""
+        nt = desc.lightInfo.trigLightSize if desc.trigLights else 0
+        npu = desc.lightInfo.puncLightSize if desc.puncLights else 0
+        self._chk(hip_lib().rt_update_lights(self._h, desc.trigLights, nt, desc.puncLights, npu, C.byref(desc.lightInfo)), "rt_update_lights")
+
+    def refit_stats(self):
+        s = abi.RefitStats()
+        self._chk(hip_lib().rt_get_refit_stats(self._h, C.byref(s)), "rt_get_refit_stats")
+        return s
+
+    def accel_readback(self, which, num_instances=None):
+        """the device tree as raw bytes: abi.ACCEL_NODES (80 B per node), ACCEL_TRIS (64 B per leaf record), ACCEL_INSTANCES (112 B per instance; pass num_instances)"""
+        st = self.accel_stats()
+        count = {abi.ACCEL_NODES: st["nodes"], abi.ACCEL_TRIS: st["references"], abi.ACCEL_INSTANCES: num_instances}[which]
+        out = np.empty(int(count) * abi.ACCEL_RECORD_BYTES[which], dtype=np.uint8)
+        self._chk(hip_lib().rt_accel_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_accel_readback")
         return out
 
     def accel_stats(self):

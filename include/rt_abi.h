@@ -671,11 +671,55 @@ int rt_taa_reset(rt_ctx* ctx);
 int rt_taa_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 /* pure function, no context, callable without a GPU: the camera the context renders frame `frames` with (jitterPhases 0..16, width, height >= 1) */
 int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Moving instances (added within ABI 2.4, no version bump; csrc/refit.hip).  The reference changes an instance's objectToWorld and rebuilds its TLAS per frame
+ * (src/accelstruct.cpp:132-162).  Here every (instance, triangle) pair is a world-space leaf record of one flat BVH8, so a move rewrites the leaf records of the
+ * moved instances and refits the node boxes above them on the GPU; the tree keeps its topology (no rebuild, no re-derived alpha records or micro-maps, no upload
+ * of the scene).  Results are a function of the triangle set only, never of the tree, so frames and ray queries after an update are bit for bit
+ * those of a context that uploaded and built the moved scene; what a refitted tree loses against a fresh one is speed (profiles/refit_timing.txt).
+ *
+ * rt_update_instances(ctx, count, instanceIds, objectToWorld): objectToWorld = count x 12 floats, the layout of rt_instance::objectToWorld.
+ *   Valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise).  An id out of range, a duplicate id, a non-finite matrix entry or a determinant that is
+ *   zero or not finite refuses the WHOLE call with RT_ERR_INVALID_ARG and changes nothing.  count == 0 is a valid call that moves nothing.
+ *   It overwrites objectToWorld in the context's copy of the scene (a later rt_build_accel builds the moved scene); the device instance rows (objectToWorld and its
+ *   inverse, the builder's own expression, so the bits equal a fresh build's); v0 / e1 / e2 and the TRI_FLIP bit of EVERY leaf record of those instances (spatial-split
+ *   duplicates included; globalId, alphaIdx, the micro-map and the other flags stay); the boxes of every node above such a record; and the hit rule's pad
+ *   2e-5 * max(1e-3, largest |world coordinate| over all triangles), which equals a fresh build's value.  A leaf slot whose triangles did not move keeps its box (its
+ *   bytes where the node's grid of that axis did not change); a node with no moved record below it keeps all 80 bytes.  When the pad grows beyond the one the
+ *   tree's boxes were computed with, every leaf box is recomputed with the new pad (rt_refit_stats::fullRefit); a smaller pad leaves the boxes as they are.
+ *   It resets the reference-mode sums (n -> 0) like rt_build_accel.  It leaves the SVGF and TAA histories alone: their consistency tests (material hash, normal,
+ *   depth) reject a surface that changed under a pixel, and motion vectors stay camera-only as in the reference.  It does not re-open the stream-priority decision
+ *   and frees nothing.
+ *   Ordering: v1 drains the pipeline — the call joins the frames in flight, runs its kernels on the context's main stream and returns after they completed.
+ *   Scope: the single-GPU context only.  rt_mgpu_* contexts and the row-tiled hosts (restir_amd/tiled.py) have no update path: they upload the moved scene.
+ * rt_update_lights: overwrites the device light arrays in place, for a host that moved an emissive instance (its Scene recomputes the triangle-light records; without
+ *   this call a moved emitter keeps lighting from its old place).  numTrig / numPunc and info's sizes must equal the uploaded counts, and the records pass the index
+ *   checks of rt_upload_scene, else RT_ERR_INVALID_ARG and nothing changes.  info->trigSampProb replaces the uploaded one.  Resets the reference-mode sums; drains the pipeline.
+ * rt_get_refit_stats: what the last rt_update_instances did.
+ * rt_accel_readback: the device tree as it is now, for tests and diagnostics: RT_ACCEL_NODES (80 B per node, rt_accel_stats' node count), RT_ACCEL_TRIS (64 B per
+ *   leaf record, rt_accel_quality's reference count), RT_ACCEL_INSTANCES (112 B per instance: objectToWorld, worldToObject, primMesh, flags, 8 B of padding).
+ *   `bytes` must be the exact size.  Synchronous.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t instances;     /* instances moved by the call */
+  uint32_t leafRecords;   /* leaf records rewritten */
+  uint32_t nodes;         /* nodes refitted */
+  uint32_t levels;        /* levels of the tree (one launch each) */
+  uint32_t fullRefit;     /* 1: the pad grew and every leaf box was recomputed */
+  float    ms;            /* HIP-event time of the call's kernels and copies on the main stream */
+  float    triPad;        /* the hit rule's pad after the call */
+  float    treePad;       /* the pad the tree's boxes are computed with (>= triPad) */
+} rt_refit_stats;         /* 32 B */
+enum { RT_ACCEL_NODES = 0, RT_ACCEL_TRIS = 1, RT_ACCEL_INSTANCES = 2 };
+int rt_update_instances(rt_ctx* ctx, uint32_t count, const uint32_t* instanceIds, const float* objectToWorld);
+int rt_update_lights(rt_ctx* ctx, const rt_trig_light* trigLights, uint32_t numTrig, const rt_punc_light* puncLights, uint32_t numPunc, const rt_light_buf_info* info);
+int rt_get_refit_stats(rt_ctx* ctx, rt_refit_stats* out);
+int rt_accel_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
+/* ABI version: (major<<16)|minor.  2.4: + moving instances (rt_update_instances, rt_update_lights, rt_get_refit_stats, rt_accel_readback; additions that change no existing call, so the version stays 2.4 like the three opt-in passes before them), + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
  * (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; opt-in additions that change no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
@@ -700,6 +744,7 @@ static_assert(sizeof(rt_sun_and_sky) == 96, "SunAndSky host_device.h:353-377");
 static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
 static_assert(sizeof(rt_gi_spatial) == 32, "rt_gi_spatial");
 static_assert(sizeof(rt_taa) == 32, "rt_taa");
+static_assert(sizeof(rt_refit_stats) == 32, "rt_refit_stats");
 #endif
 
 #endif /* RT_ABI_H */
