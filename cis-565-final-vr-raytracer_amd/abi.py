@@ -136,6 +136,11 @@ ACCEL_NODES, ACCEL_TRIS, ACCEL_INSTANCES = range(3)
 ACCEL_RECORD_BYTES = (80, 64, 112)
 
 
+class RebuildStats(C.Structure):  # rt_rebuild_stats, 32 B
+    _fields_ = [("triangles", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("maxDepth", C.c_uint32), ("ms", C.c_float), ("sortMs", C.c_float),
+                ("triPad", C.c_float), ("reserved", C.c_uint32)]
+
+
 class RefitStats(C.Structure):  # rt_refit_stats, 32 B
     _fields_ = [("instances", C.c_uint32), ("leafRecords", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("fullRefit", C.c_uint32),
                 ("ms", C.c_float), ("triPad", C.c_float), ("treePad", C.c_float)]

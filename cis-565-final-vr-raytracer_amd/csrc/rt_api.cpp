@@ -25,6 +25,7 @@
 #include "gi_spatial.h"
 #include "taa.h"
 #include "refit.h"
+#include "accel_build.h"
 #include "dev_math.h"
 
 using namespace rt;
@@ -130,6 +131,17 @@ struct rt_ctx {
     rt_refit_stats stats{};
   } refit;
   hipEvent_t evRefit[2] = {nullptr, nullptr};    // timing of the last update (created by the first one)
+  // rt_rebuild_accel (csrc/accel_build.hip).  Working buffers and two trees (the build writes the one the frames do not read; they swap after a build that succeeded),
+  // allocated by the first rebuild after a host build and dropped with the host tree; `table` holds what the host build derived per triangle.
+  struct Rebuild {
+    AccelBuildWork work;
+    AccelBuildSet set[2];
+    int cur = -1;                                // the set the context's tree lives in (-1: the host build's arrays)
+    bool ready = false;
+    rt_rebuild_stats stats{};
+  } rebuild;
+  std::vector<void*> rebuildAllocs;
+  hipEvent_t evRebuild[4] = {nullptr, nullptr, nullptr, nullptr};   // start, sort begin, sort end, end
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -426,7 +438,7 @@ int rt_destroy(rt_ctx* c)
   if(!c) return RT_ERR_INVALID_ARG;
   (void)hipSetDevice(c->device);
   (void)syncAll(c);
-  freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs);
+  freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
@@ -449,6 +461,7 @@ int rt_destroy(rt_ctx* c)
   if(c->evFork) (void)hipEventDestroy(c->evFork);
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
   for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -508,8 +521,9 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   LoadTimer lt;
-  freePool(c->sceneAllocs); freePool(c->accelAllocs);
+  freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->rebuildAllocs);
   c->refit = rt_ctx::Refit{};
+  c->rebuild = rt_ctx::Rebuild{};
   c->haveScene = c->haveAccel = false;
   c->refN = 0;   // a new scene: the reference sums start again
   c->svgfValid = false;
@@ -701,8 +715,9 @@ int rt_build_accel(rt_ctx* c)
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_build_accel: no scene uploaded");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
-  freePool(c->accelAllocs);
+  freePool(c->accelAllocs); freePool(c->rebuildAllocs);
   c->refit = rt_ctx::Refit{};
+  c->rebuild = rt_ctx::Rebuild{};
   c->haveAccel = false;
   c->refN = 0;
   c->svgfValid = false;
@@ -1957,6 +1972,112 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
   if(numPunc) RT_HIP(c, hipMemcpy(const_cast<rt_punc_light*>(c->ds.puncLights), punc, numPunc * sizeof(rt_punc_light), hipMemcpyHostToDevice));
   c->ds.lightInfo.trigSampProb = info->trigSampProb;
   c->refN = 0;
+  return RT_OK;
+}
+
+/* ---- rebuilding on the device: LBVH -> BVH8 (include/rt_abi.h "Rebuilding on the device", csrc/accel_build.hip) ---- */
+int rt_rebuild_accel(rt_ctx* c)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_rebuild_accel: no scene uploaded");
+  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_rebuild_accel: rt_build_accel has not run");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // drains the frames in flight, like rt_update_instances
+  int rc;
+  if((rc = ensureRefitState(c))) return rc;
+  rt_ctx::Refit& R = c->refit;
+  rt_ctx::Rebuild& B = c->rebuild;
+  const uint32_t n = uint32_t(c->numTris);
+  const size_t nInst = c->instances.size();
+  hipStream_t s = c->stream;
+  if(!B.ready) {   // the first rebuild after a host build: buffers, and the per-triangle table from the host tree's records (still the context's tree)
+    const hipError_t e = accelBuildAlloc(B.work, B.set, n, c->rebuildAllocs);
+    if(e != hipSuccess) {
+      freePool(c->rebuildAllocs); B = rt_ctx::Rebuild{};
+      c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+    hipError_t e1 = launchAccelTable(s, c->ds.tris, c->ds.numTris, B.work);
+    for(hipEvent_t& e2 : c->evRebuild) if(e1 == hipSuccess && !e2) e1 = hipEventCreate(&e2);
+    if(e1 != hipSuccess) {   // nothing of a first rebuild that failed is kept: the next call starts again
+      (void)hipStreamSynchronize(s);
+      freePool(c->rebuildAllocs); B = rt_ctx::Rebuild{};
+      c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e1);
+      return e1 == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+    B.ready = true;
+  }
+  // the pad of the scene as it is now (the per-instance maxima are kept by rt_update_instances), and every instance's handedness
+  float scale = 1e-3f;
+  for(float v : R.instMax) scale = std::max(scale, v);
+  const float triPad = 2e-5f * scale;
+  const size_t words = (nInst + 31) / 32 + 1;
+  std::vector<uint32_t> all(words, 0xffffffffu), flipBits(words, 0u);
+  for(size_t i = 0; i < nInst; i++) {
+    float inv[12], det;
+    inverseAffine(R.inst[i].o2w, inv, &det);
+    if(det < 0.0f) flipBits[i >> 5] |= 1u << (i & 31u);
+  }
+  rt_rebuild_stats st{};
+  st.triangles = n; st.triPad = triPad;
+  RT_HIP(c, hipEventRecord(c->evRebuild[0], s));
+  if(n > 0) {
+    const int target = B.cur == 0 ? 1 : 0;
+    const AccelBuildSet& T = B.set[target];
+    RT_HIP(c, hipMemcpyAsync(R.dDirty, all.data(), words * 4, hipMemcpyHostToDevice, s));
+    RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
+    RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
+    RefitArgs a{};
+    a.nodes = T.nodes; a.tris = T.tris; a.triRef = c->ds.triRef; a.instances = c->ds.instances;
+    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = T.recNode; a.nodeDirty = B.work.nodeDirty; a.counters = R.dCounters;
+    a.numRecs = n; a.pad = triPad; a.full = 1;
+    AccelBuildResult res;
+    hipError_t he = hipSuccess;
+    const int br = accelBuildRun(s, B.work, T, a, c->ds.alphaRec, STACK_MAX, c->evRebuild + 1, res, &he);
+    // a build that failed leaves the context's tree as it was: only the other set and the working buffers were written
+    if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
+    if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_rebuild_accel: BVH8 deeper than the traversal stack");
+    if(br != ACCEL_BUILD_OK) { c->err = std::string("rt_rebuild_accel: ") + accelBuildWhy(br); return RT_ERR_HIP; }   // a builder invariant, not the caller's argument
+    RT_HIP(c, hipEventRecord(c->evRebuild[3], s));
+    RT_HIP(c, hipStreamSynchronize(s));
+    // ---- swap ----
+    const int depth = int(res.levels.size());
+    const int stackTotal = std::max(8, ((depth + 1 + 3) / 4) * 4);
+    const DevScene old = c->ds;
+    c->ds.nodes = T.nodes; c->ds.tris = T.tris; c->ds.alphaByTri = T.alphaByTri;
+    c->ds.numNodes = res.nodes; c->ds.numTris = n;
+    if(stackTotal != old.stackTotal) {
+      c->ds.stackTotal = stackTotal; c->ds.stackEntries = stackTotal;
+      if((rc = ensureStackOverflow(c))) {   // the previous tree stays, with its stack
+        const std::string msg = c->err;
+        c->ds = old; c->ds.stackOvf = c->ds.stackOvfInd = nullptr; c->ds.stackOvfThreads = 0;
+        (void)ensureStackOverflow(c);
+        c->err = msg;
+        return rc;
+      }
+    }
+    B.cur = target;
+    c->ds.triPad = triPad;
+    c->numNodes = res.nodes; c->numRefs = n; c->spatialSplits = 0; c->maxDepth = depth;
+    c->sahNodeSteps = c->sahTriSteps = 0;   // (the host builder's SAH expectation: not computed on the device)
+    // rt_update_instances works on the new tree: its maps come from the build
+    R.levels = res.levels; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
+    st.nodes = res.nodes; st.levels = uint32_t(depth); st.maxDepth = uint32_t(depth);
+    (void)hipEventElapsedTime(&st.ms, c->evRebuild[0], c->evRebuild[3]);
+    (void)hipEventElapsedTime(&st.sortMs, c->evRebuild[1], c->evRebuild[2]);
+  } else {
+    st.nodes = uint32_t(c->numNodes); st.levels = st.maxDepth = uint32_t(c->maxDepth);   // no triangles: the single empty node stays
+  }
+  c->refN = 0;   // the reference sums start again
+  B.stats = st;
+  return RT_OK;
+}
+
+int rt_get_rebuild_stats(rt_ctx* c, rt_rebuild_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->rebuild.stats;
   return RT_OK;
 }
 

@@ -40,6 +40,14 @@ class AccelStructure {
     }
     return true;
   }
+  // A new topology for the moved scene, built on the GPU (include/rt_abi.h "Rebuilding on the device"): the host's remedy when rt_refit_stats::fullRefit is set
+  // or the refitted tree has become slow.  The previous tree stays in place when it fails.
+  bool rebuild()
+  {
+    if(rt_rebuild_accel(m_ctx) != RT_OK) { fprintf(stderr, "AccelStructure::rebuild: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_rebuild_stats rebuildStats() const { rt_rebuild_stats s{}; (void)rt_get_rebuild_stats(m_ctx, &s); return s; }
   void destroy() {}  // owned by the context
  private:
   rt_ctx* m_ctx = nullptr;

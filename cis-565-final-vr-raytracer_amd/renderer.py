@@ -21,7 +21,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
-               "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback",
+               "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -120,6 +120,9 @@ def hip_lib():
             L.rt_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
             L.rt_get_refit_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_accel_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        if hasattr(L, "rt_rebuild_accel"):   # rebuilding on the device (absent from older A/B libraries)
+            L.rt_rebuild_accel.argtypes = [C.c_void_p]
+            L.rt_get_rebuild_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -426,6 +429,16 @@ class Renderer:
     def refit_stats(self):
         s = abi.RefitStats()
         self._chk(hip_lib().rt_get_refit_stats(self._h, C.byref(s)), "rt_get_refit_stats")
+        return s
+
+    # ---- rebuilding on the device (include/rt_abi.h "Rebuilding on the device")
+    def rebuild_accel(self):
+        """rt_rebuild_accel: a new BVH8 topology built on the GPU from the scene as it is after the update_instances calls so far; drains the frames in flight"""
+        self._chk(hip_lib().rt_rebuild_accel(self._h), "rt_rebuild_accel")
+
+    def rebuild_stats(self):
+        s = abi.RebuildStats()
+        self._chk(hip_lib().rt_get_rebuild_stats(self._h, C.byref(s)), "rt_get_rebuild_stats")
         return s
 
     def accel_readback(self, which, num_instances=None):

@@ -715,6 +715,41 @@ int rt_update_instances(rt_ctx* ctx, uint32_t count, const uint32_t* instanceIds
 int rt_update_lights(rt_ctx* ctx, const rt_trig_light* trigLights, uint32_t numTrig, const rt_punc_light* puncLights, uint32_t numPunc, const rt_light_buf_info* info);
 int rt_get_refit_stats(rt_ctx* ctx, rt_refit_stats* out);
 int rt_accel_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Rebuilding on the device (added within ABI 2.4, no version bump; csrc/accel_build.hip).  A refitted tree keeps the topology of the scene it was
+ * built for and traces slower the further the instances move (profiles/refit_timing.txt); rt_build_accel is the host builder and pauses a large scene for more than a
+ * second.  rt_rebuild_accel builds a NEW topology on the GPU from the scene as it is after all rt_update_instances calls so far: Morton order of the triangle box
+ * centres (63-bit keys), a binary radix tree over the sorted keys, a top-down collapse to 8-wide nodes, and the refit kernel's boxes.  No spatial splits and no SAH:
+ * one leaf record per (instance, triangle) pair.  Results are a function of the triangle set only: frames and ray queries on the device-built tree are
+ * bit for bit those of the host-built tree; the two differ in speed (profiles/accel_build_timing.txt).  The build is deterministic: the same scene gives the same words.
+ *
+ * rt_rebuild_accel(ctx): valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise) — the host build stays the way a scene gets its first tree, and it
+ *   is the source of what does not depend on position (globalId, TRI_OPAQUE / TRI_NOCULL, alphaIdx, the opacity micro-map), kept per triangle on the device.
+ *   Ordering: like rt_update_instances v1 it joins the frames in flight, runs on the context's main stream and returns after its kernels completed.
+ *   It leaves the frame buffers, the SVGF / TAA histories and the stream-priority decision alone, and resets the reference-mode sums (n -> 0).
+ *   Afterwards rt_accel_stats, rt_accel_quality's reference count (= the triangle count; the SAH expectations read 0) and rt_accel_readback describe the new tree,
+ *   the hit rule's pad and the pad of the tree's boxes are both 2e-5 * max(1e-3, largest |world coordinate|), and rt_update_instances works on the new tree.  A
+ *   later rt_build_accel builds the host tree of the moved scene, as before.
+ *   Buffers: working buffers and two trees (the build never writes the tree the context uses; they swap on success) are allocated by the first rebuild after a host
+ *   build, about 0.7 KB per triangle, and kept; a repeated rebuild allocates and frees nothing unless the tree's depth crosses a multiple of 4 (the traversal stack).
+ *   Failure: a wide tree deeper than the traversal stack (64 levels) gives RT_ERR_INVALID_ARG, an allocation that fails RT_ERR_OOM, a HIP error or an internal
+ *   invariant of the builder that did not hold RT_ERR_HIP (rt_last_error names it); the previous tree stays in place and usable.
+ *   Scope: the single-GPU context only.  rt_mgpu_* contexts and the row-tiled hosts (restir_amd/tiled.py) have no rebuild path: they upload the moved scene.
+ * rt_get_rebuild_stats: what the last rt_rebuild_accel did.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t triangles;     /* leaf records = (instance, triangle) pairs */
+  uint32_t nodes;         /* wide nodes */
+  uint32_t levels;        /* levels of the wide tree (one collapse launch each) */
+  uint32_t maxDepth;      /* rt_accel_stats' depth of the new tree (= levels) */
+  float    ms;            /* HIP-event time of the call's kernels and copies on the main stream */
+  float    sortMs;        /* of which the radix sort */
+  float    triPad;        /* the hit rule's pad = the pad of the tree's boxes after the call */
+  uint32_t reserved;
+} rt_rebuild_stats;       /* 32 B */
+int rt_rebuild_accel(rt_ctx* ctx);                       /* LBVH -> BVH8 on the GPU from the context's current scene */
+int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
