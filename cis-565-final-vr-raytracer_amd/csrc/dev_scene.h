@@ -87,4 +87,15 @@ struct DevFrame {
   int32_t pad4;
 };
 
+// object motion vectors (rt_set_object_motion; the RT_OM builds of stages.hip take it as a kernel argument of its own, so DevFrame keeps its layout)
+struct OmCamera {   // row i: what rt_object_motion_camera replaces in the camera for a pixel that sees instance i — 80 B, 16-byte aligned
+  rt_mat4 lastProjView;
+  rt_vec3 lastPosition; float pad;
+};
+struct DevObjMotion {
+  uint32_t* instImage;      // W x H: instance of the primary hit, 0xffffffff at a miss; written by the direct stage, read by the indirect stage of the same frame at 2p
+  const OmCamera* cams;     // numInst rows, or nullptr when no instance is in motion this frame (every pixel then takes the camera's values)
+  uint32_t numInst, pad;
+};
+
 }  // namespace rt

@@ -142,6 +142,18 @@ struct rt_ctx {
   } rebuild;
   std::vector<void*> rebuildAllocs;
   hipEvent_t evRebuild[4] = {nullptr, nullptr, nullptr, nullptr};   // start, sort begin, sort end, end
+  // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
+  // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
+  int objMotion = RT_OBJECT_MOTION_OFF;
+  std::vector<std::array<float, 12>> omPrev;
+  std::vector<uint8_t> omMoved;
+  bool omPending = false;    // some omMoved flag is set
+  // the instance image (lifetime of RT_BUF_MOTION: rotated with it) and the per-instance camera table (rewritten only by frames with motion, which follow the
+  // drain of rt_update_instances, so one copy serves the frames in flight); allocated once the mode has been switched on
+  void* omInst = nullptr; void* omInstSpare = nullptr; void* omInstSpare2 = nullptr;
+  bool omInstValid = false;  // a frame has written omInst since rt_resize
+  void* omTable = nullptr; size_t omTableRows = 0;
+  std::vector<OmCamera> omHost;
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -204,9 +216,8 @@ static int latTilesIndirect(bool shared)
 }
 static hipError_t filterLauncher(hipStream_t stream, const DevScene&, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int r0, int r1)
 { return rt::launchFilterStage(stream, F, st, cam, stage, level, r0, r1); }
-static StageLauncher stageLauncher(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
+static bool latencyBuild(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
 {
-  if(stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT || stage == RT_STAGE_COMPOSE) return filterLauncher;
   bool lat = false;
   if(!c->counting && (stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT)) {
     if(c->traversal == RT_TRAVERSAL_LATENCY) lat = true;
@@ -218,8 +229,23 @@ static StageLauncher stageLauncher(const rt_ctx* c, const rt_state& st, int stag
       lat = tiles <= (half ? latTilesIndirect(c->overlap >= 2) : latTilesDirect(c->overlap >= 2));
     }
   }
+  return lat;
+}
+static StageLauncher stageLauncher(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
+{
+  if(stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT || stage == RT_STAGE_COMPOSE) return filterLauncher;
+  const bool lat = latencyBuild(c, st, stage, rowBegin, rowEnd);
   if(c->ds.sky) return lat ? rt::sky_lat::launchStage : (c->counting ? rt::sky_cnt::launchStage : rt::sky::launchStage);
   return lat ? rt::base_lat::launchStage : (c->counting ? rt::base_cnt::launchStage : rt::base::launchStage);
+}
+
+// the direct and the indirect stage of a frame rendered with object motion vectors on: the same choice among the four RT_OM builds (no counting form)
+typedef hipError_t (*OmStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const DevObjMotion&, const rt_state&, const rt_scene_camera&, int, int, int, int);
+static OmStageLauncher omStageLauncher(const rt_ctx* c, const rt_state& st, int stage)
+{
+  const bool lat = latencyBuild(c, st, stage, 0, 0);
+  if(c->ds.sky) return lat ? rt::sky_lat_om::launchStage : rt::sky_om::launchStage;
+  return lat ? rt::base_lat_om::launchStage : rt::base_om::launchStage;
 }
 
 // ---- host side of rt_build_accel, cached by scene content (buildHostAccel below) ---------------------------------------------------------------------
@@ -312,6 +338,14 @@ static void freeGiSpatial(rt_ctx* c)
   if(c->gisResv) (void)hipFree(c->gisResv);
   c->gisResv = nullptr; c->gisWritten = false;
 }
+// the instance images of rt_set_object_motion, and the motion state: what moved before the buffers were dropped is not in motion for the next frame
+// (the caller has drained the context)
+static void freeObjectMotion(rt_ctx* c)
+{
+  for(void** p : {&c->omInst, &c->omInstSpare, &c->omInstSpare2}) if(*p) { (void)hipFree(*p); *p = nullptr; }
+  c->omInstValid = false;
+  c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;
+}
 // the TAA history (the caller has drained the context)
 static void freeTaaHistory(rt_ctx* c)
 {
@@ -360,6 +394,7 @@ struct LoadTimer {
   void lap(const char* what) { if(!on) return; const auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[scene load] %-34s %.3f s\n", what, std::chrono::duration<double>(n - t).count()); t = n; }
 };
 static int ensureStackOverflow(rt_ctx* c);
+static int allocObjectMotion(rt_ctx* c);
 static void reopenPriorityDecision(rt_ctx* c);
 static void hashBytes(const void* p, size_t n, uint64_t& h0, uint64_t& h1);
 static int stackLdsEnv() { static const int v = getenv("RESTIR_STACK_LDS") ? std::max(2, atoi(getenv("RESTIR_STACK_LDS"))) : 0; return v; }
@@ -440,7 +475,7 @@ int rt_destroy(rt_ctx* c)
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
-  for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes}) if(p) (void)hipFree(p);
+  for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
   for(hipStream_t& q : c->indStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
   for(hipStream_t& q : c->sideStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
@@ -528,6 +563,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->refN = 0;   // a new scene: the reference sums start again
   c->svgfValid = false;
   c->taaValid = false;
+  c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // object motion: nothing of the new scene has moved
   c->ds = DevScene{};
   c->ds.sky = (c->sunAndSky.in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
   c->primMeshes.assign(d->primMeshes, d->primMeshes + d->numPrimMeshes);
@@ -790,6 +826,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   freeSvgfHistory(c);
   freeGiSpatial(c);
   freeTaaHistory(c);
+  freeObjectMotion(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -836,6 +873,7 @@ int rt_resize(rt_ctx* c, int w, int h)
 #undef RT_SCRATCH
   RT_HIP(c, hipDeviceSynchronize());  // memsets above ran on the null stream; the ctx stream does not wait for it implicitly
   c->W = w; c->H = h;
+  if(c->objMotion != RT_OBJECT_MOTION_OFF && (rc = allocObjectMotion(c))) return rc;
   return ensureStackOverflow(c);
 }
 
@@ -963,6 +1001,18 @@ static GiSpatialArgs giSpatialArgs(const rt_ctx* c, const DevFrame& F)
   return A;
 }
 
+// The instance images of rt_set_object_motion (callers have drained the context); they start as "miss everywhere"
+static int allocObjectMotion(rt_ctx* c)
+{
+  const size_t bytes = size_t(c->W) * c->H * sizeof(uint32_t);
+  for(void** p : {&c->omInst, &c->omInstSpare, &c->omInstSpare2}) {
+    if(*p) continue;
+    RT_HIP(c, hipMalloc(p, std::max<size_t>(bytes, 256)));
+    RT_HIP(c, hipMemset(*p, 0xff, std::max<size_t>(bytes, 256)));
+  }
+  RT_HIP(c, hipDeviceSynchronize());
+  return RT_OK;
+}
 // The TAA history of both parities (rt_render_frame's first frame with the mode on; the caller has drained the context).  Zeroed: nothing reads it before a
 // frame wrote it.
 static int allocTaaHistory(rt_ctx* c)
@@ -1096,6 +1146,30 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   if(taa && !c->taaHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocTaaHistory(c))) return rc; }
   rt_scene_camera cam = c->cam;   // the camera of this frame's launches (c->cam stays what rt_set_camera stored)
   if(taa) (void)rt_taa_jitter_camera(&c->cam, frames, c->taa.jitterPhases, c->W, c->H, &cam);
+  // Object motion vectors (rt_set_object_motion): the direct and the indirect stage come from the RT_OM builds, which write / read the instance image; when an
+  // instance is in motion they also read the per-instance camera table, filled here and uploaded ahead of the direct stage on its stream (below)
+  const bool om = c->objMotion == RT_OBJECT_MOTION_ON && !c->counting && c->omInst;
+  bool omMotion = false;
+  if(c->objMotion == RT_OBJECT_MOTION_ON) {
+    const size_t nInst = c->instances.size();
+    if(c->omPending) for(size_t i = 0; i < nInst && !omMotion; i++) omMotion = c->omMoved[i] && std::memcmp(c->omPrev[i].data(), c->instances[i].objectToWorld, 48) != 0;
+    if(omMotion && c->counting)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_render_frame: instances are in motion with object motion vectors on (rt_set_object_motion) and counting on (rt_set_counting): the counting build has no object-motion form");
+    if(omMotion) {
+      if(c->omTableRows < nInst) {
+        RT_HIP(c, syncAll(c));
+        if(c->omTable) { (void)hipFree(c->omTable); c->omTable = nullptr; c->omTableRows = 0; }
+        RT_HIP(c, hipMalloc(&c->omTable, nInst * sizeof(OmCamera)));
+        c->omTableRows = nInst;
+      }
+      c->omHost.resize(nInst);
+      for(size_t i = 0; i < nInst; i++) {
+        rt_scene_camera ci = cam;
+        if(c->omMoved[i]) (void)rt_object_motion_camera(&cam, c->omPrev[i].data(), c->instances[i].objectToWorld, &ci);
+        c->omHost[i].lastProjView = ci.lastProjView; c->omHost[i].lastPosition = ci.lastPosition; c->omHost[i].pad = 0.f;
+      }
+    }
+  }
   const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
@@ -1112,15 +1186,18 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if(c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) {
       void*& g = c->bufs[RT_BUF_GBUFFER0 + (frames & 1)]; void* t = g; g = c->spareG; c->spareG = c->spareG2; c->spareG2 = t;
       void*& m = c->bufs[RT_BUF_MOTION]; t = m; m = c->spareMotion; c->spareMotion = c->spareMotion2; c->spareMotion2 = t;
+      if(c->omInst) { t = c->omInst; c->omInst = c->omInstSpare; c->omInstSpare = c->omInstSpare2; c->omInstSpare2 = t; }
       std::swap(c->bufs[RT_BUF_DIRECT_RESULT0 + (frames & 1)], c->spareDirRes);
     } else {
       std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
       std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
+      if(c->omInst) std::swap(c->omInst, c->omInstSpare);
     }
   } else {
     RT_HIP(c, joinInFlight(c));
   }
   const DevFrame F = makeFrame(c, frames);
+  const DevObjMotion OM{static_cast<uint32_t*>(c->omInst), omMotion ? static_cast<const OmCamera*>(c->omTable) : nullptr, uint32_t(c->instances.size()), 0u};
   int k = 0, lastMain = 0, lastSide = 0, lastInd = 0;
   auto record = [&](hipStream_t strm, int stage) -> int {   // end-of-launch timestamp, timed against the previous one of the stream
     const hipError_t e = hipEventRecord(E.ev[k], strm);
@@ -1130,9 +1207,24 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     return RT_OK;
   };
   auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    hipError_t e = stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
+    hipError_t e = (om && (stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT)) ? omStageLauncher(c, *st, stage)(strm, c->ds, F, OM, *st, cam, stage, level, 0, 0)
+                                                                                     : stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
     if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     return record(strm, stage);
+  };
+  // the direct stage, after the per-instance camera table when instances are in motion: the copy is ordered before the direct stage on its stream, and the
+  // indirect stage follows the direct stage in every schedule (stream order, evD).  The table's previous reader is a frame before the last rt_update_instances,
+  // which drained the context.  The host rows (omHost, pageable) are rewritten only by such a frame too, and hipMemcpyAsync from pageable memory has staged
+  // them by the time it returns.  An update that no longer drains (event-ordered, DESIGN.md §20 "Not done") needs a table and pinned rows per frame in flight.
+  // Once the stage is issued the frame has been rendered as far as the motion state goes: every previous matrix becomes the current one.
+  auto direct = [&](hipStream_t strm) -> int {
+    if(om && omMotion) RT_HIP(c, hipMemcpyAsync(c->omTable, c->omHost.data(), c->omHost.size() * sizeof(OmCamera), hipMemcpyHostToDevice, strm));
+    const int r = run(strm, RT_STAGE_DIRECT, 0);
+    if(r == RT_OK) {
+      if(om) c->omInstValid = true;
+      if(c->omPending) { std::fill(c->omMoved.begin(), c->omMoved.end(), uint8_t(0)); c->omPending = false; }
+    }
+    return r;
   };
   // The SVGF history this frame reads is the one the previous SVGF frame wrote, if nothing invalidated it and that frame had the other parity.
   // The history of this frame's parity becomes valid once both chains are enqueued (svgfEnqueued); until then, and on every error return, it is not.
@@ -1229,7 +1321,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       RT_HIP(c, hipStreamWaitEvent(c->stream, c->evDone[(s - depth) & 3], 0));
     }
     RT_HIP(c, mark(c->stream, lastMain));
-    if((rc = run(c->stream, RT_STAGE_DIRECT, 0))) return rc;
+    if((rc = direct(c->stream))) return rc;
     RT_HIP(c, hipEventRecord(c->evD[r], c->stream));
 
     RT_HIP(c, hipStreamWaitEvent(c->indStream, c->evD[r], 0));
@@ -1258,7 +1350,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   // + its A-Trous chain only on the G-buffer, so the two chains run on two streams and join before compose: the direct
   // filter (ALU bound, full occupancy) fills the CUs that the indirect stage's long tail of multi-bounce tiles leaves idle.
   const bool fork = !decide && c->overlap && st->denoise > 0 && c->sideStream;
-  if((rc = run(c->stream, RT_STAGE_DIRECT, 0))) return rc;
+  if((rc = direct(c->stream))) return rc;
   if(fork) {
     RT_HIP(c, hipEventRecord(c->evFork, c->stream));
     RT_HIP(c, hipStreamWaitEvent(c->sideStream, c->evFork, 0));
@@ -1407,6 +1499,7 @@ int rt_rotate_buffers(rt_ctx* c, int frames)
   if(c->W == 0 || !c->spareG || !c->spareMotion) return fail(c, RT_ERR_NO_TARGET, "rt_rotate_buffers: rt_resize has not been called");
   std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
   std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
+  if(c->omInst) std::swap(c->omInst, c->omInstSpare);
   return RT_OK;
 }
 
@@ -1738,6 +1831,71 @@ int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases
   return RT_OK;
 }
 
+// ---- rt_set_object_motion: object motion vectors (the RT_OM builds of csrc/stages.hip; include/rt_abi.h "Object motion vectors")
+int rt_set_object_motion(rt_ctx* c, int mode)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(mode != RT_OBJECT_MOTION_OFF && mode != RT_OBJECT_MOTION_ON) return fail(c, RT_ERR_INVALID_ARG, "rt_set_object_motion: mode must be RT_OBJECT_MOTION_OFF or RT_OBJECT_MOTION_ON");
+  if(mode == c->objMotion) return RT_OK;
+  if(mode == RT_OBJECT_MOTION_ON && c->W > 0 && !c->omInst) {   // (a context that was resized before the mode was first switched on)
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    int rc;
+    if((rc = allocObjectMotion(c))) return rc;
+  }
+  c->objMotion = mode;
+  return RT_OK;
+}
+
+int rt_object_motion_readback(rt_ctx* c, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(!c->omInst || !c->omInstValid) return fail(c, RT_ERR_NO_TARGET, "rt_object_motion_readback: no frame has been rendered with object motion vectors on since the last rt_resize");
+  if(bytes != size_t(c->W) * c->H * sizeof(uint32_t)) return fail(c, RT_ERR_INVALID_ARG, "rt_object_motion_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, c->omInst, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectToWorld[12], const float curObjectToWorld[12], rt_scene_camera* out)
+{
+  if(!cam || !prevObjectToWorld || !curObjectToWorld || !out) return RT_ERR_INVALID_ARG;
+  rt_scene_camera r = *cam;
+  const float* P = prevObjectToWorld; const float* C = curObjectToWorld;
+  float Pi[12], Ci[12], detP = 0.f, detC = 0.f;
+  bool usable = std::memcmp(P, C, 12 * sizeof(float)) != 0;   // P == C bit for bit: the camera's own values, copied
+  if(usable) {
+    inverseAffine(P, Pi, &detP);
+    inverseAffine(C, Ci, &detC);
+    usable = detP != 0.0f && detC != 0.0f && std::isfinite(detP) && std::isfinite(detC);
+    for(int a = 0; a < 12 && usable; a++) usable = std::isfinite(P[a]) && std::isfinite(C[a]) && std::isfinite(Pi[a]) && std::isfinite(Ci[a]);
+  }
+  if(usable) {
+    // M = P · inverse(C), rows of 4 (the layout of rt_instance::objectToWorld); sums left to right, the translation last
+    float M[12];
+    for(int row = 0; row < 3; row++)
+      for(int col = 0; col < 4; col++) {
+        const float v = (P[4 * row] * Ci[col] + P[4 * row + 1] * Ci[4 + col]) + P[4 * row + 2] * Ci[8 + col];
+        M[4 * row + col] = col == 3 ? v + P[4 * row + 3] : v;
+      }
+    // lastProjView_i = lastProjView · M (column-major m[c * 4 + r]; M's fourth row is 0 0 0 1)
+    const float* L = cam->lastProjView.m;
+    for(int row = 0; row < 4; row++)
+      for(int col = 0; col < 4; col++) {
+        const float v = (L[row] * M[col] + L[4 + row] * M[4 + col]) + L[8 + row] * M[8 + col];
+        r.lastProjView.m[4 * col + row] = col == 3 ? v + L[12 + row] : v;
+      }
+    // lastPosition_i = C · (inverse(P) · lastPosition)
+    float q[3], w[3];
+    xformPointRaw(Pi, cam->lastPosition.x, cam->lastPosition.y, cam->lastPosition.z, q);
+    xformPointRaw(C, q[0], q[1], q[2], w);
+    r.lastPosition = rt_vec3{w[0], w[1], w[2]};
+  }
+  *out = r;
+  return RT_OK;
+}
+
 int rt_set_overlap(rt_ctx* c, int mode)
 {
   if(!c || mode < 0 || mode > 3) return RT_ERR_INVALID_ARG;
@@ -1910,8 +2068,13 @@ int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const fl
   rt_ctx::Refit& R = c->refit;
   const size_t words = (nInst + 31) / 32 + 1;
   std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
+  if(c->omPrev.size() != nInst) { c->omPrev.assign(nInst, std::array<float, 12>{}); c->omMoved.assign(nInst, 0); c->omPending = false; }
   for(uint32_t k = 0; k < count; k++) {
     const uint32_t i = ids[k];
+    if(!c->omMoved[i]) {   // the matrix of the last rendered frame, recorded once: a second update before the next frame keeps it
+      memcpy(c->omPrev[i].data(), c->instances[i].objectToWorld, sizeof(rows[k].o2w));
+      c->omMoved[i] = 1; c->omPending = true;
+    }
     memcpy(c->instances[i].objectToWorld, rows[k].o2w, sizeof(rows[k].o2w));
     R.inst[i] = rows[k];
     R.instMax[i] = instanceCoordMax(c, i, rows[k].o2w);

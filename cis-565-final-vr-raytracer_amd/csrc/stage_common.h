@@ -146,6 +146,29 @@ RT_DEV i2 createMotionIndex(const Ctx& c, f3 wpos)  // direct_stage.comp:125-139
   f2 s = mv * mk2(float(c.rtx.size.x), float(c.rtx.size.y));
   return i2{rt_ftoi(s.x), rt_ftoi(s.y)};
 }
+// ---- object motion vectors (the RT_OM builds of stages.hip) ----------------------------------------
+// A pixel that sees instance i takes lastProjView / lastPosition of its temporal lookup from row i of the table the host filled with rt_object_motion_camera;
+// without a table (no instance in motion this frame), and for an instance id outside it, the camera's own values.  The rows are read per lane (neighbouring
+// pixels see different instances), so they are vector loads from the global address space: 5 x global_load_dwordx4.
+RT_DEV i2 createMotionIndexOm(const Ctx& c, const DevObjMotion& OM, uint32_t inst, f3 wpos)   // createMotionIndex with the instance's lastProjView
+{
+  if(OM.cams == nullptr || inst >= OM.numInst) return createMotionIndex(c, wpos);
+  const float* row = OM.cams[inst].lastProjView.m;
+  rt_mat4 M;
+#pragma unroll
+  for(int k = 0; k < 4; k++) { const float4 v = gLoadF4(row + 4 * k); M.m[4 * k] = v.x; M.m[4 * k + 1] = v.y; M.m[4 * k + 2] = v.z; M.m[4 * k + 3] = v.w; }
+  f4 proj = mul(M, mk4(wpos, 1.0f));
+  f3 ndc = xyz(proj) / proj.w;
+  f2 mv = mk2(ndc.x, ndc.y) * 0.5f + 0.5f;
+  f2 s = mv * mk2(float(c.rtx.size.x), float(c.rtx.size.y));
+  return i2{rt_ftoi(s.x), rt_ftoi(s.y)};
+}
+RT_DEV f3 omLastPosition(const DevObjMotion& OM, const rt_scene_camera& cam, uint32_t inst)
+{
+  if(OM.cams == nullptr || inst >= OM.numInst) return mk3(cam.lastPosition);
+  const float4 v = gLoadF4(&OM.cams[inst].lastPosition);
+  return mk3(v.x, v.y, v.z);
+}
 // direct_stage.comp:47-84 == direct_reuse.comp:52-89
 RT_DEV bool findTemporalNeighborDirect(const DevFrame& F, const rt_state& st, f3 norm, float reprojDepth, uint32_t matId, i2 lastCoord,
                                        rt_direct_reservoir& resv, uint32_t& lid)

@@ -20,6 +20,17 @@ RT_DECL_LAUNCH(sky_cnt)
 RT_DECL_LAUNCH(base_lat)
 RT_DECL_LAUNCH(sky_lat)
 #undef RT_DECL_LAUNCH
+// the four object-motion builds (RT_OM, stages_*om.hip): RT_STAGE_DIRECT and RT_STAGE_INDIRECT only, no counting form
+#define RT_DECL_LAUNCH_OM(ns)                                                                                                                                  \
+  namespace ns {                                                                                                                                               \
+  hipError_t launchStage(hipStream_t stream, const DevScene& S, const DevFrame& F, const DevObjMotion& OM, const rt_state& st, const rt_scene_camera& cam,      \
+                         int stage, int level, int rowBegin, int rowEnd);                                                                                      \
+  }
+RT_DECL_LAUNCH_OM(base_om)
+RT_DECL_LAUNCH_OM(sky_om)
+RT_DECL_LAUNCH_OM(base_lat_om)
+RT_DECL_LAUNCH_OM(sky_lat_om)
+#undef RT_DECL_LAUNCH_OM
 // filters.hip, compiled once: every other stage (both A-Trous chains, compose; hipErrorInvalidValue for a level outside the chain or any other stage), and the
 // tile-order pass that every build of the indirect stage launches ahead of k_indirect_stage
 hipError_t launchFilterStage(hipStream_t stream, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int rowBegin, int rowEnd);

@@ -9,6 +9,7 @@
 // an XCD-aware tile order: consecutive workgroup ids land on different XCDs (observed b % 8), so XCD x gets the x-th
 // contiguous band of tile rows and its private 4 MiB L2 sees one compact screen region + the BVH subtrees under it.
 // This file is compiled six times: as is, and through stages_{sky,cnt,sky_cnt,lat,sky_lat}.hip with RT_SKY / RT_COUNT / RT_LAT set; what those switches do not reach is in filters.hip.
+// Four more builds, stages_{om,sky_om,lat_om,sky_lat_om}.hip, set RT_OM (below) for contexts with object motion vectors on.
 //   RT_SKY = 1    procedural sun & sky code paths compiled in.  Keeping sun_and_sky() out of the default kernels saves 13 VGPRs
 //                 in k_direct_stage — the procedural sky is the rarely used mode (default in_use = 0, sample_example.hpp:202).
 //   RT_COUNT = 1  traversal / shading counters (rt_set_counting) are flushed at the end of the traced kernels.  Without the
@@ -25,10 +26,40 @@
 #ifndef RT_LAT
 #define RT_LAT 0
 #endif
+//   RT_OM = 1     object motion vectors (rt_set_object_motion): k_direct_stage and k_indirect_stage take a DevObjMotion, store the primary hit's
+//                 instance per pixel and read lastProjView / lastPosition of the temporal lookup from the per-instance table instead of from the camera.  Every
+//                 expression stays what it is; k_direct_spatial (no temporal lookup) forwards to base / sky; no counting build, no direct_gen / direct_reuse.
+#ifndef RT_OM
+#define RT_OM 0
+#endif
+#if RT_OM && RT_COUNT
+#error "object motion vectors have no counting build"
+#endif
+#if RT_OM
+#define RT_OM_PARAM , const DevObjMotion& OM
+#define RT_OM_KPARAM , DevObjMotion OM
+#define RT_OM_ARG , OM
+#else
+#define RT_OM_PARAM
+#define RT_OM_KPARAM
+#define RT_OM_ARG
+#endif
 #if RT_LAT && RT_COUNT
 #error "the counting build exists for the throughput kernels only"
 #endif
-#if RT_LAT && RT_SKY
+#if RT_OM && RT_LAT && RT_SKY
+#define RT_VARIANT sky_lat_om
+#define RT_FORWARD sky
+#elif RT_OM && RT_LAT
+#define RT_VARIANT base_lat_om
+#define RT_FORWARD base
+#elif RT_OM && RT_SKY
+#define RT_VARIANT sky_om
+#define RT_FORWARD sky
+#elif RT_OM
+#define RT_VARIANT base_om
+#define RT_FORWARD base
+#elif RT_LAT && RT_SKY
 #define RT_VARIANT sky_lat
 #define RT_FORWARD sky
 #elif RT_LAT
@@ -68,26 +99,38 @@ struct DirectCont {
   State state; f3 wo, radiance; i2 motionIdx;
   rt_direct_reservoir resv; uint32_t lid;
   float pdf;     // kind 2: pdf of the single light sample (kept in resv.lightSample)
+#if RT_OM
+  uint32_t inst; // instance of the primary hit
+#endif
   int kind;      // 0: radiance is final (miss, emitter, debug view), 1: RIS reservoir, 2: single sample (ReSTIRState none)
 };
 RT_DEV float occlusionDist(const Ray& ray, f3 statePos, float dist)   // Occlusion, pathtrace.glsl:18-22
 {
   return ((dist - rt_abs(ray.origin.x - statePos.x)) - rt_abs(ray.origin.y - statePos.y)) - rt_abs(ray.origin.z - statePos.z);
 }
-RT_DEV bool directPre(Ctx& c, const DevFrame& F, const rt_state& st, i2 px, const Ray& r, DirectCont& K, Ray& shadowRay, float& shadowDist)
+RT_DEV bool directPre(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st, i2 px, const Ray& r, DirectCont& K, Ray& shadowRay, float& shadowDist)
 {
   const size_t index = size_t(px.y) * st.size.x + px.x;
   K.kind = 0; K.radiance = mk3(0.0f);
   if(c.hit.t >= RT_INFINITY) {  // :155-159
     F.thisG[index] = make_uint4(rt_f2u(RT_INFINITY), 0u, 0u, RT_INVALID_MAT_ID);
     storeMotion(F, px, i2{0, 0});
+#if RT_OM
+    OM.instImage[index] = 0xffffffffu;
+#endif
     K.radiance = c.EnvRadiance(r.direction);
     return false;
   }
   State& state = K.state;
   state = c.GetState(r.direction);
   c.GetMaterials(state, r);
+#if RT_OM
+  K.inst = gLoadU32(&c.S.triRef[c.hit.gid].inst);
+  OM.instImage[index] = K.inst;
+  K.motionIdx = createMotionIndexOm(c, OM, K.inst, state.position);
+#else
   K.motionIdx = createMotionIndex(c, state.position);
+#endif
   const uint4 gInfo = encodeGeometryInfo(state, c.hit.t);
   storeMotion(F, px, K.motionIdx);
   F.thisG[index] = gInfo;
@@ -110,7 +153,7 @@ RT_DEV bool directPre(Ctx& c, const DevFrame& F, const rt_state& st, i2 px, cons
   K.kind = 1;
   return risCandidatesNoVisibility(c, state, K.wo, K.resv, K.lid, shadowRay, shadowDist);
 }
-RT_DEV void directPost(Ctx& c, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, i2 px, DirectCont& K, bool occluded)
+RT_DEV void directPost(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, i2 px, DirectCont& K, bool occluded)
 {
   const size_t index = size_t(px.y) * st.size.x + px.x;
   const bool spatial = st.ReSTIRState == RT_RESTIR_SPATIAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
@@ -129,7 +172,11 @@ RT_DEV void directPost(Ctx& c, const DevFrame& F, const rt_state& st, const rt_s
       uint32_t lid = K.lid;
       if(occluded) resv.weight = 0.0f;
       if(st.ReSTIRState == RT_RESTIR_TEMPORAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL) {
+#if RT_OM
+        const float reprojDepth = length(omLastPosition(OM, cam, K.inst) - state.position);
+#else
         const float reprojDepth = length(mk3(cam.lastPosition) - state.position);
+#endif
         rt_direct_reservoir temporal; uint32_t tlid = 0xffffffffu;
         if(findTemporalNeighborDirect(F, st, state.normal, reprojDepth, state.matID, K.motionIdx, temporal, tlid)) {
           if(!resvInvalidW(temporal.weight)) { if(resvMerge(resv, temporal, rnd(c.seed))) lid = tlid; }
@@ -207,7 +254,7 @@ RT_DEV void groupTrace(const DevScene& S, const WideLds& L, TravCounters& tc)
 #ifndef RT_LAT_DIRECT_WAVES
 #define RT_LAT_DIRECT_WAVES 4   // 128 VGPRs: two workgroups per CU (151 VGPRs and one workgroup at 2: 15-30 % slower on every band, scripts/variants_ab.sh with -DRT_LAT_DIRECT_WAVES=2)
 #endif
-__global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevScene S, DevFrame F, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
+__global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevScene S, DevFrame F RT_OM_KPARAM, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
 {
   extern __shared__ uint2 s_stack[];
   const TileCoord tile = tileOf(tilesX, tilesY);
@@ -243,7 +290,7 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
   bool wantShadow = false;
   if(mine) {
     c.hit = poolGet(L.pool, lane * 2);
-    wantShadow = directPre(c, F, st, px, r, K, shadowRay, shadowDist);
+    wantShadow = directPre(c, F RT_OM_ARG, st, px, r, K, shadowRay, shadowDist);
     if(wantShadow) { c.nAny++; poolPut(L.pool, lane * 2 + 1, shadowRay.origin, shadowRay.direction, shadowDist, c.seed); }
   }
   if(wave == 0) poolPublish(L, false, wantShadow);
@@ -254,7 +301,7 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
 #if RT_WAVEPROF
   p4 = clock64();
 #endif
-  if(mine) directPost(c, F, st, cam, px, K, wantShadow && poolGet(L.pool, lane * 2 + 1).gid != 0xffffffffu);
+  if(mine) directPost(c, F RT_OM_ARG, st, cam, px, K, wantShadow && poolGet(L.pool, lane * 2 + 1).gid != 0xffffffffu);
 #if RT_WAVEPROF
   {  // record: 0 x | 1 y | 2 workgroup cycles | 3 primary trace | 4 shadow trace | 5 node-only rounds (max over waves) | 6 rounds with triangles | 7 raygen | 8 cyc node rounds | 9 cyc tri rounds | 10 pre | 11 post | 15 ticks
     uint32_t* rec = F.waveProf + size_t(blockIdx.x) * 16;
@@ -274,7 +321,7 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
 #endif
 }
 #else
-__global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, DevFrame F, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
+__global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, DevFrame F RT_OM_KPARAM, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
 {
   extern __shared__ uint2 s_stack[];
 #if RT_WAVEPROF
@@ -294,9 +341,9 @@ __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, D
   DirectCont K;
   Ray shadowRay{mk3(0.0f), mk3(0.0f)};
   float shadowDist = 0.0f;
-  const bool wantShadow = directPre(c, F, st, px, r, K, shadowRay, shadowDist);
+  const bool wantShadow = directPre(c, F RT_OM_ARG, st, px, r, K, shadowRay, shadowDist);
   const bool occluded = wantShadow && c.AnyHit(shadowRay, shadowDist);
-  directPost(c, F, st, cam, px, K, occluded);
+  directPost(c, F RT_OM_ARG, st, cam, px, K, occluded);
   flushCounters(F, c);
 #if RT_WAVEPROF
   waveProfFlush(F, c, tile.x, tile.y, prof_c0, prof_w0);
@@ -304,7 +351,7 @@ __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, D
 }
 #endif
 
-#if !RT_LAT   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency form)
+#if !RT_LAT && !RT_OM   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency or an object-motion form)
 // Second half of direct_stage.comp's ReSTIRDirect for the spatial modes (:86-121, 236-262): two rounds of five neighbour
 // merges from the cached reservoirs, the final merge and the shading.  No rays.
 // The 10 x 10 block of cached reservoirs around the 8 x 8 tile (every neighbour lies within one pixel) is staged in LDS once and the
@@ -457,14 +504,14 @@ __global__ __launch_bounds__(64) void k_direct_reuse(DevScene S, DevFrame F, rt_
   storeImg(F.thisDirectResult, F, px, mk4(HDRToLDR(c.clampRadiance(direct)), 1.0f));
 }
 
-#endif  // !RT_LAT
+#endif  // !RT_LAT && !RT_OM
 
 // ------------------------------------------------------------------------------------------------------------
 // indirect_stage.comp
 // ------------------------------------------------------------------------------------------------------------
 // ReSTIRIndirect, indirect_stage.comp:228-268 (+ findTemporalNeighbor :74-108): temporal lookup, reservoir update, shading
 // of the half-resolution pixel.  Shared by the generic indirect kernel body and the multi-tile single-bounce body.
-RT_DEV void restirIndirectFinish(Ctx& c, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, i2 px, i2 indSize, const GState& primState, f3 primWo,
+RT_DEV void restirIndirectFinish(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, i2 px, i2 indSize, const GState& primState, f3 primWo,
                                  rt_gi_sample gi, float primSamplePdf)
 {
   f3 indirect = mk3(0.0f);
@@ -473,7 +520,11 @@ RT_DEV void restirIndirectFinish(Ctx& c, const DevFrame& F, const rt_state& st, 
   resv.giSample.xs = rt_vec3{0, 0, 0}; resv.giSample.ns = rt_vec3{0, 0, 0}; resv.giSample.pHat = 0.f;
   resv.num = 0; resv.weight = 0.f; resv.bigW = 0.f;
   if(st.ReSTIRState == RT_RESTIR_TEMPORAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL) {
+#if RT_OM
+    const float reprojDepth = length(omLastPosition(OM, cam, OM.instImage[size_t(px.y * 2) * F.W + px.x * 2]) - primState.position);
+#else
     const float reprojDepth = length(mk3(cam.lastPosition) - primState.position);
+#endif
     const i2 motionIdx = loadMotion(F, i2{px.x * 2, px.y * 2});
     if(motionIdx.x >= 0 && motionIdx.x < F.W && motionIdx.y >= 0 && motionIdx.y < F.H && (motionIdx.y < F.histRow0 || motionIdx.y >= F.histRow1)) *F.histMiss = 1u;
     const uint4 lg = loadG(F.lastG, F, motionIdx);
@@ -524,7 +575,7 @@ RT_DEV void restirIndirectFinish(Ctx& c, const DevFrame& F, const rt_state& st, 
 // hit point, normal, pending NEE term), so K paths per lane stay in registers, both traces run over a pool of up to 64 K
 // rays, and lanes pull rays until the pool is dry.  Same arithmetic, same RNG draw order per path as the generic body.
 template <int K>
-RT_DEV void indirectSingleBounceTiles(const DevScene& S, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int rowBegin, int rowEnd, int tilesX,
+RT_DEV void indirectSingleBounceTiles(const DevScene& S, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, int rowBegin, int rowEnd, int tilesX,
                                       const uint32_t* tiles /* K entries */, int nTilesHere, uint2* s_stack)
 {
   const int lane = int(threadIdx.x);
@@ -626,7 +677,7 @@ RT_DEV void indirectSingleBounceTiles(const DevScene& S, const DevFrame& F, cons
     if(p.shadow && poolGet(pool, k * 64 + lane).gid == 0xffffffffu) gi.L = toR(mk3(gi.L) + p.pend);  // not occluded
     c.seed = p.seed;
     c.imageCoords = p.px;
-    restirIndirectFinish(c, F, st, cam, p.px, indSize, primState, -ray0.direction, gi, p.primSamplePdf);
+    restirIndirectFinish(c, F RT_OM_ARG, st, cam, p.px, indSize, primState, -ray0.direction, gi, p.primSamplePdf);
   }
 #if RT_WAVEPROF
   // (round 5: the K-tile waves were missing from the profile — 75 % of the stage's tiles; their record is keyed by the first tile, bit 17 marks the kind)
@@ -647,10 +698,10 @@ RT_DEV void indirectSingleBounceTiles(const DevScene& S, const DevFrame& F, cons
 // workgroup's ray pool: after every path vertex wave 0 lists the vertex's rays, all waves trace them eight lanes per ray, wave 0 goes on shading
 // (4 waves per SIMD = 128 VGPRs: two of these workgroups per CU, and beside one of them two direct-stage waves per SIMD — with 165 registers the next
 //  frame's direct stage, which runs beside this kernel when frames are in flight, had one wave slot per SIMD left: profiles/r03_mgpu_period_ab.txt)
-__global__ __launch_bounds__(512, 4) void k_indirect_stage(DevScene S, DevFrame F, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY, int cap,
+__global__ __launch_bounds__(512, 4) void k_indirect_stage(DevScene S, DevFrame F RT_OM_KPARAM, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY, int cap,
                                                        const uint32_t* lists, uint32_t* counts, int subShift, int sbK, int genericBlocks)
 #else
-__global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene S, DevFrame F, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY, int cap,
+__global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene S, DevFrame F RT_OM_KPARAM, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY, int cap,
                                                           const uint32_t* lists, uint32_t* counts, int subShift, int sbK, int genericBlocks)
 #endif
 {
@@ -674,8 +725,8 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
       uint32_t t[3] = {0u, 0u, 0u};
       const int n = min(sbK, nb - first);
       for(int k = 0; k < n; k++) t[k] = lists[size_t(xcd) * cap + (cap - 1 - (first + k))];
-      if(sbK == 3) indirectSingleBounceTiles<3>(S, F, st, cam, rowBegin, rowEnd, tilesX, t, n, s_stack);
-      else indirectSingleBounceTiles<2>(S, F, st, cam, rowBegin, rowEnd, tilesX, t, n, s_stack);  // (4 per wave was measured: slower, spills)
+      if(sbK == 3) indirectSingleBounceTiles<3>(S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, t, n, s_stack);
+      else indirectSingleBounceTiles<2>(S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, t, n, s_stack);  // (4 per wave was measured: slower, spills)
       return;
     }
 #endif
@@ -838,14 +889,14 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
 #endif
   if(!hasSurface) { flushCounters(F, c); return; }
 
-  restirIndirectFinish(c, F, st, cam, px, indSize, primState, primWo, gi, primSamplePdf);
+  restirIndirectFinish(c, F RT_OM_ARG, st, cam, px, indSize, primState, primWo, gi, primSamplePdf);
   flushCounters(F, c);
 }
 
 // ------------------------------------------------------------------------------------------------------------
 // host-side launch (one entry of Renderer::run's dispatch list, renderer.cpp:163-205)
 // ------------------------------------------------------------------------------------------------------------
-hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
+hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
                        int rowBegin, int rowEnd)
 {
   DevScene S = Sin;
@@ -875,12 +926,16 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
       // (row-tiled multi-GPU frames with spatial reuse): 0 = the whole stage, 1 = k_direct_stage only, 2 = k_direct_spatial only
       if(level < 0 || level > 2 || (level != 0 && !spatial)) return hipErrorInvalidValue;
 #if RT_LAT
-      if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, dim3(64 * nWaves), wideLdsBytes(S.stackEntries, nWaves), stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+      if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, dim3(64 * nWaves), wideLdsBytes(S.stackEntries, nWaves), stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY);
       if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
 #else
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
-      if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, block, lds, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+      if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, block, lds, stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+#if RT_OM
+      if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
+#else
       if(level != 1 && spatial) hipLaunchKernelGGL(k_direct_spatial, grid, block, 0, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+#endif
 #endif
       break;
     case RT_STAGE_INDIRECT: {
@@ -889,7 +944,7 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
       (void)launchIndTileOrder(stream, st, rowBegin, tilesX, tilesY, cap, F.tileOrder, F.qcount + 192);   // filters.hip: longest tiles first
 #if RT_LAT
       // one workgroup per tile, multi-bounce tiles first (same lists)
-      hipLaunchKernelGGL(k_indirect_stage, grid, dim3(64 * nWaves), wideLdsBytes(S.stackEntries, nWaves), stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY, cap,
+      hipLaunchKernelGGL(k_indirect_stage, grid, dim3(64 * nWaves), wideLdsBytes(S.stackEntries, nWaves), stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY, cap,
                          (const uint32_t*)F.tileOrder, F.qcount + 192, 0, 0, int(grid.x));
 #else
       // under ~2 waves per SIMD (1024 SIMDs) the launch is latency bound: split tiles over more waves
@@ -903,12 +958,12 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
       const unsigned sbBlocks = sbK > 0 ? 8u * unsigned((cap + sbK - 1) / sbK) : 0u;
       const size_t poolBytes = std::max<size_t>(POOL_BYTES, size_t(sbK) * 64 * 33);
       if(needOvf && (genericBlocks + sbBlocks) * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;
-      hipLaunchKernelGGL(k_indirect_stage, dim3(genericBlocks + sbBlocks), block, lds + poolBytes, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY, cap,
+      hipLaunchKernelGGL(k_indirect_stage, dim3(genericBlocks + sbBlocks), block, lds + poolBytes, stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY, cap,
                          (const uint32_t*)F.tileOrder, F.qcount + 192, subShift, sbK, int(genericBlocks));
 #endif
       break;
     }
-#if !RT_LAT   // the two stages the reference compiles but does not dispatch: throughput builds only
+#if !RT_LAT && !RT_OM   // the two stages the reference compiles but does not dispatch: throughput builds only
     case RT_STAGE_DIRECT_GEN:
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
       hipLaunchKernelGGL(k_direct_gen, grid, block, lds, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);

@@ -62,6 +62,12 @@ class Renderer {
     return true;
   }
   void destroy() { if(m_ctx) rt_destroy(m_ctx); m_ctx = nullptr; }  // renderer.cpp:75-91
+  // Object motion vectors (include/rt_abi.h "Object motion vectors"): temporal reuse follows moved instances; off by default
+  bool setObjectMotion(bool on)
+  {
+    if(rt_set_object_motion(m_ctx, on ? RT_OBJECT_MOTION_ON : RT_OBJECT_MOTION_OFF) != RT_OK) { fprintf(stderr, "Renderer::setObjectMotion: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
   // renderer.cpp:97-148: screen-space buffers for `size` (the reference also creates 7 pipelines + descriptor sets here)
   bool create(int width, int height, Scene* scene) { (void)scene; return update(width, height); }
   // renderer.cpp:154-206: the 12 dispatches of one frame

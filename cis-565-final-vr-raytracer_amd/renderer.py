@@ -22,6 +22,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
+               "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -123,6 +124,10 @@ def hip_lib():
         if hasattr(L, "rt_rebuild_accel"):   # rebuilding on the device (absent from older A/B libraries)
             L.rt_rebuild_accel.argtypes = [C.c_void_p]
             L.rt_get_rebuild_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_object_motion"):   # object motion vectors (absent from older A/B libraries)
+            L.rt_set_object_motion.argtypes = [C.c_void_p, C.c_int]
+            L.rt_object_motion_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_object_motion_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -440,6 +445,29 @@ class Renderer:
         s = abi.RebuildStats()
         self._chk(hip_lib().rt_get_rebuild_stats(self._h, C.byref(s)), "rt_get_rebuild_stats")
         return s
+
+    # ---- object motion vectors (include/rt_abi.h "Object motion vectors")
+    def set_object_motion(self, mode):
+        """rt_set_object_motion: abi.OBJECT_MOTION_OFF (default) / OBJECT_MOTION_ON"""
+        self._chk(hip_lib().rt_set_object_motion(self._h, int(mode)), "rt_set_object_motion")
+
+    def object_motion_readback(self):
+        """the instance image of the last frame rendered with the mode on: (H, W) uint32, 0xffffffff where the primary ray missed"""
+        nbytes = self.buffer_bytes(abi.BUF_MOTION)   # 4 B per full-resolution pixel
+        out = np.empty(nbytes // 4, dtype=np.uint32)
+        self._chk(hip_lib().rt_object_motion_readback(self._h, out.ctypes.data, out.nbytes), "rt_object_motion_readback")
+        return out
+
+    @staticmethod
+    def object_motion_camera(cam, prev, cur):
+        """rt_object_motion_camera (no context, no GPU): the per-instance previous camera for an instance that moved from objectToWorld `prev` to `cur` (12 floats each)"""
+        p = np.ascontiguousarray(prev, dtype=np.float32).reshape(12)
+        c = np.ascontiguousarray(cur, dtype=np.float32).reshape(12)
+        out = abi.SceneCamera()
+        rc = hip_lib().rt_object_motion_camera(C.byref(cam), p.ctypes.data, c.ctypes.data, C.byref(out))
+        if rc != 0:
+            raise RtError(f"rt_object_motion_camera failed ({rc})")
+        return out
 
     def accel_readback(self, which, num_instances=None):
         """the device tree as raw bytes: abi.ACCEL_NODES (80 B per node), ACCEL_TRIS (64 B per leaf record), ACCEL_INSTANCES (112 B per instance; pass num_instances)"""

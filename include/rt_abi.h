@@ -750,11 +750,53 @@ typedef struct {
 } rt_rebuild_stats;       /* 32 B */
 int rt_rebuild_accel(rt_ctx* ctx);                       /* LBVH -> BVH8 on the GPU from the context's current scene */
 int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Object motion vectors (added within ABI 2.4, no version bump; the RT_OM builds of csrc/stages.hip).  rt_update_instances moves a surface, but the
+ * reference's temporal lookup reprojects a hit with the camera's lastProjView and measures reprojDepth from the camera's lastPosition only, so on a moved surface
+ * it lands on whatever was at that world position one frame earlier: the history is rejected (the prop stays noisy) or, on a large one-material object, taken
+ * from the wrong surface point.  With the mode on, for a pixel that sees instance i the frame behaves as if the previous camera had been a per-instance camera:
+ *   P = the instance's objectToWorld when the previous frame was rendered, C = its current one, M = P · inverse(C) (a current world point -> where that material
+ *   point was); lastProjView_i = lastProjView · M; lastPosition_i = C · (inverse(P) · lastPosition), so that |lastPosition_i - x| = |lastPosition - M x| for rigid motion.
+ * Every kernel expression stays what it is; createMotionIndex reads lastProjView_i, and reprojDepth of the direct and the indirect temporal lookup lastPosition_i.
+ * The normal test, the material hash, the column 0-1 exclusion and every quirk of DESIGN.md §6 are untouched — so a rotation of more than acos(0.9) = 25.8 degrees
+ * per frame (indirect: acos(0.5)) rejects the history, and a reused reservoir's light sample / GI sample points are one frame stale (ReSTIR's own lag).
+ *
+ * rt_object_motion_camera(cam, prev, cur, out): pure function, no context, callable without a GPU.  out = *cam with lastProjView and lastPosition replaced.
+ *   fp32, no contraction (include/rt_detmath.h), this order: Pi = inverseAffine(prev), Ci = inverseAffine(cur) (the BVH builder's expression);
+ *   M[r][c] = (P[r][0] Ci[0][c] + P[r][1] Ci[1][c]) + P[r][2] Ci[2][c], and for c = 3 then + P[r][3];
+ *   lastProjView_i[r][c] = (L[r][0] M[0][c] + L[r][1] M[1][c]) + L[r][2] M[2][c], and for c = 3 then + L[r][3]   (L = cam->lastProjView; M's fourth row is 0 0 0 1);
+ *   q = (Pi[r][0] x + Pi[r][1] y + Pi[r][2] z) + Pi[r][3] of lastPosition, lastPosition_i = the same expression with cur applied to q.
+ *   prev == cur bit for bit returns *cam bit for bit (copied, not computed); so does a prev or cur that is not finite, or whose determinant is zero or not
+ *   finite, or whose inverse is not finite.  RT_ERR_INVALID_ARG only for a NULL pointer.
+ * rt_set_object_motion(ctx, mode): RT_OBJECT_MOTION_OFF (default) / _ON.  A call that changes nothing does nothing; a change invalidates no history and does
+ *   not re-open the stream-priority decision.  The context keeps, per instance, the objectToWorld of the last frame rt_render_frame rendered (whether the mode is
+ *   on or off): rt_update_instances records it once, so several updates between two frames keep the rendered frame's matrix; issuing a frame's direct stage makes
+ *   every previous matrix the current one.  rt_build_accel and rt_rebuild_accel keep this state; rt_upload_scene and rt_resize clear it.  An instance is IN
+ *   MOTION for a frame when its two matrices differ in any bit.
+ *   Frames (rt_render_frame) with the mode on run the direct and the indirect stage from the object-motion builds, which store the instance image (below).  When
+ *   at least one instance is in motion, the table {lastProjView_i, lastPosition_i} of all instances (rt_object_motion_camera per moved instance, the camera's
+ *   values copied for the others; 80 B per instance) is uploaded on the direct stage's stream ahead of it; when none is, no table exists and every pixel reads the
+ *   camera's values, so the frame equals the mode-off frame word for word — as do the pixels of a static instance in any frame.
+ *   There is no counting form of these builds: with rt_set_counting on, a frame with an instance in motion is RT_ERR_INVALID_ARG (the message names the
+ *   combination), and a frame with none runs the counting kernels, which do not write the instance image.
+ *   rt_run_stage (and so restir_amd/tiled.py) and rt_mgpu_* contexts ignore the mode in this version: they run the default kernels with the camera's values and do
+ *   not advance the motion state.  The SVGF and TAA passes are unchanged: SVGF reads RT_BUF_MOTION, so it reprojects to the object-motion position and keeps its
+ *   camera-only depth test (it may reject, it cannot accept a wrong surface); TAA reprojects from its own camera.
+ * rt_object_motion_readback(ctx, dst, bytes): the instance image of the last frame rendered with the mode on (in motion or not; counting frames excepted):
+ *   uint32 per full-resolution pixel (W * H * 4 B, `bytes` must be exact, else RT_ERR_INVALID_ARG), the index of the instance the primary ray hit, 0xffffffff
+ *   where it missed.  RT_ERR_NO_TARGET before the first such frame since rt_resize.  Synchronous.  The image has the lifetime of RT_BUF_MOTION (written by the
+ *   direct stage, read by the indirect stage of the same frame at 2p) and is rotated with it by the frames-in-flight schedules and rt_rotate_buffers; it is
+ *   allocated by rt_resize once the mode has been switched on (or by the call that first switches it on).
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_OBJECT_MOTION_OFF = 0 /* default */, RT_OBJECT_MOTION_ON = 1 };
+int rt_set_object_motion(rt_ctx* ctx, int mode);
+int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectToWorld[12], const float curObjectToWorld[12], rt_scene_camera* out);
+int rt_object_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + moving instances (rt_update_instances, rt_update_lights, rt_get_refit_stats, rt_accel_readback; additions that change no existing call, so the version stays 2.4 like the three opt-in passes before them), + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
+/* ABI version: (major<<16)|minor.  2.4: + object motion vectors (rt_set_object_motion, rt_object_motion_camera, rt_object_motion_readback; additions), + moving instances (rt_update_instances, rt_update_lights, rt_get_refit_stats, rt_accel_readback; additions that change no existing call, so the version stays 2.4 like the three opt-in passes before them), + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
  * (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; opt-in additions that change no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
