@@ -1,5 +1,6 @@
 """ctypes mirrors of include/rt_abi.h (the data contract of shaders/host_device.h:153-333)."""
 import ctypes as C
+import numpy as np
 
 class Vec2(C.Structure): _fields_ = [("x", C.c_float), ("y", C.c_float)]
 class Vec3(C.Structure): _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
@@ -140,6 +141,17 @@ OBJECT_MOTION_OFF, OBJECT_MOTION_ON = range(2)   # rt_set_object_motion
 class RebuildStats(C.Structure):  # rt_rebuild_stats, 32 B
     _fields_ = [("triangles", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("maxDepth", C.c_uint32), ("ms", C.c_float), ("sortMs", C.c_float),
                 ("triPad", C.c_float), ("reserved", C.c_uint32)]
+
+
+class DeformStats(C.Structure):  # rt_deform_stats, 32 B
+    _fields_ = [("meshes", C.c_uint32), ("vertices", C.c_uint32), ("instances", C.c_uint32), ("vertexBytesCopied", C.c_uint32), ("skinMs", C.c_float), ("ms", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+# rt_skin (16 B) and rt_skin_influence (24 B) as numpy rows; rt_vertex (32 B)
+SKIN_DT = np.dtype([("primMesh", "<u4"), ("firstJoint", "<u4"), ("jointCount", "<u4"), ("firstInfluence", "<u4")])
+SKIN_INFLUENCE_DT = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
+VERTEX_DT = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("texcoord", "<f4", 2), ("tangent", "<u4"), ("color", "<u4")])
 
 
 class RefitStats(C.Structure):  # rt_refit_stats, 32 B

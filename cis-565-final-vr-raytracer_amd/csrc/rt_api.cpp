@@ -26,6 +26,7 @@
 #include "taa.h"
 #include "refit.h"
 #include "accel_build.h"
+#include "deform.h"
 #include "dev_math.h"
 
 using namespace rt;
@@ -142,6 +143,21 @@ struct rt_ctx {
   } rebuild;
   std::vector<void*> rebuildAllocs;
   hipEvent_t evRebuild[4] = {nullptr, nullptr, nullptr, nullptr};   // start, sort begin, sort end, end
+  // rt_update_vertices / rt_set_skins / rt_update_skins (csrc/deform.hip).  The skins' device buffers (rest pose, staging range, influences, the
+  // per-call job and matrix tables) live in skinAllocs: replaced by rt_set_skins, dropped by rt_upload_scene.  The per-instance job table and the result words of
+  // k_inst_coord_max live in deformAllocs, made by the first deforming call after an upload.  `stale[k]`: the device rows of skin k's mesh are newer than c->vertices.
+  struct Deform {
+    std::vector<rt_skin> skins;
+    std::vector<uint32_t> restFirst;             // per skin: first row of its mesh in dRest / dStaged
+    std::vector<int32_t> skinOfMesh;             // per prim mesh: its skin, or -1 (empty: no skins)
+    std::vector<uint8_t> stale;
+    rt_vertex* dRest = nullptr; rt_vertex* dStaged = nullptr; rt_skin_influence* dInfluences = nullptr;
+    float* dJoints = nullptr; SkinJob* dSkinJobs = nullptr;
+    CoordJob* dCoordJobs = nullptr; uint32_t* dOut = nullptr;   // dOut[0]: non-finite staged positions; dOut[1 + j]: coordinate maximum of job j
+    rt_deform_stats stats{};
+  } deform;
+  std::vector<void*> skinAllocs, deformAllocs;
+  hipEvent_t evDeform[2] = {nullptr, nullptr};   // start / end of the skinning kernel and its commit copy
   // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
   // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
   int objMotion = RT_OBJECT_MOTION_OFF;
@@ -394,6 +410,7 @@ struct LoadTimer {
   void lap(const char* what) { if(!on) return; const auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[scene load] %-34s %.3f s\n", what, std::chrono::duration<double>(n - t).count()); t = n; }
 };
 static int ensureStackOverflow(rt_ctx* c);
+static int syncHostVertices(rt_ctx* c, int mesh = -1);
 static int allocObjectMotion(rt_ctx* c);
 static void reopenPriorityDecision(rt_ctx* c);
 static void hashBytes(const void* p, size_t n, uint64_t& h0, uint64_t& h1);
@@ -474,6 +491,7 @@ int rt_destroy(rt_ctx* c)
   (void)hipSetDevice(c->device);
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
+  freePool(c->skinAllocs); freePool(c->deformAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
@@ -496,6 +514,7 @@ int rt_destroy(rt_ctx* c)
   if(c->evFork) (void)hipEventDestroy(c->evFork);
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
   for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evDeform) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
@@ -557,6 +576,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   RT_HIP(c, syncAll(c));
   LoadTimer lt;
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->rebuildAllocs);
+  freePool(c->skinAllocs); freePool(c->deformAllocs);   // a new scene has no skins
+  c->deform = rt_ctx::Deform{};
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
   c->haveScene = c->haveAccel = false;
@@ -751,6 +772,7 @@ int rt_build_accel(rt_ctx* c)
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_build_accel: no scene uploaded");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
+  { const int rc = syncHostVertices(c); if(rc) return rc; }   // the build and its cache key read the context's copy: skinned meshes are current on the device only
   freePool(c->accelAllocs); freePool(c->rebuildAllocs);
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
@@ -2011,6 +2033,7 @@ static int ensureRefitState(rt_ctx* c)
     first += count; count = next;
   }
   if(size_t(first) != nNodes) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: the tree's levels are not contiguous node ranges");
+  { const int rc = syncHostVertices(c); if(rc) return rc; }
   R.instMax.resize(nInst);
   for(uint32_t i = 0; i < nInst; i++) R.instMax[i] = instanceCoordMax(c, i, c->instances[i].objectToWorld);
   const size_t words = (nInst + 31) / 32 + 1;
@@ -2066,6 +2089,7 @@ int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const fl
   int rc;
   if((rc = ensureRefitState(c))) return rc;
   rt_ctx::Refit& R = c->refit;
+  for(uint32_t k = 0; k < count; k++) if((rc = syncHostVertices(c, int(c->instances[ids[k]].primMesh)))) return rc;   // instanceCoordMax reads the context's copy
   const size_t words = (nInst + 31) / 32 + 1;
   std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
   if(c->omPrev.size() != nInst) { c->omPrev.assign(nInst, std::array<float, 12>{}); c->omMoved.assign(nInst, 0); c->omPending = false; }
@@ -2266,6 +2290,288 @@ int rt_accel_readback(rt_ctx* c, int which, void* dst, size_t bytes)
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   if(want) RT_HIP(c, hipMemcpy(dst, src, want, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+/* ---- deforming meshes: vertex updates and GPU skinning + the refit of rt_update_instances (include/rt_abi.h "Deforming meshes", csrc/deform.hip) ---- */
+}  // extern "C"
+
+// the context's copy of the vertices of skinned meshes is refreshed here, at the top of what reads it, not by rt_update_skins (mesh < 0: every stale mesh)
+static int syncHostVertices(rt_ctx* c, int mesh)
+{
+  rt_ctx::Deform& D = c->deform;
+  for(size_t k = 0; k < D.skins.size(); k++) {
+    if(!D.stale[k] || (mesh >= 0 && uint32_t(mesh) != D.skins[k].primMesh)) continue;
+    const rt_prim_mesh& pm = c->primMeshes[D.skins[k].primMesh];
+    if(pm.vertexCount) RT_HIP(c, hipMemcpy(c->vertices.data() + pm.vertexOffset, c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToHost));
+    D.stale[k] = 0;
+  }
+  return RT_OK;
+}
+
+static int ensureDeformBuffers(rt_ctx* c)
+{
+  rt_ctx::Deform& D = c->deform;
+  if(D.dOut) return RT_OK;
+  const size_t nInst = c->instances.size();
+  int rc;
+  const CoordJob* cj = nullptr; const uint32_t* out = nullptr;
+  if((rc = upload<CoordJob>(c, c->deformAllocs, nullptr, std::max<size_t>(nInst, 1), &cj))) return rc;
+  if((rc = upload<uint32_t>(c, c->deformAllocs, nullptr, nInst + 1, &out))) return rc;
+  D.dCoordJobs = const_cast<CoordJob*>(cj); D.dOut = const_cast<uint32_t*>(out);
+  for(hipEvent_t& e : c->evDeform) if(!e) RT_HIP(c, hipEventCreate(&e));
+  return RT_OK;
+}
+
+// What rt_update_vertices and rt_update_skins share.  `meshes`: the deformed prim meshes.  skinJobs != nullptr: the pose is in the staging range (k_skin has been
+// enqueued after evRefit[0] / evDeform[0]); it is committed to the live array only when no staged position is non-finite, else the call is refused with nothing changed.
+// Then, as rt_update_instances: dirty and flip bits of every instance of those meshes, their coordinate maxima (k_inst_coord_max), the pads, the refit, the stats.
+static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& meshes, const std::vector<SkinJob>* skinJobs, const std::vector<uint32_t>* skinIds,
+                       uint32_t verticesWritten, uint32_t bytesCopied)
+{
+  rt_ctx::Refit& R = c->refit;
+  rt_ctx::Deform& D = c->deform;
+  const size_t nInst = c->instances.size();
+  hipStream_t s = c->stream;
+  std::vector<uint8_t> deformed(c->primMeshes.size(), 0);
+  for(uint32_t m : meshes) deformed[m] = 1;
+  std::vector<CoordJob> jobs;
+  uint32_t threads = 0;
+  for(uint32_t i = 0; i < nInst; i++) {
+    const uint32_t m = c->instances[i].primMesh;
+    if(!deformed[m]) continue;
+    const rt_prim_mesh& pm = c->primMeshes[m];
+    CoordJob j{};
+    j.threadBase = threads; j.indexCount = pm.indexCount; j.firstIndex = pm.firstIndex; j.instance = i;
+    j.vertexBase = skinJobs ? D.restFirst[size_t(D.skinOfMesh[m])] : pm.vertexOffset;
+    jobs.push_back(j);
+    threads += (pm.indexCount + 63u) & ~63u;
+  }
+  std::vector<uint32_t> out(jobs.size() + 1, 0u);
+  if(!skinJobs) RT_HIP(c, hipMemsetAsync(D.dOut, 0, 4, s));   // (the skin path cleared the counter ahead of k_skin)
+  if(!jobs.empty()) {
+    RT_HIP(c, hipMemsetAsync(D.dOut + 1, 0, jobs.size() * 4, s));
+    RT_HIP(c, hipMemcpyAsync(D.dCoordJobs, jobs.data(), jobs.size() * sizeof(CoordJob), hipMemcpyHostToDevice, s));
+    CoordMaxArgs ca{};
+    ca.vertices = skinJobs ? D.dStaged : c->ds.vertices; ca.indices = c->ds.indices; ca.instances = c->ds.instances; ca.jobs = D.dCoordJobs;
+    ca.numJobs = uint32_t(jobs.size()); ca.numThreads = threads; ca.out = D.dOut + 1;
+    RT_HIP(c, launchInstCoordMax(s, ca));
+  }
+  RT_HIP(c, hipMemcpyAsync(out.data(), D.dOut, out.size() * 4, hipMemcpyDeviceToHost, s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  if(skinJobs && out[0] != 0u) { c->err = std::string(who) + ": the pose yields a non-finite position"; return RT_ERR_INVALID_ARG; }   // only the staging range was written
+  if(skinJobs) {   // commit: staging range -> live rows, on the stream ahead of the refit
+    for(size_t k = 0; k < skinJobs->size(); k++) {
+      const SkinJob& j = (*skinJobs)[k];
+      const rt_prim_mesh& pm = c->primMeshes[D.skins[(*skinIds)[k]].primMesh];
+      if(j.count) RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + pm.vertexOffset, D.dStaged + j.restFirst, size_t(j.count) * sizeof(rt_vertex), hipMemcpyDeviceToDevice, s));
+      D.stale[(*skinIds)[k]] = 1;
+    }
+    RT_HIP(c, hipEventRecord(c->evDeform[1], s));
+  }
+  const size_t words = (nInst + 31) / 32 + 1;
+  std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
+  for(size_t k = 0; k < jobs.size(); k++) {
+    const uint32_t i = jobs[k].instance;
+    memcpy(&R.instMax[i], &out[1 + k], 4);
+    dirty[i >> 5] |= 1u << (i & 31u);
+    float inv[12], det;
+    inverseAffine(R.inst[i].o2w, inv, &det);   // k_refit_tris rewrites TRI_FLIP of every dirty record: the handedness of the instance's current matrix
+    if(det < 0.0f) flipBits[i >> 5] |= 1u << (i & 31u);
+  }
+  float scale = 1e-3f;
+  for(float v : R.instMax) scale = std::max(scale, v);
+  const float triPad = 2e-5f * scale;
+  const bool full = triPad > R.treePad && c->ds.numTris > 0;
+  if(triPad > R.treePad) R.treePad = triPad;
+  RT_HIP(c, hipMemcpyAsync(R.dDirty, dirty.data(), words * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemsetAsync(R.dNodeDirty, 0, std::max<size_t>(c->ds.numNodes, 1) * 4, s));
+  RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
+  uint32_t counters[4] = {0, 0, 0, 0};
+  if(c->ds.numTris > 0 && (!jobs.empty() || full)) {
+    RefitArgs a{};
+    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
+    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
+    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
+    RT_HIP(c, launchRefitTris(s, a));
+    for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
+    RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
+  }
+  RT_HIP(c, hipEventRecord(c->evRefit[1], s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  c->ds.triPad = triPad;
+  c->refN = 0;   // the scene changed: the reference sums start again
+  R.stats = rt_refit_stats{};
+  R.stats.instances = uint32_t(jobs.size()); R.stats.leafRecords = counters[0]; R.stats.nodes = counters[1]; R.stats.levels = uint32_t(R.levels.size());
+  R.stats.fullRefit = full ? 1u : 0u; R.stats.triPad = triPad; R.stats.treePad = R.treePad;
+  (void)hipEventElapsedTime(&R.stats.ms, c->evRefit[0], c->evRefit[1]);
+  D.stats = rt_deform_stats{};
+  D.stats.meshes = uint32_t(meshes.size()); D.stats.vertices = verticesWritten; D.stats.instances = uint32_t(jobs.size()); D.stats.vertexBytesCopied = bytesCopied;
+  D.stats.ms = R.stats.ms;
+  if(skinJobs) (void)hipEventElapsedTime(&D.stats.skinMs, c->evDeform[0], c->evDeform[1]);
+  return RT_OK;
+}
+
+extern "C" {
+
+int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint32_t count, const rt_vertex* rows)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_vertices: no scene uploaded");
+  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_vertices: rt_build_accel has not run");
+  if(primMesh >= c->primMeshes.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: prim mesh out of range");
+  const rt_prim_mesh& pm = c->primMeshes[primMesh];
+  if(uint64_t(firstVertex) + count > pm.vertexCount) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: vertex range outside the prim mesh");
+  if(count && !rows) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: NULL rows");
+  if(!c->deform.skinOfMesh.empty() && c->deform.skinOfMesh[primMesh] >= 0) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: the prim mesh has a skin");
+  const size_t base = size_t(pm.vertexOffset) + firstVertex;
+  for(uint32_t k = 0; k < count; k++) {
+    const rt_vertex& v = rows[k];
+    if(!std::isfinite(v.position.x) || !std::isfinite(v.position.y) || !std::isfinite(v.position.z)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: non-finite position");
+    if(memcmp(&v.texcoord, &c->vertices[base + k].texcoord, sizeof(rt_vec2)) != 0)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: texcoord differs from the uploaded row (alpha records and micro-maps were derived from it)");
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // v1: joins the frames in flight
+  int rc;
+  if((rc = ensureRefitState(c))) return rc;
+  if((rc = ensureDeformBuffers(c))) return rc;
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evRefit[0], s));
+  std::vector<uint32_t> meshes;
+  if(count) {
+    memcpy(c->vertices.data() + base, rows, size_t(count) * sizeof(rt_vertex));
+    RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + base, c->vertices.data() + base, size_t(count) * sizeof(rt_vertex), hipMemcpyHostToDevice, s));
+    meshes.push_back(primMesh);
+  }
+  return deformRefit(c, "rt_update_vertices", meshes, nullptr, nullptr, count, count * uint32_t(sizeof(rt_vertex)));
+}
+
+int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t numInfluences, const rt_skin_influence* influences)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_skins: no scene uploaded");
+  if(numSkins && !skins) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: NULL skins");
+  std::vector<int32_t> skinOfMesh(c->primMeshes.size(), -1);
+  std::vector<uint32_t> restFirst(numSkins, 0u);
+  uint64_t totalVerts = 0, totalJoints = 0;
+  for(uint32_t k = 0; k < numSkins; k++) {
+    const rt_skin& sk = skins[k];
+    if(sk.primMesh >= c->primMeshes.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: prim mesh out of range");
+    if(skinOfMesh[sk.primMesh] >= 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: prim mesh listed twice");
+    skinOfMesh[sk.primMesh] = int32_t(k);
+    if(sk.jointCount == 0 || sk.jointCount > 65536u) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: jointCount must be 1 .. 65536");
+    const rt_prim_mesh& pm = c->primMeshes[sk.primMesh];
+    if(uint64_t(sk.firstInfluence) + pm.vertexCount > numInfluences || (pm.vertexCount && !influences))
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: influence range outside the array");
+    for(uint32_t v = 0; v < pm.vertexCount; v++) {
+      const rt_skin_influence& in = influences[size_t(sk.firstInfluence) + v];
+      for(int q = 0; q < 4; q++) {
+        if(in.joint[q] >= sk.jointCount) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: joint index beyond the skin's jointCount");
+        if(!std::isfinite(in.weight[q])) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: non-finite weight");
+      }
+    }
+    const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
+    if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
+    restFirst[k] = uint32_t(totalVerts);
+    totalVerts += pm.vertexCount; totalJoints += sk.jointCount;
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  int rc;
+  if((rc = syncHostVertices(c))) return rc;   // the stale marks go with the old skins
+  rt_ctx::Deform& D = c->deform;
+  freePool(c->skinAllocs);
+  D.skins.clear(); D.restFirst.clear(); D.skinOfMesh.clear(); D.stale.clear();
+  D.dRest = D.dStaged = nullptr; D.dInfluences = nullptr; D.dJoints = nullptr; D.dSkinJobs = nullptr;
+  c->refN = 0;
+  if(numSkins == 0) return RT_OK;
+  const rt_vertex* vp = nullptr; const rt_skin_influence* ip = nullptr; const float* fp = nullptr; const SkinJob* jp = nullptr;
+  if((rc = upload<rt_vertex>(c, c->skinAllocs, nullptr, size_t(totalVerts), &vp))) return rc;
+  D.dRest = const_cast<rt_vertex*>(vp);
+  if((rc = upload<rt_vertex>(c, c->skinAllocs, nullptr, size_t(totalVerts), &vp))) return rc;
+  D.dStaged = const_cast<rt_vertex*>(vp);
+  if((rc = upload(c, c->skinAllocs, influences, size_t(numInfluences), &ip))) return rc;
+  D.dInfluences = const_cast<rt_skin_influence*>(ip);
+  if((rc = upload<float>(c, c->skinAllocs, nullptr, size_t(totalJoints) * 12, &fp))) return rc;
+  D.dJoints = const_cast<float*>(fp);
+  if((rc = upload<SkinJob>(c, c->skinAllocs, nullptr, numSkins, &jp))) return rc;
+  D.dSkinJobs = const_cast<SkinJob*>(jp);
+  for(uint32_t k = 0; k < numSkins; k++) {   // the rest pose: the context's current rows
+    const rt_prim_mesh& pm = c->primMeshes[skins[k].primMesh];
+    if(pm.vertexCount) RT_HIP(c, hipMemcpy(D.dRest + restFirst[k], c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToDevice));
+  }
+  RT_HIP(c, hipDeviceSynchronize());
+  D.skins.assign(skins, skins + numSkins);
+  D.restFirst = restFirst; D.skinOfMesh = skinOfMesh; D.stale.assign(numSkins, 0);
+  return RT_OK;
+}
+
+int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const float* mats)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_skins: no scene uploaded");
+  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_skins: rt_build_accel has not run");
+  rt_ctx::Deform& D = c->deform;
+  if(D.skins.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: no skins (rt_set_skins)");
+  if(count && (!skinIds || !mats)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: NULL ids / matrices");
+  std::vector<SkinJob> jobs(count);
+  std::vector<uint32_t> ids(skinIds, skinIds + count), meshes;
+  uint32_t threads = 0, joints = 0;
+  {
+    std::vector<bool> seen(D.skins.size(), false);
+    for(uint32_t k = 0; k < count; k++) {
+      if(ids[k] >= D.skins.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: skin id out of range");
+      if(seen[ids[k]]) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: duplicate skin id");
+      seen[ids[k]] = true;
+      const rt_skin& sk = D.skins[ids[k]];
+      for(size_t a = 0; a < size_t(sk.jointCount) * 12; a++)
+        if(!std::isfinite(mats[size_t(joints) * 12 + a])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: non-finite matrix entry");
+      SkinJob& j = jobs[k];
+      j = SkinJob{};
+      j.threadBase = threads; j.count = c->primMeshes[sk.primMesh].vertexCount; j.restFirst = D.restFirst[ids[k]]; j.firstInfluence = sk.firstInfluence; j.firstJoint = joints;
+      threads += j.count; joints += sk.jointCount;
+      meshes.push_back(sk.primMesh);
+    }
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // v1: joins the frames in flight
+  int rc;
+  if((rc = ensureRefitState(c))) return rc;
+  if((rc = ensureDeformBuffers(c))) return rc;
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evRefit[0], s));
+  RT_HIP(c, hipEventRecord(c->evDeform[0], s));
+  RT_HIP(c, hipMemsetAsync(D.dOut, 0, 4, s));
+  if(count) {
+    RT_HIP(c, hipMemcpyAsync(D.dSkinJobs, jobs.data(), jobs.size() * sizeof(SkinJob), hipMemcpyHostToDevice, s));
+    RT_HIP(c, hipMemcpyAsync(D.dJoints, mats, size_t(joints) * 12 * sizeof(float), hipMemcpyHostToDevice, s));
+    SkinArgs a{};
+    a.rest = D.dRest; a.staged = D.dStaged; a.influences = D.dInfluences; a.joints = D.dJoints; a.jobs = D.dSkinJobs;
+    a.numJobs = count; a.numThreads = threads; a.nonFinite = D.dOut;
+    RT_HIP(c, launchSkin(s, a));
+  }
+  return deformRefit(c, "rt_update_skins", meshes, &jobs, &ids, threads, 0u);
+}
+
+int rt_vertices_readback(rt_ctx* c, uint64_t firstVertex, uint64_t count, rt_vertex* dst)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_vertices_readback: no scene uploaded");
+  if(firstVertex > c->vertices.size() || count > c->vertices.size() - firstVertex || (count && !dst)) return fail(c, RT_ERR_INVALID_ARG, "rt_vertices_readback: range outside the vertex array");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(count) RT_HIP(c, hipMemcpy(dst, c->ds.vertices + firstVertex, size_t(count) * sizeof(rt_vertex), hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_get_deform_stats(rt_ctx* c, rt_deform_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->deform.stats;
   return RT_OK;
 }
 

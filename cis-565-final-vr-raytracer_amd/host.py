@@ -30,6 +30,7 @@ def host_lib():
             "rth_scene_get_camera_pose": [C.c_void_p, C.c_void_p], "rth_scene_update_camera": [C.c_void_p, C.c_int, C.c_int],
             "rth_scene_get_camera": [C.c_void_p, C.c_void_p], "rth_scene_light_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_scene_update_instances": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
+            "rth_scene_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_env_destroy": [C.c_void_p], "rth_env_load": [C.c_void_p, C.c_char_p], "rth_env_set": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
             "rth_env_make_sky": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint32], "rth_env_integral": [C.c_void_p], "rth_env_average": [C.c_void_p],
@@ -113,6 +114,13 @@ class Scene:
         assert xf.shape[0] == ids.size
         if host_lib().rth_scene_update_instances(self._h, ids.ctypes.data, xf.ctypes.data, ids.size) != 0:
             raise ValueError("Scene.updateInstances: instance id out of range")
+    def updateVertices(self, prim_mesh, first, rows):
+        """Scene::updateVertices: rows (abi.VERTEX_DT records or n x 32 bytes) replace vertices [first, first + n) of one prim mesh; the triangle-light records are
+        recomputed; desc() afterwards describes the deformed scene"""
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(-1)
+        assert rows.size % 32 == 0
+        if host_lib().rth_scene_update_vertices(self._h, int(prim_mesh), int(first), rows.size // 32, rows.ctypes.data) != 0:
+            raise ValueError("Scene.updateVertices: prim mesh or vertex range out of bounds")
     def desc(self, env=None):
         d = abi.SceneDesc()
         host_lib().rth_scene_desc(self._h, env._h if env is not None else None, C.byref(d))

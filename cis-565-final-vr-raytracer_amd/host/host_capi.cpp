@@ -72,6 +72,10 @@ int rth_scene_update_instances(void* s, const uint32_t* ids, const float* transf
 {
   return static_cast<Scene*>(s)->updateInstances(ids, transforms, count) ? 0 : -1;
 }
+int rth_scene_update_vertices(void* s, uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows)
+{
+  return static_cast<Scene*>(s)->updateVertices(primMesh, first, count, rows) ? 0 : -1;
+}
 void rth_scene_desc(void* s, void* env, rt_scene_desc* out) { *out = static_cast<Scene*>(s)->getDesc(static_cast<HdrSampling*>(env)); }
 
 void* rth_env_create() { return new(std::nothrow) HdrSampling(); }

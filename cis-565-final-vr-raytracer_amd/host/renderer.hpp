@@ -40,6 +40,29 @@ class AccelStructure {
     }
     return true;
   }
+  // Deforming meshes (include/rt_abi.h "Deforming meshes"): host-computed rows for one prim mesh (the scene's copy and its triangle-light records follow, then the
+  // device rows, the refit and the light records), or skins posed on the GPU from joint matrices (setSkins once, updateSkins per frame).
+  bool updateVertices(Scene& scene, uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows)
+  {
+    if(!scene.updateVertices(primMesh, first, count, rows)) { fprintf(stderr, "AccelStructure::updateVertices: prim mesh or range out of bounds\n"); return false; }
+    const rt_scene_desc d = scene.getDesc(nullptr);
+    if(rt_update_vertices(m_ctx, primMesh, first, count, rows) != RT_OK ||
+       rt_update_lights(m_ctx, d.trigLights, d.trigLights ? d.lightInfo.trigLightSize : 0, d.puncLights, d.puncLights ? d.lightInfo.puncLightSize : 0, &d.lightInfo) != RT_OK) {
+      fprintf(stderr, "AccelStructure::updateVertices: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
+  bool setSkins(const std::vector<rt_skin>& skins, const std::vector<rt_skin_influence>& influences)
+  {
+    if(rt_set_skins(m_ctx, uint32_t(skins.size()), skins.data(), influences.size(), influences.data()) != RT_OK) { fprintf(stderr, "AccelStructure::setSkins: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  bool updateSkins(const uint32_t* skinIds, const float* jointMatrices, uint32_t count)
+  {
+    if(rt_update_skins(m_ctx, count, skinIds, jointMatrices) != RT_OK) { fprintf(stderr, "AccelStructure::updateSkins: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
   // A new topology for the moved scene, built on the GPU (include/rt_abi.h "Rebuilding on the device"): the host's remedy when rt_refit_stats::fullRefit is set
   // or the refitted tree has become slow.  The previous tree stays in place when it fails.
   bool rebuild()

@@ -270,6 +270,22 @@ bool Scene::updateInstances(const uint32_t* ids, const float* transforms, uint32
   return true;
 }
 
+bool Scene::updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows)
+{
+  if(primMesh >= m_gltf.primMeshes.size()) return false;
+  const GltfPrimMesh& pm = m_gltf.primMeshes[primMesh];
+  if(uint64_t(first) + count > pm.vertexCount || (count && !rows)) return false;
+  for(uint32_t k = 0; k < count; k++) {
+    const size_t i = size_t(pm.vertexOffset) + first + k;
+    m_vertices[i] = rows[k];
+    m_gltf.positions[i] = V3{rows[k].position.x, rows[k].position.y, rows[k].position.z};
+  }
+  createTrigLightBuffer();   // (as updateInstances: the records keep their order, the alias table depends on the materials only)
+  if(m_lightBufInfo.puncLightSize > 0 || m_lightBufInfo.trigLightSize > 0)
+    m_lightBufInfo.trigSampProb = m_trigLightWeight / (m_trigLightWeight + m_puncLightWeight);
+  return true;
+}
+
 rt_scene_desc Scene::getDesc(const HdrSampling* env) const
 {
   rt_scene_desc d{};

@@ -89,6 +89,10 @@ class Scene {
   // getDesc() afterwards describes the moved scene (rt_update_lights takes trigLights / puncLights / lightInfo from it).  The reference moves a node by editing
   // nvh::GltfScene::m_nodes and rebuilding its TLAS (src/accelstruct.cpp:132-162).
   bool updateInstances(const uint32_t* ids, const float* transforms, uint32_t count);
+  // Deform a prim mesh on the host (include/rt_abi.h "Deforming meshes"): rows replace vertices [first, first + count) of the mesh in the vertex buffer and their
+  // positions in the loader's arrays, and the triangle-light records are recomputed as by updateInstances, so a deformed emitter lights from its new shape
+  // (rt_update_vertices takes the same rows, rt_update_lights the records from getDesc()).  False (nothing changed) for a mesh or a range out of bounds.
+  bool updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows);
 
   float m_puncLightWeight = 0.f, m_trigLightWeight = 0.f;  // scene.hpp:79-80
   rt_light_buf_info m_lightBufInfo{};                      // scene.hpp:113 (zero-initialised here: quirk 10)

@@ -23,6 +23,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback",
+               "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -128,6 +129,12 @@ def hip_lib():
             L.rt_set_object_motion.argtypes = [C.c_void_p, C.c_int]
             L.rt_object_motion_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rt_object_motion_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        if hasattr(L, "rt_update_vertices"):   # deforming meshes (absent from older A/B libraries)
+            L.rt_update_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+            L.rt_set_skins.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+            L.rt_update_skins.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rt_vertices_readback.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+            L.rt_get_deform_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -444,6 +451,38 @@ class Renderer:
     def rebuild_stats(self):
         s = abi.RebuildStats()
         self._chk(hip_lib().rt_get_rebuild_stats(self._h, C.byref(s)), "rt_get_rebuild_stats")
+        return s
+
+    # ---- deforming meshes (include/rt_abi.h "Deforming meshes")
+    def update_vertices(self, prim_mesh, first_vertex, rows):
+        """rt_update_vertices: rows = abi.VERTEX_DT records (or n x 32 bytes) that replace rows [first_vertex, first_vertex + n) of one prim mesh; every instance of
+        the mesh is refitted on the GPU; drains the frames in flight"""
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(-1)
+        if rows.size % 32:
+            raise ValueError("update_vertices: 32 bytes per row")
+        self._chk(hip_lib().rt_update_vertices(self._h, int(prim_mesh), int(first_vertex), rows.size // 32, rows.ctypes.data), "rt_update_vertices")
+
+    def set_skins(self, skins, influences):
+        """rt_set_skins: skins = abi.SKIN_DT records (one per skinned prim mesh), influences = abi.SKIN_INFLUENCE_DT records; captures the rest pose.  Empty: removes the skins"""
+        sk = np.ascontiguousarray(skins, dtype=abi.SKIN_DT).reshape(-1)
+        inf = np.ascontiguousarray(influences, dtype=abi.SKIN_INFLUENCE_DT).reshape(-1)
+        self._chk(hip_lib().rt_set_skins(self._h, sk.size, sk.ctypes.data, inf.size, inf.ctypes.data), "rt_set_skins")
+
+    def update_skins(self, skin_ids, joint_matrices):
+        """rt_update_skins: re-poses the listed skins on the GPU; joint_matrices = per listed skin jointCount x 12 floats (3 x 4 row-major), concatenated"""
+        ids = np.ascontiguousarray(skin_ids, dtype=np.uint32).reshape(-1)
+        m = np.ascontiguousarray(joint_matrices, dtype=np.float32).reshape(-1)
+        self._chk(hip_lib().rt_update_skins(self._h, ids.size, ids.ctypes.data, m.ctypes.data), "rt_update_skins")
+
+    def vertices_readback(self, first_vertex, count):
+        """the device vertex array as it is now: abi.VERTEX_DT records"""
+        out = np.zeros(int(count), dtype=abi.VERTEX_DT)
+        self._chk(hip_lib().rt_vertices_readback(self._h, int(first_vertex), int(count), out.ctypes.data), "rt_vertices_readback")
+        return out
+
+    def deform_stats(self):
+        s = abi.DeformStats()
+        self._chk(hip_lib().rt_get_deform_stats(self._h, C.byref(s)), "rt_get_deform_stats")
         return s
 
     # ---- object motion vectors (include/rt_abi.h "Object motion vectors", DESIGN.md §20)

@@ -792,6 +792,69 @@ enum { RT_OBJECT_MOTION_OFF = 0 /* default */, RT_OBJECT_MOTION_ON = 1 };
 int rt_set_object_motion(rt_ctx* ctx, int mode);
 int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectToWorld[12], const float curObjectToWorld[12], rt_scene_camera* out);
 int rt_object_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Deforming meshes (added within ABI 2.4, no version bump; csrc/deform.hip).  rt_update_instances moves rigid instances; these calls change the
+ * VERTICES of a prim mesh on the device — rows supplied by the host (rt_update_vertices: cloth, morph targets, anything the host computes) or posed on the GPU from
+ * a rest pose and a few joint matrices (rt_set_skins once, rt_update_skins per frame) — then rewrite the leaf records of every instance of that mesh and refit the
+ * BVH8 above them with the kernels of rt_update_instances.  No upload of the scene, no rebuild, no re-derived alpha records or micro-maps.  Results are a function of
+ * the triangle set only: frames and ray queries afterwards are bit for bit those of a context that uploaded and built the deformed scene.
+ * EVERY instance of a prim mesh deforms with it: characters that move independently need a prim mesh each.
+ *
+ * rt_update_vertices(ctx, primMesh, firstVertex, count, rows): replaces rows [firstVertex, firstVertex + count) of one prim mesh (indices relative to the mesh).
+ *   Valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise).  A prim mesh out of range, a range outside the mesh, a non-finite position, a texcoord
+ *   whose bits differ from the uploaded row (the alpha records and opacity micro-maps were derived from it, and the tangent's handedness bit lives there) or a mesh
+ *   that has a skin refuses the WHOLE call with RT_ERR_INVALID_ARG and changes nothing.  Position, normal, tangent and colour may change.  count == 0 is a valid call
+ *   that changes no vertex.  The rows also replace the context's copy of the scene (a later rt_build_accel builds the deformed scene).
+ *   Emitters: the triangle-light records hold world positions; a host that deforms an emissive mesh recomputes them and calls rt_update_lights.
+ * rt_set_skins(ctx, numSkins, skins, numInfluences, influences): valid after rt_upload_scene.  Replaces all skins (numSkins == 0 removes them).  Skin k poses prim
+ *   mesh skins[k].primMesh with jointCount matrices; its vertex v has the influence row influences[firstInfluence + v] (vertexCount rows).  The call captures the rest
+ *   pose — the context's current rows of those meshes — into a device buffer of its own and allocates a staging range of the same size for the posed rows.
+ *   RT_ERR_INVALID_ARG, nothing changed, for: a prim mesh out of range or listed twice; jointCount == 0 or > 65536; an influence range that lies outside the array
+ *   (it is vertexCount rows long); a joint index >= jointCount; a non-finite weight; a mesh whose material is emissive by the scene's light rule (luminance of
+ *   emissiveFactor > 1e-2): its triangle-light records hold world positions the host could no longer supply.  That is a limit of this version; host-deformed
+ *   emitters go through rt_update_vertices + rt_update_lights.  rt_upload_scene drops the skins; rt_build_accel and rt_rebuild_accel keep them.
+ * rt_update_skins(ctx, count, skinIds, jointMatrices): re-poses the listed skins from the rest pose on the GPU.  jointMatrices = for every listed skin, in the
+ *   order listed, jointCount x 12 floats (3 x 4 row-major, the layout of rt_instance::objectToWorld), concatenated.  Valid after rt_build_accel.  No skins set, an id
+ *   out of range or listed twice, a non-finite matrix entry, or a pose that yields a non-finite position refuses the WHOLE call with RT_ERR_INVALID_ARG: the kernel
+ *   writes the staging range and counts such positions, and the staged rows are copied to the live vertex array only when the count is zero.
+ *   The arithmetic, fp32, no contraction (include/rt_detmath.h), for a vertex with rest row (p, normal, texcoord, tangent, colour) and influence (j_k, w_k), k = 0..3:
+ *     B[e] = ((w0 M[j0][e] + w1 M[j1][e]) + w2 M[j2][e]) + w3 M[j3][e] for each of the 12 entries e; a zero weight is not skipped;
+ *     position' = ((B[r][0] x + B[r][1] y) + B[r][2] z) + B[r][3] per row r (xformPointRaw);
+ *     with a b c / d e f / g h i the rows of B's 3 x 3 part, the cofactors  c00 = e i - f h, c01 = f g - d i, c02 = d h - e g, c10 = c h - b i, c11 = a i - c g,
+ *     c12 = b g - a h, c20 = b f - c e, c21 = c d - a f, c22 = a e - b d, det = (a c00 + b c01) + c c02, s = -1 when det < 0, else +1, n = decompress_unit_vec(normal),
+ *     m[r] = s ((c[r][0] n.x + c[r][1] n.y) + c[r][2] n.z)   (the inverse transpose without its division, turned outwards again under a mirroring blend);
+ *     u[r] = (B[r][0] t.x + B[r][1] t.y) + B[r][2] t.z with t = decompress_unit_vec(tangent);
+ *     for v = m or u: d = (v.x v.x + v.y v.y) + v.z v.z, q = 1 / sqrt(d), packed' = compress_unit_vec(v q) — but the rest row's packed value is kept when d is not
+ *     > 0, d is infinite or q is infinite, and a packed value of 0xffffffff (the codec's sentinel) stays as it is.  texcoord (with the handedness bit) and colour are copied.
+ * All three: like rt_update_instances v1 they join the frames in flight, run on the context's main stream and return after their kernels completed; they reset the
+ *   reference-mode sums (n -> 0); they leave the SVGF / TAA histories, the object-motion state and the stream-priority decision alone (a deformation is not instance
+ *   motion: an instance's previous matrix stays its current one, and the histories' G-buffer tests reject a surface that changed under a pixel); they free nothing.
+ *   rt_update_vertices and rt_update_skins refit like rt_update_instances — v0 / e1 / e2 and TRI_FLIP of every leaf record of every instance of the deformed meshes,
+ *   the boxes above them, the hit rule's pad (which equals a fresh build's: a reduction over the INDEXED vertices, so a vertex no triangle references does not
+ *   move it), a full refit when the pad grows — and rt_get_refit_stats afterwards describes that refit (instances = the instances refitted).
+ *   Host copy: rt_update_skins moves no vertex across the bus; the context's own copy of a skinned mesh is refreshed from the device by the calls that read it
+ *   (rt_build_accel, rt_rebuild_accel's first use, rt_update_instances of an instance of that mesh, rt_set_skins).
+ *   Scope: the single-GPU context only.  rt_mgpu_* contexts and the row-tiled hosts (restir_amd/tiled.py) have no deformation path: they upload the deformed scene.
+ * rt_vertices_readback(ctx, firstVertex, count, dst): rows [firstVertex, firstVertex + count) of the device vertex array (indices into rt_scene_desc::vertices) as
+ *   they are now, for tests and diagnostics.  Valid after rt_upload_scene; a range outside the array is RT_ERR_INVALID_ARG.  Synchronous.
+ * rt_get_deform_stats: what the last rt_update_vertices / rt_update_skins that succeeded did.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t primMesh, firstJoint, jointCount, firstInfluence; } rt_skin;   /* one per skinned prim mesh; firstJoint is the host's own bookkeeping (its joint palette) and is not read */
+typedef struct { uint16_t joint[4]; float weight[4]; } rt_skin_influence;                /* 24 B per vertex; joint < the skin's jointCount */
+typedef struct {
+  uint32_t meshes;            /* prim meshes deformed by the call */
+  uint32_t vertices;          /* vertices written */
+  uint32_t instances;         /* instances refitted */
+  uint32_t vertexBytesCopied; /* vertex bytes the call moved between host and device, either way (0 for rt_update_skins) */
+  float    skinMs;            /* HIP-event time of the skinning kernel and the commit copy (0 for rt_update_vertices) */
+  float    ms;                /* HIP-event time of the whole call on the main stream */
+  uint32_t reserved[2];
+} rt_deform_stats;            /* 32 B */
+int rt_update_vertices(rt_ctx* ctx, uint32_t primMesh, uint32_t firstVertex, uint32_t count, const rt_vertex* rows);
+int rt_set_skins(rt_ctx* ctx, uint32_t numSkins, const rt_skin* skins, uint64_t numInfluences, const rt_skin_influence* influences);
+int rt_update_skins(rt_ctx* ctx, uint32_t count, const uint32_t* skinIds, const float* jointMatrices);
+int rt_vertices_readback(rt_ctx* ctx, uint64_t firstVertex, uint64_t count, rt_vertex* dst);
+int rt_get_deform_stats(rt_ctx* ctx, rt_deform_stats* out);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
@@ -822,6 +885,8 @@ static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
 static_assert(sizeof(rt_gi_spatial) == 32, "rt_gi_spatial");
 static_assert(sizeof(rt_taa) == 32, "rt_taa");
 static_assert(sizeof(rt_refit_stats) == 32, "rt_refit_stats");
+static_assert(sizeof(rt_deform_stats) == 32, "rt_deform_stats");
+static_assert(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 #endif
 
 #endif /* RT_ABI_H */
