@@ -784,8 +784,6 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
     }
     scaleOf[i] = sm;
   });
-  float scale = 1e-3f;
-  for(float v : scaleOf) scale = std::max(scale, v);
   timer.lap("flatten");
   const size_t n = total;
   out.nodes.clear(); out.tris.clear(); out.maxDepth = 0; out.sahNodeSteps = out.sahTriSteps = out.sahNodeStepsQ = out.sahTriStepsQ = 0; out.references = 0; out.spatialSplits = 0; out.rotations = 0; out.reinsertions = 0;
@@ -794,7 +792,7 @@ bool buildBvh8(const rt_scene_desc& sc, BuildOutput& out, int threads, bool plai
     out.nodes.push_back(e);
     return true;
   }
-  const float pad = 2e-5f * scale;
+  const float pad = triPadOf(scaleOf);
   out.pad = pad;
 
   // ---- 2. padded triangle boxes + binned-SAH BVH2 ---------------------------------------------------------------

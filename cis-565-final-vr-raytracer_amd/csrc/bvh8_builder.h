@@ -1,4 +1,5 @@
 #pragma once
+#include <algorithm>
 #include <vector>
 #include "bvh8.h"
 #include "dev_scene.h"
@@ -30,5 +31,13 @@ bool buildBvh8(const rt_scene_desc& scene, BuildOutput& out, int threads, bool p
 // 3x4 affine inverse of an instance matrix (R = world-to-object, *detOut = the determinant of the 3x3 block): the builder's, shared with rt_update_instances so that a
 // moved instance's w2o bits equal a fresh build's
 void inverseAffine(const float* M, float* R, float* detOut);
+// The pad of the leaf boxes from every instance's largest |world coordinate|.  The one statement of the rule: the builder and the update / rebuild calls of rt_api.cpp
+// reduce with it, so a refitted or rebuilt tree's pad has the bits of a fresh build's (a float maximum does not depend on the order).
+inline float triPadOf(const std::vector<float>& instMax)
+{
+  float scale = 1e-3f;
+  for(float v : instMax) scale = std::max(scale, v);
+  return 2e-5f * scale;
+}
 
 }  // namespace rt

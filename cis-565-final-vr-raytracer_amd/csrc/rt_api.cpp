@@ -120,12 +120,13 @@ struct rt_ctx {
   bool taaHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame taaFrame[parity] (rt_tonemap)
   int taaFrame[2] = {0, 0};
   // rt_update_instances (csrc/refit.hip).  Made by the first update after a build from the device tree (ensureRefitState) and dropped with the tree: the record -> node
-  // map, the contiguous node range of every level, per instance its largest |world coordinate| (the pad is a reduction over instances) and its leaf-record count.
+  // map, the contiguous node range of every level, per instance its largest |world coordinate| (the pad is a reduction over instances) and its handedness.
   // The device arrays live in accelAllocs.
   struct Refit {
     bool ready = false;
     std::vector<DevInstance> inst;               // host copy of the device instance rows
     std::vector<float> instMax;                  // largest |world coordinate| of every instance's triangles
+    std::vector<uint8_t> flip;                   // 1: the instance's current matrix mirrors (det < 0): the TRI_FLIP bit k_refit_tris gives its records
     std::vector<std::pair<uint32_t, uint32_t>> levels;   // (first node, count), root level first
     uint32_t* dDirty = nullptr; uint32_t* dFlip = nullptr; uint32_t* dRecNode = nullptr; uint32_t* dNodeDirty = nullptr; uint32_t* dCounters = nullptr;
     float treePad = 0.f;                         // the pad the tree's boxes were last computed with
@@ -401,6 +402,15 @@ template <class T> static int upload(rt_ctx* c, std::vector<void*>& pool, const 
   else RT_HIP(c, hipMemset(d, 0, bytes));
   *out = static_cast<const T*>(d);
   return RT_OK;
+}
+// a zero-filled device array the library itself writes later (upload is for scene data, which stays const)
+template <class T> static int allocZeroed(rt_ctx* c, std::vector<void*>& pool, size_t count, T** out)
+{
+  const T* const noSource = nullptr;   // upload clears the array instead of copying
+  const T* p = nullptr;
+  const int rc = upload(c, pool, noSource, count, &p);
+  *out = const_cast<T*>(p);
+  return rc;
 }
 static void freePool(std::vector<void*>& pool) { for(void* p : pool) (void)hipFree(p); pool.clear(); }
 // RESTIR_BVH_TIMING=1: where the seconds of rt_upload_scene / rt_build_accel go (stderr)
@@ -1990,6 +2000,24 @@ int rt_get_stream_layout(rt_ctx* c, int* created, int index[3])
 /* ---- moving instances: leaf-record rewrite + BVH8 refit (include/rt_abi.h "Moving instances", csrc/refit.hip) ---- */
 }  // extern "C"
 
+// what the calls that change a built tree open with; the message carries the caller's name
+static int needTree(rt_ctx* c, const char* who)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(c->haveScene && c->haveAccel) return RT_OK;
+  c->err = std::string(who) + (c->haveScene ? ": rt_build_accel has not run" : ": no scene uploaded");
+  return c->haveScene ? RT_ERR_NO_ACCEL : RT_ERR_NO_SCENE;
+}
+
+// the per-instance bit tables of k_refit_tris (dDirty, dFlip): one bit per instance and a spare word; bit i is set where pred(i)
+static size_t instanceWords(size_t nInst) { return (nInst + 31) / 32 + 1; }
+template <class P> static std::vector<uint32_t> instanceBits(size_t nInst, P pred)
+{
+  std::vector<uint32_t> w(instanceWords(nInst), 0u);
+  for(size_t i = 0; i < nInst; i++) if(pred(i)) w[i >> 5] |= 1u << (i & 31u);
+  return w;
+}
+
 // largest |world coordinate| over the triangles of instance i under matrix m: the builder's expression (buildBvh8, flatten), per instance
 static float instanceCoordMax(const rt_ctx* c, uint32_t i, const float* m)
 {
@@ -2034,24 +2062,65 @@ static int ensureRefitState(rt_ctx* c)
   }
   if(size_t(first) != nNodes) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: the tree's levels are not contiguous node ranges");
   { const int rc = syncHostVertices(c); if(rc) return rc; }
-  R.instMax.resize(nInst);
-  for(uint32_t i = 0; i < nInst; i++) R.instMax[i] = instanceCoordMax(c, i, c->instances[i].objectToWorld);
-  const size_t words = (nInst + 31) / 32 + 1;
+  R.instMax.resize(nInst); R.flip.resize(nInst);
+  for(uint32_t i = 0; i < nInst; i++) {
+    R.instMax[i] = instanceCoordMax(c, i, c->instances[i].objectToWorld);
+    float inv[12], det;
+    inverseAffine(R.inst[i].o2w, inv, &det);
+    R.flip[i] = det < 0.0f;
+  }
+  const size_t words = instanceWords(nInst);
   int rc;
   const uint32_t* up = nullptr;
-  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, words, &up))) return rc;
-  R.dDirty = const_cast<uint32_t*>(up);
-  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, words, &up))) return rc;
-  R.dFlip = const_cast<uint32_t*>(up);
+  if((rc = allocZeroed(c, c->accelAllocs, words, &R.dDirty))) return rc;
+  if((rc = allocZeroed(c, c->accelAllocs, words, &R.dFlip))) return rc;
   if((rc = upload(c, c->accelAllocs, recNode.data(), recNode.size(), &up))) return rc;
   R.dRecNode = const_cast<uint32_t*>(up);
-  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, std::max<size_t>(nNodes, 1), &up))) return rc;
-  R.dNodeDirty = const_cast<uint32_t*>(up);
-  if((rc = upload<uint32_t>(c, c->accelAllocs, nullptr, 4, &up))) return rc;
-  R.dCounters = const_cast<uint32_t*>(up);
+  if((rc = allocZeroed(c, c->accelAllocs, std::max<size_t>(nNodes, 1), &R.dNodeDirty))) return rc;
+  if((rc = allocZeroed(c, c->accelAllocs, 4, &R.dCounters))) return rc;
   for(hipEvent_t& e : c->evRefit) if(!e) RT_HIP(c, hipEventCreate(&e));
   R.treePad = c->ds.triPad;
   R.ready = true;
+  return RT_OK;
+}
+
+// The refit every update ends with (rt_update_instances, rt_update_vertices, rt_update_skins).  dirty[i] != 0: instance i moved or deformed; R.inst, R.instMax and
+// R.flip already hold its new state, and the caller has recorded evRefit[0] and enqueued what the kernels read (instance rows, vertices).  From the pad to R.stats:
+// the dirty and flip words, the cleared node marks and counters, k_refit_tris, k_refit_level deepest level first, the counters, evRefit[1], one synchronise.
+static int refitTail(rt_ctx* c, const std::vector<uint8_t>& dirty)
+{
+  rt_ctx::Refit& R = c->refit;
+  const uint32_t count = uint32_t(dirty.size() - std::count(dirty.begin(), dirty.end(), uint8_t(0)));   // the predicate of the dirty bits: != 0
+  const std::vector<uint32_t> dirtyBits = instanceBits(dirty.size(), [&](size_t i) { return dirty[i] != 0; });
+  // k_refit_tris rewrites TRI_FLIP of every dirty record: the handedness of the instance's current matrix
+  const std::vector<uint32_t> flipBits = instanceBits(dirty.size(), [&](size_t i) { return dirty[i] && R.flip[i]; });
+  const float triPad = triPadOf(R.instMax);
+  const bool full = triPad > R.treePad && c->ds.numTris > 0;
+  if(triPad > R.treePad) R.treePad = triPad;
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipMemcpyAsync(R.dDirty, dirtyBits.data(), dirtyBits.size() * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), flipBits.size() * 4, hipMemcpyHostToDevice, s));
+  RT_HIP(c, hipMemsetAsync(R.dNodeDirty, 0, std::max<size_t>(c->ds.numNodes, 1) * 4, s));
+  RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
+  uint32_t counters[4] = {0, 0, 0, 0};
+  if(c->ds.numTris > 0 && (count > 0 || full)) {
+    RefitArgs a{};
+    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
+    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
+    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
+    RT_HIP(c, launchRefitTris(s, a));
+    for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
+    RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
+  }
+  RT_HIP(c, hipEventRecord(c->evRefit[1], s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  c->ds.triPad = triPad;
+  c->refN = 0;   // the scene changed: the reference sums start again
+  R.stats = rt_refit_stats{};
+  R.stats.instances = count; R.stats.leafRecords = counters[0]; R.stats.nodes = counters[1]; R.stats.levels = uint32_t(R.levels.size());
+  R.stats.fullRefit = full ? 1u : 0u; R.stats.triPad = triPad; R.stats.treePad = R.treePad;
+  (void)hipEventElapsedTime(&R.stats.ms, c->evRefit[0], c->evRefit[1]);
   return RT_OK;
 }
 
@@ -2059,9 +2128,7 @@ extern "C" {
 
 int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const float* xf)
 {
-  if(!c) return RT_ERR_INVALID_ARG;
-  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_instances: no scene uploaded");
-  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_instances: rt_build_accel has not run");
+  if(int rc = needTree(c, "rt_update_instances")) return rc;
   if(count && (!ids || !xf)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: NULL ids / matrices");
   const size_t nInst = c->instances.size();
   // the whole call is checked before anything changes
@@ -2090,8 +2157,7 @@ int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const fl
   if((rc = ensureRefitState(c))) return rc;
   rt_ctx::Refit& R = c->refit;
   for(uint32_t k = 0; k < count; k++) if((rc = syncHostVertices(c, int(c->instances[ids[k]].primMesh)))) return rc;   // instanceCoordMax reads the context's copy
-  const size_t words = (nInst + 31) / 32 + 1;
-  std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
+  std::vector<uint8_t> moved(nInst, 0);
   if(c->omPrev.size() != nInst) { c->omPrev.assign(nInst, std::array<float, 12>{}); c->omMoved.assign(nInst, 0); c->omPending = false; }
   for(uint32_t k = 0; k < count; k++) {
     const uint32_t i = ids[k];
@@ -2102,43 +2168,15 @@ int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const fl
     memcpy(c->instances[i].objectToWorld, rows[k].o2w, sizeof(rows[k].o2w));
     R.inst[i] = rows[k];
     R.instMax[i] = instanceCoordMax(c, i, rows[k].o2w);
-    dirty[i >> 5] |= 1u << (i & 31u);
-    if(flip[k]) flipBits[i >> 5] |= 1u << (i & 31u);
+    R.flip[i] = flip[k];
+    moved[i] = 1;
   }
-  float scale = 1e-3f;
-  for(float v : R.instMax) scale = std::max(scale, v);
-  const float triPad = 2e-5f * scale;
-  const bool full = triPad > R.treePad && c->ds.numTris > 0;
-  if(triPad > R.treePad) R.treePad = triPad;
   hipStream_t s = c->stream;
   RT_HIP(c, hipEventRecord(c->evRefit[0], s));
   DevInstance* dInst = const_cast<DevInstance*>(c->ds.instances);
   if(count * 4 > nInst) RT_HIP(c, hipMemcpyAsync(dInst, R.inst.data(), nInst * sizeof(DevInstance), hipMemcpyHostToDevice, s));
   else for(uint32_t k = 0; k < count; k++) RT_HIP(c, hipMemcpyAsync(dInst + ids[k], &rows[k], sizeof(DevInstance), hipMemcpyHostToDevice, s));
-  RT_HIP(c, hipMemcpyAsync(R.dDirty, dirty.data(), words * 4, hipMemcpyHostToDevice, s));
-  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
-  RT_HIP(c, hipMemsetAsync(R.dNodeDirty, 0, std::max<size_t>(c->ds.numNodes, 1) * 4, s));
-  RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
-  uint32_t counters[4] = {0, 0, 0, 0};
-  if(c->ds.numTris > 0 && (count > 0 || full)) {
-    RefitArgs a{};
-    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
-    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
-    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
-    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
-    RT_HIP(c, launchRefitTris(s, a));
-    for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
-    RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
-  }
-  RT_HIP(c, hipEventRecord(c->evRefit[1], s));
-  RT_HIP(c, hipStreamSynchronize(s));
-  c->ds.triPad = triPad;
-  c->refN = 0;   // the scene changed: the reference sums start again
-  R.stats = rt_refit_stats{};
-  R.stats.instances = count; R.stats.leafRecords = counters[0]; R.stats.nodes = counters[1]; R.stats.levels = uint32_t(R.levels.size());
-  R.stats.fullRefit = full ? 1u : 0u; R.stats.triPad = triPad; R.stats.treePad = R.treePad;
-  (void)hipEventElapsedTime(&R.stats.ms, c->evRefit[0], c->evRefit[1]);
-  return RT_OK;
+  return refitTail(c, moved);
 }
 
 int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, const rt_punc_light* punc, uint32_t numPunc, const rt_light_buf_info* info)
@@ -2165,9 +2203,7 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
 /* ---- rebuilding on the device: LBVH -> BVH8 (include/rt_abi.h "Rebuilding on the device", csrc/accel_build.hip) ---- */
 int rt_rebuild_accel(rt_ctx* c)
 {
-  if(!c) return RT_ERR_INVALID_ARG;
-  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_rebuild_accel: no scene uploaded");
-  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_rebuild_accel: rt_build_accel has not run");
+  if(int rc = needTree(c, "rt_rebuild_accel")) return rc;
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));   // drains the frames in flight, like rt_update_instances
   int rc;
@@ -2175,7 +2211,6 @@ int rt_rebuild_accel(rt_ctx* c)
   rt_ctx::Refit& R = c->refit;
   rt_ctx::Rebuild& B = c->rebuild;
   const uint32_t n = uint32_t(c->numTris);
-  const size_t nInst = c->instances.size();
   hipStream_t s = c->stream;
   if(!B.ready) {   // the first rebuild after a host build: buffers, and the per-triangle table from the host tree's records (still the context's tree)
     const hipError_t e = accelBuildAlloc(B.work, B.set, n, c->rebuildAllocs);
@@ -2194,17 +2229,11 @@ int rt_rebuild_accel(rt_ctx* c)
     }
     B.ready = true;
   }
-  // the pad of the scene as it is now (the per-instance maxima are kept by rt_update_instances), and every instance's handedness
-  float scale = 1e-3f;
-  for(float v : R.instMax) scale = std::max(scale, v);
-  const float triPad = 2e-5f * scale;
-  const size_t words = (nInst + 31) / 32 + 1;
-  std::vector<uint32_t> all(words, 0xffffffffu), flipBits(words, 0u);
-  for(size_t i = 0; i < nInst; i++) {
-    float inv[12], det;
-    inverseAffine(R.inst[i].o2w, inv, &det);
-    if(det < 0.0f) flipBits[i >> 5] |= 1u << (i & 31u);
-  }
+  // the pad of the scene as it is now, and every instance's handedness (both kept by the update calls)
+  const float triPad = triPadOf(R.instMax);
+  const std::vector<uint32_t> flipBits = instanceBits(c->instances.size(), [&](size_t i) { return R.flip[i] != 0; });
+  const size_t words = flipBits.size();
+  const std::vector<uint32_t> all(words, 0xffffffffu);
   rt_rebuild_stats st{};
   st.triangles = n; st.triPad = triPad;
   RT_HIP(c, hipEventRecord(c->evRebuild[0], s));
@@ -2315,17 +2344,15 @@ static int ensureDeformBuffers(rt_ctx* c)
   if(D.dOut) return RT_OK;
   const size_t nInst = c->instances.size();
   int rc;
-  const CoordJob* cj = nullptr; const uint32_t* out = nullptr;
-  if((rc = upload<CoordJob>(c, c->deformAllocs, nullptr, std::max<size_t>(nInst, 1), &cj))) return rc;
-  if((rc = upload<uint32_t>(c, c->deformAllocs, nullptr, nInst + 1, &out))) return rc;
-  D.dCoordJobs = const_cast<CoordJob*>(cj); D.dOut = const_cast<uint32_t*>(out);
+  if((rc = allocZeroed(c, c->deformAllocs, std::max<size_t>(nInst, 1), &D.dCoordJobs))) return rc;
+  if((rc = allocZeroed(c, c->deformAllocs, nInst + 1, &D.dOut))) return rc;
   for(hipEvent_t& e : c->evDeform) if(!e) RT_HIP(c, hipEventCreate(&e));
   return RT_OK;
 }
 
 // What rt_update_vertices and rt_update_skins share.  `meshes`: the deformed prim meshes.  skinJobs != nullptr: the pose is in the staging range (k_skin has been
 // enqueued after evRefit[0] / evDeform[0]); it is committed to the live array only when no staged position is non-finite, else the call is refused with nothing changed.
-// Then, as rt_update_instances: dirty and flip bits of every instance of those meshes, their coordinate maxima (k_inst_coord_max), the pads, the refit, the stats.
+// Then the coordinate maxima of every instance of those meshes (k_inst_coord_max) go into R.instMax, and refitTail does the rest as for rt_update_instances.
 static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& meshes, const std::vector<SkinJob>* skinJobs, const std::vector<uint32_t>* skinIds,
                        uint32_t verticesWritten, uint32_t bytesCopied)
 {
@@ -2336,10 +2363,12 @@ static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& 
   std::vector<uint8_t> deformed(c->primMeshes.size(), 0);
   for(uint32_t m : meshes) deformed[m] = 1;
   std::vector<CoordJob> jobs;
+  std::vector<uint8_t> dirty(nInst, 0);
   uint32_t threads = 0;
   for(uint32_t i = 0; i < nInst; i++) {
     const uint32_t m = c->instances[i].primMesh;
     if(!deformed[m]) continue;
+    dirty[i] = 1;
     const rt_prim_mesh& pm = c->primMeshes[m];
     CoordJob j{};
     j.threadBase = threads; j.indexCount = pm.indexCount; j.firstIndex = pm.firstIndex; j.instance = i;
@@ -2369,44 +2398,8 @@ static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& 
     }
     RT_HIP(c, hipEventRecord(c->evDeform[1], s));
   }
-  const size_t words = (nInst + 31) / 32 + 1;
-  std::vector<uint32_t> dirty(words, 0u), flipBits(words, 0u);
-  for(size_t k = 0; k < jobs.size(); k++) {
-    const uint32_t i = jobs[k].instance;
-    memcpy(&R.instMax[i], &out[1 + k], 4);
-    dirty[i >> 5] |= 1u << (i & 31u);
-    float inv[12], det;
-    inverseAffine(R.inst[i].o2w, inv, &det);   // k_refit_tris rewrites TRI_FLIP of every dirty record: the handedness of the instance's current matrix
-    if(det < 0.0f) flipBits[i >> 5] |= 1u << (i & 31u);
-  }
-  float scale = 1e-3f;
-  for(float v : R.instMax) scale = std::max(scale, v);
-  const float triPad = 2e-5f * scale;
-  const bool full = triPad > R.treePad && c->ds.numTris > 0;
-  if(triPad > R.treePad) R.treePad = triPad;
-  RT_HIP(c, hipMemcpyAsync(R.dDirty, dirty.data(), words * 4, hipMemcpyHostToDevice, s));
-  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
-  RT_HIP(c, hipMemsetAsync(R.dNodeDirty, 0, std::max<size_t>(c->ds.numNodes, 1) * 4, s));
-  RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
-  uint32_t counters[4] = {0, 0, 0, 0};
-  if(c->ds.numTris > 0 && (!jobs.empty() || full)) {
-    RefitArgs a{};
-    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
-    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
-    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
-    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
-    RT_HIP(c, launchRefitTris(s, a));
-    for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
-    RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
-  }
-  RT_HIP(c, hipEventRecord(c->evRefit[1], s));
-  RT_HIP(c, hipStreamSynchronize(s));
-  c->ds.triPad = triPad;
-  c->refN = 0;   // the scene changed: the reference sums start again
-  R.stats = rt_refit_stats{};
-  R.stats.instances = uint32_t(jobs.size()); R.stats.leafRecords = counters[0]; R.stats.nodes = counters[1]; R.stats.levels = uint32_t(R.levels.size());
-  R.stats.fullRefit = full ? 1u : 0u; R.stats.triPad = triPad; R.stats.treePad = R.treePad;
-  (void)hipEventElapsedTime(&R.stats.ms, c->evRefit[0], c->evRefit[1]);
+  for(size_t k = 0; k < jobs.size(); k++) memcpy(&R.instMax[jobs[k].instance], &out[1 + k], 4);
+  if(const int rc = refitTail(c, dirty)) return rc;
   D.stats = rt_deform_stats{};
   D.stats.meshes = uint32_t(meshes.size()); D.stats.vertices = verticesWritten; D.stats.instances = uint32_t(jobs.size()); D.stats.vertexBytesCopied = bytesCopied;
   D.stats.ms = R.stats.ms;
@@ -2418,9 +2411,7 @@ extern "C" {
 
 int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint32_t count, const rt_vertex* rows)
 {
-  if(!c) return RT_ERR_INVALID_ARG;
-  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_vertices: no scene uploaded");
-  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_vertices: rt_build_accel has not run");
+  if(int rc = needTree(c, "rt_update_vertices")) return rc;
   if(primMesh >= c->primMeshes.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: prim mesh out of range");
   const rt_prim_mesh& pm = c->primMeshes[primMesh];
   if(uint64_t(firstVertex) + count > pm.vertexCount) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: vertex range outside the prim mesh");
@@ -2489,17 +2480,13 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
   D.dRest = D.dStaged = nullptr; D.dInfluences = nullptr; D.dJoints = nullptr; D.dSkinJobs = nullptr;
   c->refN = 0;
   if(numSkins == 0) return RT_OK;
-  const rt_vertex* vp = nullptr; const rt_skin_influence* ip = nullptr; const float* fp = nullptr; const SkinJob* jp = nullptr;
-  if((rc = upload<rt_vertex>(c, c->skinAllocs, nullptr, size_t(totalVerts), &vp))) return rc;
-  D.dRest = const_cast<rt_vertex*>(vp);
-  if((rc = upload<rt_vertex>(c, c->skinAllocs, nullptr, size_t(totalVerts), &vp))) return rc;
-  D.dStaged = const_cast<rt_vertex*>(vp);
+  const rt_skin_influence* ip = nullptr;
+  if((rc = allocZeroed(c, c->skinAllocs, size_t(totalVerts), &D.dRest))) return rc;
+  if((rc = allocZeroed(c, c->skinAllocs, size_t(totalVerts), &D.dStaged))) return rc;
   if((rc = upload(c, c->skinAllocs, influences, size_t(numInfluences), &ip))) return rc;
   D.dInfluences = const_cast<rt_skin_influence*>(ip);
-  if((rc = upload<float>(c, c->skinAllocs, nullptr, size_t(totalJoints) * 12, &fp))) return rc;
-  D.dJoints = const_cast<float*>(fp);
-  if((rc = upload<SkinJob>(c, c->skinAllocs, nullptr, numSkins, &jp))) return rc;
-  D.dSkinJobs = const_cast<SkinJob*>(jp);
+  if((rc = allocZeroed(c, c->skinAllocs, size_t(totalJoints) * 12, &D.dJoints))) return rc;
+  if((rc = allocZeroed(c, c->skinAllocs, numSkins, &D.dSkinJobs))) return rc;
   for(uint32_t k = 0; k < numSkins; k++) {   // the rest pose: the context's current rows
     const rt_prim_mesh& pm = c->primMeshes[skins[k].primMesh];
     if(pm.vertexCount) RT_HIP(c, hipMemcpy(D.dRest + restFirst[k], c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToDevice));
@@ -2512,9 +2499,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
 
 int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const float* mats)
 {
-  if(!c) return RT_ERR_INVALID_ARG;
-  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_skins: no scene uploaded");
-  if(!c->haveAccel) return fail(c, RT_ERR_NO_ACCEL, "rt_update_skins: rt_build_accel has not run");
+  if(int rc = needTree(c, "rt_update_skins")) return rc;
   rt_ctx::Deform& D = c->deform;
   if(D.skins.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: no skins (rt_set_skins)");
   if(count && (!skinIds || !mats)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: NULL ids / matrices");
