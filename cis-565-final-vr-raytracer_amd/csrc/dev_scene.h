@@ -85,6 +85,11 @@ struct DevFrame {
   uint32_t* histMiss;
   int32_t stackLds;                 // traversal stack entries per lane kept in LDS by this frame's traced launches (0 = the whole stack); the rest sits in DevScene::stackOvf
   int32_t pad4;
+  // Seed plane (ctx-owned, sized by rt_resize): per full-resolution pixel the index into DevScene::tris of the leaf record the pixel's primary ray last accepted,
+  // 0xffffffff for a miss or "nothing yet"; k_direct_stage tests that record before its traversal loop (traverse.h traceRaySeeded).  ONE plane updated in place
+  // is enough: pixel p is read and written only by the thread that owns p, and the direct stages of successive frames are ordered on the context's main stream.
+  // seedIn is what the kernel reads (nullptr: no seed test this launch), seedOut what it writes; both point at the same plane.
+  const uint32_t* seedIn; uint32_t* seedOut;
 };
 
 // object motion vectors (rt_set_object_motion; the RT_OM builds of stages.hip take it as a kernel argument of its own, so DevFrame keeps its layout)

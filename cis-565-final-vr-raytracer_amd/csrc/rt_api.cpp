@@ -546,6 +546,17 @@ int rt_sync(rt_ctx* c)
   return RT_OK;
 }
 
+// The seed plane of the direct stage (DevFrame::seedIn / seedOut) holds indices into the tree's leaf records: whatever changes their order or count — a new
+// scene, a host build, a device rebuild — and rt_resize empty it, on the context's stream (the direct stages run there), so that two contexts that issue
+// the same calls trace the same steps and report the same counters.  The refit paths (rt_update_instances / _vertices / _skins) keep record indices: the
+// plane stays warm across them.  Nothing but speed depends on its contents (traverse.h traceRaySeeded).
+static int resetSeedPlane(rt_ctx* c)
+{
+  if(!c->scratch.seedOut || c->W <= 0) return RT_OK;
+  RT_HIP(c, hipMemsetAsync(c->scratch.seedOut, 0xff, size_t(c->W) * size_t(c->H) * sizeof(uint32_t), c->stream));
+  return RT_OK;
+}
+
 int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 {
   if(!c) return RT_ERR_INVALID_ARG;
@@ -674,7 +685,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   RT_HIP(c, hipDeviceSynchronize());
   c->haveScene = true;
   reopenPriorityDecision(c);   // (the context is drained: syncAll above / hipDeviceSynchronize below)
-  return RT_OK;
+  return resetSeedPlane(c);
 }
 
 
@@ -839,6 +850,7 @@ int rt_build_accel(rt_ctx* c)
   lt.lap("uploads (tree, alpha records)");
   c->haveAccel = true;
   reopenPriorityDecision(c);
+  if((rc = resetSeedPlane(c))) return rc;
   return ensureStackOverflow(c);
 }
 
@@ -899,12 +911,14 @@ int rt_resize(rt_ctx* c, int w, int h)
   RT_SCRATCH(postRowSums, size_t(h) * 6, double); RT_SCRATCH(postMean, 8, float);
   RT_SCRATCH(postMipD, n + 64, float4); RT_SCRATCH(postMipI, n + 64, float4);   // levels 1..7 (n/3 texels; up to n for one-pixel-wide images)
   RT_SCRATCH(tileOrder, (size_t(w / 2 + 7) / 8) * (size_t(h / 2 + 7) / 8 + 16 * 2) + 64 + 4096, uint32_t);   // 8 per-XCD lists: tiles + one chunk of slack each
+  RT_SCRATCH(seedOut, n, uint32_t); X.seedIn = X.seedOut;   // the direct stage's seed plane: read and written in place (dev_scene.h)
 #if RT_WAVEPROF
   RT_SCRATCH(waveProf, WAVEPROF_RECORDS * 16, uint32_t);
 #endif
 #undef RT_SCRATCH
   RT_HIP(c, hipDeviceSynchronize());  // memsets above ran on the null stream; the ctx stream does not wait for it implicitly
   c->W = w; c->H = h;
+  if((rc = resetSeedPlane(c))) return rc;
   if(c->objMotion != RT_OBJECT_MOTION_OFF && (rc = allocObjectMotion(c))) return rc;
   return ensureStackOverflow(c);
 }
@@ -1099,6 +1113,7 @@ static DevFrame makeFrame(rt_ctx* c, int frames)
   F.W = c->W; F.H = c->H;
   const DevFrame& X = c->scratch;
   F.surf = X.surf; F.status = X.status; F.qcount = X.qcount; F.waveProf = X.waveProf;
+  F.seedIn = X.seedIn; F.seedOut = X.seedOut;
   F.histRow0 = c->histRow0; F.histRow1 = c->histRow1; F.histMiss = X.qcount + 250;
   F.geomN = X.geomN; F.geomP = X.geomP; F.geomNh = X.geomNh; F.geomPh = X.geomPh; F.tileOrder = X.tileOrder; F.postRowSums = X.postRowSums; F.postMean = X.postMean;
   return F;
@@ -2287,7 +2302,7 @@ int rt_rebuild_accel(rt_ctx* c)
   }
   c->refN = 0;   // the reference sums start again
   B.stats = st;
-  return RT_OK;
+  return resetSeedPlane(c);   // the rebuild has written the records in a new order
 }
 
 int rt_get_rebuild_stats(rt_ctx* c, rt_rebuild_stats* out)

@@ -263,9 +263,12 @@ struct Ctx {
   uint32_t cycClosest = 0, cycAny = 0;
   RT_DEV void ClosestHit(const Ray& r) { nClosest++; const uint64_t c0 = clock64(); traceRay<false>(S, r.origin, r.direction, RT_INFINITY, seed, stack, hit, tc); cycClosest += uint32_t(clock64() - c0); }
   RT_DEV bool AnyHit(const Ray& r, float maxDist) { nAny++; RayHit h; const uint64_t c0 = clock64(); const bool f = traceRay<true>(S, r.origin, r.direction, maxDist, seed, stack, h, tc); cycAny += uint32_t(clock64() - c0); return f; }
+  RT_DEV uint32_t ClosestHitSeeded(const Ray& r, uint32_t seedTri) { nClosest++; uint32_t rec; const uint64_t c0 = clock64(); traceRaySeeded(S, r.origin, r.direction, seed, seedTri, stack, hit, rec, tc); cycClosest += uint32_t(clock64() - c0); return rec; }
 #else
   RT_DEV void ClosestHit(const Ray& r) { nClosest++; traceRay<false>(S, r.origin, r.direction, RT_INFINITY, seed, stack, hit, tc); }
   RT_DEV bool AnyHit(const Ray& r, float maxDist) { nAny++; RayHit h; return traceRay<true>(S, r.origin, r.direction, maxDist, seed, stack, h, tc); }
+  // ClosestHit of a primary ray with the record the pixel hit last frame tested first (traverse.h traceRaySeeded); returns the record of this frame's hit
+  RT_DEV uint32_t ClosestHitSeeded(const Ray& r, uint32_t seedTri) { nClosest++; uint32_t rec; traceRaySeeded(S, r.origin, r.direction, seed, seedTri, stack, hit, rec, tc); return rec; }
 #endif
 
   // ----------------------------------------------------------------------------------- gltf_material.glsl

@@ -242,12 +242,13 @@ RT_DEV void poolPublish(const WideLds& L, bool hasC, bool hasS)
   if(hasS) L.list[nC + __popcll(mS & lt)] = (unsigned char)((lane * 2 + 1) | 0x80);
   if(lane == 0) { L.ctrl[0] = uint32_t(nC + __popcll(mS)); L.ctrl[1] = 0u; L.ctrl[2] = 0u; }
 }
-// every wave of the workgroup
+// every wave of the workgroup (REC: results carry the leaf record of their hit, poolGetRec)
+template <bool REC>
 RT_DEV void groupTrace(const DevScene& S, const WideLds& L, TravCounters& tc)
 {
   __syncthreads();
   const int wave = int(threadIdx.x) >> 6;
-  tracePoolWide(S, L.pool, L.list, int(L.ctrl[0]), &L.ctrl[1], L.stacks + size_t(wave) * wideWaveStride(S.stackEntries), tc);
+  tracePoolWide<REC>(S, L.pool, L.list, int(L.ctrl[0]), &L.ctrl[1], L.stacks + size_t(wave) * wideWaveStride(S.stackEntries), tc);
   __syncthreads();
 }
 
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
 #if RT_WAVEPROF
   p1 = clock64();
 #endif
-  groupTrace(S, L, c.tc);
+  groupTrace<true>(S, L, c.tc);
 #if RT_WAVEPROF
   p2 = clock64();
 #endif
@@ -290,6 +291,9 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
   bool wantShadow = false;
   if(mine) {
     c.hit = poolGet(L.pool, lane * 2);
+    // The latency build WRITES the seed plane (DevFrame::seedOut), so that a context whose launches switch between the builds (RT_TRAVERSAL_AUTO) keeps it
+    // warm, and does not test the seed: its rays go through the workgroup pool, whose slots have no room for a seeded hit, and it never runs a full frame.
+    F.seedOut[size_t(px.y) * st.size.x + px.x] = poolGetRec(L.pool, lane * 2);
     wantShadow = directPre(c, F RT_OM_ARG, st, px, r, K, shadowRay, shadowDist);
     if(wantShadow) { c.nAny++; poolPut(L.pool, lane * 2 + 1, shadowRay.origin, shadowRay.direction, shadowDist, c.seed); }
   }
@@ -297,7 +301,7 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
 #if RT_WAVEPROF
   p3 = clock64();
 #endif
-  groupTrace(S, L, c.tc);
+  groupTrace<false>(S, L, c.tc);
 #if RT_WAVEPROF
   p4 = clock64();
 #endif
@@ -337,7 +341,13 @@ __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, D
   c.imageCoords = px;
   c.seed = tea(uint32_t(st.size.x) * uint32_t(px.y) + uint32_t(px.x), st.time);  // :279
   const Ray r = c.raySpawn(px, i2{st.size.x, st.size.y});
-  c.ClosestHit(r);
+  {  // The primary ray, seeded with the record this pixel hit last frame (DevFrame::seedIn); the record of this frame's hit is the next frame's seed, stored
+     // before the shading so that it is not live across it.  The read indexes with the 32-bit pixel number the seed hash above already holds and the write with
+     // directPre's own `index` expression, so that no address of the plane has to survive the traversal loop (a shared 64-bit index did: 8 B more scratch).
+    const uint32_t seedTri = F.seedIn ? gLoadU32(F.seedIn + (uint32_t(st.size.x) * uint32_t(px.y) + uint32_t(px.x))) : 0xffffffffu;
+    const uint32_t rec = c.ClosestHitSeeded(r, seedTri);
+    F.seedOut[size_t(px.y) * st.size.x + px.x] = rec;
+  }
   DirectCont K;
   Ray shadowRay{mk3(0.0f), mk3(0.0f)};
   float shadowDist = 0.0f;
@@ -743,7 +753,7 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
     for(;;) {
       __syncthreads();
       if(WL.ctrl[2] != 0u) break;
-      tracePoolWide(S, WL.pool, WL.list, int(WL.ctrl[0]), &WL.ctrl[1], WL.stacks + size_t(int(threadIdx.x) >> 6) * wideWaveStride(S.stackEntries), htc);
+      tracePoolWide<false>(S, WL.pool, WL.list, int(WL.ctrl[0]), &WL.ctrl[1], WL.stacks + size_t(int(threadIdx.x) >> 6) * wideWaveStride(S.stackEntries), htc);
       __syncthreads();
     }
     return;
@@ -840,9 +850,9 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
 #if RT_LAT
     poolPublish(WL, hasBounce, hasShadow);
 #if RT_WAVEPROF
-    { const uint64_t g0 = clock64(); groupTrace(S, WL, c.tc); c.cycClosest += uint32_t(clock64() - g0); c.cycAny++; }   // [3] cycles in the pool traces, [4] their number
+    { const uint64_t g0 = clock64(); groupTrace<false>(S, WL, c.tc); c.cycClosest += uint32_t(clock64() - g0); c.cycAny++; }   // [3] cycles in the pool traces, [4] their number
 #else
-    groupTrace(S, WL, c.tc);
+    groupTrace<false>(S, WL, c.tc);
 #endif
 #else
     tracePool(S, pool, hasBounce, hasShadow, c.stack, c.tc);

@@ -268,6 +268,8 @@ struct Trav {
   float tmax;      // ANY: ray tmax; closest: unused (RT_INFINITY)
   uint32_t seed;
   RayHit hit;
+  uint32_t rec;    // index into S.tris of the leaf record hit.* came from (0xffffffff: none).  Read by traceRaySeeded only: every other caller never looks
+                   // at it, so the compiler drops it from their loops
   bool found;
   bool isAny;      // MODE 2 only (rays of both kinds in one wave: tracePool)
 };
@@ -283,7 +285,7 @@ RT_DEV bool travInit(Trav& T, f3 o, f3 d, float tmax, uint32_t raySeed)
   const bool ANY = MODE == 2 ? T.isAny : MODE == 1;
   T.o = o; T.d = d; T.tmax = tmax; T.seed = raySeed; T.found = false; T.sp = 0;
   T.hit.t = ANY ? tmax : RT_INFINITY;
-  T.hit.gid = 0xffffffffu; T.hit.u = 0.f; T.hit.v = 0.f;
+  T.hit.gid = 0xffffffffu; T.hit.u = 0.f; T.hit.v = 0.f; T.rec = 0xffffffffu;
   T.ngroup = make_uint2(0u, 0u);
   T.tgroup = make_uint2(0u, 0u);
   if(hasNan(o) || hasNan(d) || !(T.hit.t > 0.0f)) return false;
@@ -454,7 +456,7 @@ RT_DEV void travTri(const DevScene& S, Trav& T, TravCounters& tc)
   tc.tris++;
   float t, u, v; uint32_t gid;
   if(!triCandidate(S, T.tgroup.x + bit, T.o, T.d, ANY, T.tmax, T.hit.t, T.hit.gid, T.seed, t, u, v, gid, tc)) return;
-  T.hit.t = t; T.hit.gid = gid; T.hit.u = u; T.hit.v = v;
+  T.hit.t = t; T.hit.gid = gid; T.hit.u = u; T.hit.v = v; T.rec = T.tgroup.x + bit;
   T.found = true;
   if(ANY) { T.tgroup.y = 0u; T.ngroup.y = 0u; T.sp = 0; }  // first accepted hit terminates the query
 }
@@ -483,7 +485,7 @@ RT_DEV void travTriCoop(const DevScene& S, Trav& T, unsigned long long triMask, 
     const float tmax = laneF(T.tmax, l);
     const bool ANY = MODE == 2 ? (laneU(T.isAny ? 1u : 0u, l) != 0u) : MODE == 1;
     float bt = laneF(T.hit.t, l), bu = 0.0f, bv = 0.0f;
-    uint32_t bg = laneU(T.hit.gid, l);
+    uint32_t bg = laneU(T.hit.gid, l), br = 0u;
     bool found = false;
     if(lane == l) tc.tris += uint32_t(__popc(tbits));
     while(tbits != 0u && !(ANY && found)) {
@@ -502,14 +504,14 @@ RT_DEV void travTriCoop(const DevScene& S, Trav& T, unsigned long long triMask, 
         const int w = __builtin_ctzll(okm);
         okm &= okm - 1ull;
         const float wt = laneF(t, w); const uint32_t wg = laneU(gid, w);
-        if(ANY || wt < bt || (wt == bt && wg < bg)) { bt = wt; bg = wg; bu = laneF(u, w); bv = laneF(v, w); found = true; }
+        if(ANY || wt < bt || (wt == bt && wg < bg)) { bt = wt; bg = wg; bu = laneF(u, w); bv = laneF(v, w); br = tbase + laneU(uint32_t(mine), w); found = true; }
         if(ANY) break;  // list order = rank order = lane order: the lowest accepted lane is the one travTri would have stopped at
       }
     }
     if(lane == l) {
       T.tgroup.y = 0u;
       if(found) {
-        T.hit.t = bt; T.hit.gid = bg; T.hit.u = bu; T.hit.v = bv; T.found = true;
+        T.hit.t = bt; T.hit.gid = bg; T.hit.u = bu; T.hit.v = bv; T.rec = br; T.found = true;
         if(ANY) { T.ngroup.y = 0u; T.sp = 0; }
       }
     }
@@ -575,6 +577,35 @@ RT_DEV bool traceRay(const DevScene& S, f3 o, f3 d, float tmax, uint32_t raySeed
   return T.found;
 }
 
+// Closest hit with a SEED: `seedTri` is the leaf record (index into S.tris) this pixel's primary ray accepted last frame, or anything else.  The record is
+// tested first, through the ordinary triCandidate, so that a camera at rest has its final t in T.hit.t before the first node step and every child group
+// farther away is culled when it would have been pushed ("Seeded primary rays").  The result is bit for bit the unseeded one: the closest hit
+// is the lexicographic minimum of (t, globalId) over the accepted candidates, acceptance is a property of (ray, triangle, seed) alone, so one more candidate
+// tested early cannot change the minimum; when the loop meets the seeded record again its `t < curT || (t == curT && gid < curG)` test rejects it and the
+// same (t, gid, u, v) bits stay.  A stale, foreign or wrong seed is a candidate that fails its test; the range guard is all that correctness needs of it.
+// `rec`: the record the returned hit came from (0xffffffff at a miss) — the next frame's seed.  seedTri is dead once the loop starts.
+RT_DEV bool traceRaySeeded(const DevScene& S, f3 o, f3 d, uint32_t raySeed, uint32_t seedTri, uint2* stack, RayHit& hit, uint32_t& rec, TravCounters& tc)
+{
+  // (the seed is tested BEFORE travInit sets up the slab-test state: the candidate test is the register peak of the call and needs none of it.  A ray that
+  //  travInit refuses — a NaN component — fails every comparison of the test as well.)
+  float st = 0.0f, su = 0.0f, sv = 0.0f; uint32_t sg = 0xffffffffu;
+  bool seeded = false;
+  if(seedTri < S.numTris) {   // one triangle step, every lane of the wave that holds a seed at once
+    tc.tris++;
+    seeded = triCandidate(S, seedTri, o, d, false, RT_INFINITY, RT_INFINITY, 0xffffffffu, raySeed, st, su, sv, sg, tc);
+  }
+  Trav T;
+  bool live = travInit<0>(T, o, d, RT_INFINITY, raySeed);
+  if(live && seeded) { T.hit.t = st; T.hit.gid = sg; T.hit.u = su; T.hit.v = sv; T.rec = seedTri; T.found = true; }
+  unsigned long long liveMask = __ballot(live ? 1 : 0);
+  while(liveMask != 0ull) {
+    live = travRoundMasked<0>(S, T, live, liveMask, stack, tc);
+    liveMask = __ballot(live ? 1 : 0);
+  }
+  hit = T.hit; rec = T.rec;
+  return T.found;
+}
+
 // ---- wave-level ray pool ---------------------------------------------------------------------------------------
 // A path vertex spawns up to two independent rays (the NEE shadow ray and the BSDF bounce ray); in a multi-bounce tile many
 // lanes are dead (path left the scene) while the live ones would trace their two rays back to back.  tracePool() lets the 64
@@ -596,6 +627,9 @@ RT_DEV RayHit poolGet(const float4* pool, int slot)
   RayHit h; h.t = r.x; h.gid = rt_f2u(r.y); h.u = r.z; h.v = r.w;
   return h;
 }
+// tracePoolWide<true> also reports the leaf record (index into S.tris) of a ray's hit, in the first word of the slot's second half — over d.y of the finished ray
+RT_DEV void poolPutRec(float4* pool, int slot, uint32_t rec) { reinterpret_cast<uint32_t*>(pool + slot * POOL_SLOT_F4 + 1)[0] = rec; }
+RT_DEV uint32_t poolGetRec(const float4* pool, int slot) { return reinterpret_cast<const uint32_t*>(pool + slot * POOL_SLOT_F4 + 1)[0]; }
 RT_DEV void waveLdsSync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 // Every lane of the wave must call this (uniform control flow).  hasC / hasS: this lane parked a closest-hit / any-hit ray.
@@ -718,12 +752,12 @@ RT_DEV uint32_t groupOr(uint32_t v)
   v |= dppU<RT_DPP_HALF_MIRROR>(v);
   return v;
 }
-struct WideCand { float t; uint32_t gid; float u, v; };   // t = +inf (IEEE): no candidate
+struct WideCand { float t; uint32_t gid; float u, v; uint32_t rec; };   // t = +inf (IEEE): no candidate; rec: the candidate's leaf record (dropped by the compiler where Trav::rec is not read)
 template <int CTRL> RT_DEV void candMinStep(WideCand& c)
 {
-  const float ot = dppF<CTRL>(c.t); const uint32_t og = dppU<CTRL>(c.gid); const float ou = dppF<CTRL>(c.u), ov = dppF<CTRL>(c.v);
+  const float ot = dppF<CTRL>(c.t); const uint32_t og = dppU<CTRL>(c.gid); const float ou = dppF<CTRL>(c.u), ov = dppF<CTRL>(c.v); const uint32_t orc = dppU<CTRL>(c.rec);
   const bool take = ot < c.t || (ot == c.t && og < c.gid);
-  c.t = take ? ot : c.t; c.gid = take ? og : c.gid; c.u = take ? ou : c.u; c.v = take ? ov : c.v;
+  c.t = take ? ot : c.t; c.gid = take ? og : c.gid; c.u = take ? ou : c.u; c.v = take ? ov : c.v; c.rec = take ? orc : c.rec;
 }
 // lexicographic minimum of (t, gid) over the group, with its (u, v)
 RT_DEV void groupMinCand(WideCand& c) { candMinStep<RT_DPP_XOR1>(c); candMinStep<RT_DPP_XOR2>(c); candMinStep<RT_DPP_HALF_MIRROR>(c); }
@@ -786,7 +820,7 @@ RT_DEV void travTriW(const DevScene& S, Trav& T, int j, TravCounters& tc)
     }
   }
   T.tgroup.y = rem;
-  WideCand c; c.t = __builtin_huge_valf(); c.gid = 0xffffffffu; c.u = 0.0f; c.v = 0.0f;
+  WideCand c; c.t = __builtin_huge_valf(); c.gid = 0xffffffffu; c.u = 0.0f; c.v = 0.0f; c.rec = 0xffffffffu;
   bool ok = false;
 #if RT_WAVEPROF
 #define RT_PH(k) { __builtin_amdgcn_s_waitcnt(0); const uint64_t pn = clock64(); tc.ph[k] += uint32_t(pn - pc); pc = pn; }
@@ -814,14 +848,14 @@ RT_DEV void travTriW(const DevScene& S, Trav& T, int j, TravCounters& tc)
       ok = alphaFinish(A, Fh, a00, a10, a01, a11, gid, T.seed);
       RT_PH(4) // filter + draw
     }
-    if(ok) { c.t = t; c.gid = gid; c.u = u; c.v = v; }
+    if(ok) { c.t = t; c.gid = gid; c.u = u; c.v = v; c.rec = ti; }
   }
   // (all eight lanes of the group are back together here)
   RT_PH(5)
   groupMinCand(c);
   const bool any = c.t < __builtin_huge_valf();   // an accepted candidate has a finite t
   if(any && (ANY || c.t < T.hit.t || (c.t == T.hit.t && c.gid < T.hit.gid))) {
-    T.hit.t = c.t; T.hit.gid = c.gid; T.hit.u = c.u; T.hit.v = c.v;
+    T.hit.t = c.t; T.hit.gid = c.gid; T.hit.u = c.u; T.hit.v = c.v; T.rec = c.rec;
     T.found = true;
     if(ANY) { T.tgroup.y = 0u; T.ngroup.y = 0u; T.sp = 0; }
   }
@@ -868,7 +902,7 @@ RT_DEV bool travRoundW(const DevScene& S, Trav& T, bool live, int j, uint2* stac
 // LDS mailbox (minimum over (t, id); any-hit: any accepted).  A round then advances a ray by up to eight nodes instead of one.  Verdicts are functions of
 // (ray, triangle), the closest hit a minimum over (t, id), boxes are only culled against hits already found: the result does not depend on the order the
 // nodes are visited in, so the frame is bit-identical with and without (tests: every latency-build parity case).  S.gangMax = 0 switches it off.
-constexpr int GANG_BOX_UINT2 = 16;   // per wave, behind its stacks: 8 x float4 mailbox
+constexpr int GANG_BOX_UINT2 = 20;   // per wave, behind its stacks: 8 x float4 mailbox, then 8 x u32 for the hits' leaf records (gangTail<true>)
 constexpr int GANG_SCAN = 2;         // stack entries a round looks at for pending children
 constexpr int GANG_EXTRA = 20;       // stack entries per ray on top of the tree's own bound: the room parallel expansion may use
 RT_DEV uint32_t leaderBits(unsigned long long m) { return uint32_t(((m & 0x0101010101010101ull) * 0x0102040810204080ull) >> 56); }   // lanes 0, 8, .., 56 -> bits 0..7
@@ -883,10 +917,13 @@ RT_DEV uint32_t dropTopBits(uint32_t v, int n) { for(int k = 0; k < n; k++) v &=
 // Stack space: a ray's column holds S.stackEntries = S.stackTotal + GANG_EXTRA entries in the latency build.  Several children are expanded per round only while
 // the column has more than S.stackTotal entries to spare; beyond that one child per round is taken — plain depth-first order, which from any state needs at most
 // the tree's depth (< S.stackTotal) more entries — so the column cannot overflow.
+// REC: the leaf record of a ray's hit travels with the hit (adoption, mailbox, result slot): tracePoolWide<true>.
+template <bool REC>
 RT_DEV void gangTail(const DevScene& S, float4* pool, uint2* waveStack, Trav& T, bool& live, int mySlot, TravCounters& tc)
 {
   const int lane = int(threadIdx.x) & 63, j = lane & (WIDE_G - 1), g = lane >> 3;
   float4* gbox = reinterpret_cast<float4*>(waveStack + size_t(S.stackEntries) * WIDE_RAYS);
+  uint32_t* rbox = reinterpret_cast<uint32_t*>(gbox + WIDE_RAYS);
   const int wideRoom = S.stackEntries - S.stackTotal;   // parallel expansion while sp + taken <= wideRoom
   bool working = false;          // this group works on a ray (its own or an adopted one)
   int og = g;                    // owner group of that ray = its stack column
@@ -919,12 +956,13 @@ RT_DEV void gangTail(const DevScene& S, float4* pool, uint2* waveStack, Trav& T,
       const float bt = __shfl(T.hit.t, src), bu = __shfl(T.hit.u, src), bv = __shfl(T.hit.v, src);
       const uint32_t bg = uint32_t(__shfl(int(T.hit.gid), src));
       const int any = __shfl(T.isAny ? 1 : 0, src);
+      const uint32_t brc = REC ? uint32_t(__shfl(int(T.rec), src)) : 0xffffffffu;
       if(adopt) {
         const float4 a = pool[slot * POOL_SLOT_F4], b = pool[slot * POOL_SLOT_F4 + 1];
         T.isAny = any != 0;
         (void)travInit<2>(T, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), b.z, rt_f2u(b.w));
         T.ngroup.y = 0u; T.tgroup.y = 0u;
-        T.sp = sp; T.hit.t = bt; T.hit.gid = bg; T.hit.u = bu; T.hit.v = bv;
+        T.sp = sp; T.hit.t = bt; T.hit.gid = bg; T.hit.u = bu; T.hit.v = bv; T.rec = brc;
       }
       working = true;
       wm = 0u;
@@ -936,14 +974,14 @@ RT_DEV void gangTail(const DevScene& S, float4* pool, uint2* waveStack, Trav& T,
     const bool hasTri = working && T.tgroup.y != 0u;
     if(__ballot(hasTri ? 1 : 0) != 0ull) {
       if(hasTri) travTriW<2>(S, T, j, tc);
-      if(j == 0) gbox[g] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
+      if(j == 0) { gbox[g] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v); if(REC) rbox[g] = T.rec; }
       waveLdsSync();
       uint32_t rest = wm & ~(1u << g);
       while(rest != 0u) {   // merge: the workers of a ray end up with the same best hit
         const int k = __ffs(int(rest)) - 1; rest &= rest - 1u;
         const float4 c = gbox[k];
         const uint32_t cg = rt_f2u(c.y);
-        if(cg != 0xffffffffu && (T.hit.gid == 0xffffffffu || (!T.isAny && (c.x < T.hit.t || (c.x == T.hit.t && cg < T.hit.gid))))) { T.hit.t = c.x; T.hit.gid = cg; T.hit.u = c.z; T.hit.v = c.w; }
+        if(cg != 0xffffffffu && (T.hit.gid == 0xffffffffu || (!T.isAny && (c.x < T.hit.t || (c.x == T.hit.t && cg < T.hit.gid))))) { T.hit.t = c.x; T.hit.gid = cg; T.hit.u = c.z; T.hit.v = c.w; if(REC) T.rec = rbox[k]; }
       }
       if(T.isAny && T.hit.gid != 0xffffffffu) { T.sp = 0; T.tgroup.y = 0u; T.ngroup.y = 0u; }   // first accepted hit terminates the query, for every worker
       waveLdsSync();
@@ -1003,7 +1041,7 @@ RT_DEV void gangTail(const DevScene& S, float4* pool, uint2* waveStack, Trav& T,
     // ---- finished rays: the owner publishes the result, its workers are free for the next assignment -------------------------------------------------------
     const uint32_t busyM = leaderBits(__ballot((working && (T.tgroup.y != 0u || T.sp > 0)) ? 1 : 0)) & wm;
     if(working && busyM == 0u) {
-      if(live) { if(j == 0) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v); live = false; }
+      if(live) { if(j == 0) { pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v); if(REC) poolPutRec(pool, mySlot, T.rec); } live = false; }
       working = false;
     }
   }
@@ -1012,6 +1050,8 @@ RT_DEV void gangTail(const DevScene& S, float4* pool, uint2* waveStack, Trav& T,
 // ---- workgroup-wide ray pool ------------------------------------------------------------------------------------------------------------------------
 // Rays wait in LDS slots (poolPut: ray in, hit out, 32 B), `list` holds the n occupied slot ids (kind of the ray in bit 7: any-hit), *next is the shared cursor.
 // EVERY wave of the workgroup calls this between two workgroup barriers; a wave serves up to eight rays at a time and refills group by group.
+// REC: every result also carries the leaf record of its hit (poolGetRec) — the primary rays of the latency build's direct stage, whose records seed the next frame.
+template <bool REC>
 RT_DEV void tracePoolWide(const DevScene& S, float4* pool, const unsigned char* list, int n, uint32_t* next, uint2* waveStack, TravCounters& tc)
 {
   const int lane = int(threadIdx.x) & 63, j = lane & (WIDE_G - 1), r = lane >> 3;
@@ -1037,7 +1077,7 @@ RT_DEV void tracePoolWide(const DevScene& S, float4* pool, const unsigned char* 
         const float4 a = pool[mySlot * POOL_SLOT_F4], b = pool[mySlot * POOL_SLOT_F4 + 1];
         T.isAny = (e & 0x80u) != 0u;
         live = travInit<2>(T, mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y), b.z, rt_f2u(b.w));
-        if(!live && j == 0) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
+        if(!live && j == 0) { pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v); if(REC) poolPutRec(pool, mySlot, T.rec); }
       }
       if(int(base) + nIdle >= n) exhausted = true;
       liveMask = __ballot(live ? 1 : 0);
@@ -1047,7 +1087,7 @@ RT_DEV void tracePoolWide(const DevScene& S, float4* pool, const unsigned char* 
       continue;
     }
     if(exhausted && S.gangMax > 0 && __popcll(liveMask & leaders) <= S.gangMax && __popcll(liveMask & leaders) < WIDE_RAYS) {   // the tail: idle slots become workers of the live rays
-      gangTail(S, pool, waveStack, T, live, mySlot, tc);
+      gangTail<REC>(S, pool, waveStack, T, live, mySlot, tc);
       break;
     }
 #if RT_WAVEPROF
@@ -1059,7 +1099,7 @@ RT_DEV void tracePoolWide(const DevScene& S, float4* pool, const unsigned char* 
 #if RT_WAVEPROF
     { const uint32_t dc = uint32_t(clock64() - pc0); if(anyTri) { tc.rT++; tc.cT += dc; } else { tc.rN++; tc.cN += dc; } }
 #endif
-    if(live && !still && j == 0) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
+    if(live && !still && j == 0) { pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v); if(REC) poolPutRec(pool, mySlot, T.rec); }
     live = still;
   }
 }
