@@ -154,6 +154,21 @@ SKIN_INFLUENCE_DT = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
 VERTEX_DT = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("texcoord", "<f4", 2), ("tangent", "<u4"), ("color", "<u4")])
 
 
+class LightStats(C.Structure):  # rt_light_stats, 32 B
+    _fields_ = [("bound", C.c_uint32), ("rewritten", C.c_uint32), ("lightBytesCopied", C.c_uint32), ("ms", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+# rt_set_light_sources / rt_lights_readback: rt_light_source (8 B), rt_trig_light (96 B) and rt_punc_light (80 B) as numpy rows
+LIGHTS_TRIG, LIGHTS_PUNC = range(2)
+LIGHT_SOURCE_DT = np.dtype([("instance", "<u4"), ("triangle", "<u4")])
+_IMPT_SAMP_DT = np.dtype([("alias", "<i4"), ("q", "<f4"), ("pdf", "<f4"), ("aliasPdf", "<f4")])
+TRIG_LIGHT_DT = np.dtype([("matIndex", "<u4"), ("transformIndex", "<u4"), ("v0", "<f4", 3), ("v1", "<f4", 3), ("v2", "<f4", 3),
+                          ("uv0", "<f4", 2), ("uv1", "<f4", 2), ("uv2", "<f4", 2), ("impSamp", _IMPT_SAMP_DT), ("pad", "<f4", 3)])
+PUNC_LIGHT_DT = np.dtype([("type", "<i4"), ("direction", "<f4", 3), ("intensity", "<f4"), ("color", "<f4", 3), ("position", "<f4", 3), ("range", "<f4"),
+                          ("outerConeCos", "<f4"), ("innerConeCos", "<f4"), ("padding", "<f4", 2), ("impSamp", _IMPT_SAMP_DT)])
+assert LIGHT_SOURCE_DT.itemsize == 8 and TRIG_LIGHT_DT.itemsize == 96 and PUNC_LIGHT_DT.itemsize == 80 and C.sizeof(LightStats) == 32
+
+
 class RefitStats(C.Structure):  # rt_refit_stats, 32 B
     _fields_ = [("instances", C.c_uint32), ("leafRecords", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("fullRefit", C.c_uint32),
                 ("ms", C.c_float), ("triPad", C.c_float), ("treePad", C.c_float)]

@@ -27,6 +27,7 @@
 #include "refit.h"
 #include "accel_build.h"
 #include "deform.h"
+#include "light_records.h"
 #include "dev_math.h"
 
 using namespace rt;
@@ -159,6 +160,16 @@ struct rt_ctx {
   } deform;
   std::vector<void*> skinAllocs, deformAllocs;
   hipEvent_t evDeform[2] = {nullptr, nullptr};   // start / end of the skinning kernel and its commit copy
+  // rt_set_light_sources (csrc/light_records.hip).  The binding (one source per triangle-light record), the scratch records of the bind-time check
+  // and the counter live in lightAllocs: replaced by rt_set_light_sources, dropped by rt_upload_scene.  The context keeps no host copy of the light records.
+  struct Lights {
+    uint32_t bound = 0;                          // records that have a source (0: no binding)
+    rt_light_source* dSources = nullptr;
+    uint32_t* dCounter = nullptr;
+    rt_light_stats stats{};
+  } lights;
+  std::vector<void*> lightAllocs;
+  hipEvent_t evLights[2] = {nullptr, nullptr};   // start / end of the light kernel of the last update (created by the first binding)
   // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
   // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
   int objMotion = RT_OBJECT_MOTION_OFF;
@@ -501,7 +512,7 @@ int rt_destroy(rt_ctx* c)
   (void)hipSetDevice(c->device);
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
-  freePool(c->skinAllocs); freePool(c->deformAllocs);
+  freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
@@ -525,6 +536,7 @@ int rt_destroy(rt_ctx* c)
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
   for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evDeform) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evLights) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
@@ -598,6 +610,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   LoadTimer lt;
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->rebuildAllocs);
   freePool(c->skinAllocs); freePool(c->deformAllocs);   // a new scene has no skins
+  freePool(c->lightAllocs);   // ... and no light-source binding
+  c->lights = rt_ctx::Lights{};
   c->deform = rt_ctx::Deform{};
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
@@ -2128,8 +2142,27 @@ static int refitTail(rt_ctx* c, const std::vector<uint8_t>& dirty)
     for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
     RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
   }
+  // bound triangle-light records of the refitted instances follow them (csrc/light_records.hip): the instance rows and the vertices are in place on this stream
+  rt_ctx::Lights& L = c->lights;
+  uint32_t lightsRewritten = 0;
+  if(L.bound) {
+    RT_HIP(c, hipMemsetAsync(L.dCounter, 0, 4, s));
+    RT_HIP(c, hipEventRecord(c->evLights[0], s));
+    if(count > 0) {
+      LightRecArgs la{};
+      la.records = const_cast<rt_trig_light*>(c->ds.trigLights); la.sources = L.dSources; la.instances = c->ds.instances; la.primMeshes = c->ds.primMeshes;
+      la.vertices = c->ds.vertices; la.indices = c->ds.indices; la.dirtyBits = R.dDirty; la.counter = L.dCounter; la.numRecs = L.bound; la.all = 0u;
+      RT_HIP(c, launchLightRecords(s, la));
+    }
+    RT_HIP(c, hipEventRecord(c->evLights[1], s));
+    RT_HIP(c, hipMemcpyAsync(&lightsRewritten, L.dCounter, 4, hipMemcpyDeviceToHost, s));
+  }
   RT_HIP(c, hipEventRecord(c->evRefit[1], s));
   RT_HIP(c, hipStreamSynchronize(s));
+  if(L.bound) {
+    L.stats.rewritten = lightsRewritten; L.stats.lightBytesCopied = 0u; L.stats.ms = 0.f;
+    (void)hipEventElapsedTime(&L.stats.ms, c->evLights[0], c->evLights[1]);
+  }
   c->ds.triPad = triPad;
   c->refN = 0;   // the scene changed: the reference sums start again
   R.stats = rt_refit_stats{};
@@ -2212,6 +2245,8 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
   if(numPunc) RT_HIP(c, hipMemcpy(const_cast<rt_punc_light*>(c->ds.puncLights), punc, numPunc * sizeof(rt_punc_light), hipMemcpyHostToDevice));
   c->ds.lightInfo.trigSampProb = info->trigSampProb;
   c->refN = 0;
+  c->lights.stats.rewritten = 0u; c->lights.stats.ms = 0.f;   // the binding stays in place
+  c->lights.stats.lightBytesCopied = uint32_t(numTrig * sizeof(rt_trig_light) + numPunc * sizeof(rt_punc_light));
   return RT_OK;
 }
 
@@ -2480,7 +2515,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
       }
     }
     const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-    if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer)
+    if(c->lights.bound == 0 && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer); with a binding the refit tail rewrites the records
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
     restFirst[k] = uint32_t(totalVerts);
     totalVerts += pm.vertexCount; totalJoints += sk.jointCount;
@@ -2572,6 +2607,111 @@ int rt_get_deform_stats(rt_ctx* c, rt_deform_stats* out)
 {
   if(!c || !out) return RT_ERR_INVALID_ARG;
   *out = c->deform.stats;
+  return RT_OK;
+}
+
+/* ---- light sources: triangle-light records that follow the instances the refit tail refits (include/rt_abi.h "Light sources", csrc/light_records.hip) ---- */
+int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sources)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_light_sources: no scene uploaded");
+  rt_ctx::Lights& L = c->lights;
+  if(numTrig == 0) {
+    for(const rt_skin& sk : c->deform.skins) {
+      const rt_prim_mesh& pm = c->primMeshes[sk.primMesh];
+      const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
+      if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
+        return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a skin on an emissive prim mesh needs the binding (remove the skin first)");
+    }
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    freePool(c->lightAllocs);
+    L = rt_ctx::Lights{};
+    return RT_OK;
+  }
+  if(numTrig != c->ds.lightInfo.trigLightSize) return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: numTrig must equal the uploaded trigLightSize");
+  if(!sources) return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: NULL sources");
+  const size_t nInst = c->instances.size();
+  for(uint32_t k = 0; k < numTrig; k++) {
+    if(sources[k].instance >= nInst) return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: instance index out of range");
+    if(sources[k].triangle >= c->primMeshes[c->instances[sources[k].instance].primMesh].indexCount / 3u)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: triangle beyond the prim mesh's index list");
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  std::vector<rt_trig_light> recs(numTrig), eval(numTrig);
+  RT_HIP(c, hipMemcpy(recs.data(), c->ds.trigLights, size_t(numTrig) * sizeof(rt_trig_light), hipMemcpyDeviceToHost));
+  for(uint32_t k = 0; k < numTrig; k++)
+    if(recs[k].matIndex != uint32_t(c->primMeshes[c->instances[sources[k].instance].primMesh].materialIndex))
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a record's matIndex differs from its prim mesh's materialIndex");
+  // The binding must describe the records: the update kernel, for all records, into a scratch array; v0 v1 v2 must come out bit for bit.  Nothing of the context
+  // changes before that holds: the candidate lives in a pool of its own.
+  std::vector<void*> fresh, temp;
+  const rt_light_source* dSrc = nullptr;
+  rt_trig_light* dScratch = nullptr;
+  uint32_t* dCounter = nullptr;
+  const DevInstance* dInst = c->haveAccel ? c->ds.instances : nullptr;
+  int rc = upload(c, fresh, sources, size_t(numTrig), &dSrc);
+  if(!rc) rc = allocZeroed(c, fresh, 1, &dCounter);
+  if(!rc) rc = allocZeroed(c, temp, size_t(numTrig), &dScratch);
+  if(!rc && !dInst) {   // before rt_build_accel there are no device instance rows: the kernel reads objectToWorld and primMesh of a row
+    std::vector<DevInstance> rows(std::max<size_t>(nInst, 1), DevInstance{});
+    for(size_t i = 0; i < nInst; i++) { memcpy(rows[i].o2w, c->instances[i].objectToWorld, sizeof(rows[i].o2w)); rows[i].primMesh = c->instances[i].primMesh; }
+    rc = upload(c, temp, rows.data(), rows.size(), &dInst);
+  }
+  hipError_t he = hipSuccess;
+  if(!rc) {
+    LightRecArgs la{};
+    la.records = dScratch; la.sources = dSrc; la.instances = dInst; la.primMeshes = c->ds.primMeshes; la.vertices = c->ds.vertices; la.indices = c->ds.indices;
+    la.dirtyBits = nullptr; la.counter = dCounter; la.numRecs = numTrig; la.all = 1u;
+    he = launchLightRecords(c->stream, la);
+    if(he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if(he == hipSuccess) he = hipMemcpy(eval.data(), dScratch, size_t(numTrig) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
+    for(hipEvent_t& e : c->evLights) if(he == hipSuccess && !e) he = hipEventCreate(&e);
+  }
+  freePool(temp);
+  if(rc || he != hipSuccess) {
+    freePool(fresh);
+    if(rc) return rc;
+    c->err = std::string("rt_set_light_sources: ") + hipGetErrorString(he);
+    return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+  }
+  for(uint32_t k = 0; k < numTrig; k++)
+    if(memcmp(&recs[k].v0, &eval[k].v0, 3 * sizeof(rt_vec3)) != 0) {
+      freePool(fresh);
+      c->err = "rt_set_light_sources: record " + std::to_string(k) + " does not hold the positions of triangle " + std::to_string(sources[k].triangle) +
+               " of instance " + std::to_string(sources[k].instance) + " (stale records: rt_update_lights first)";
+      return RT_ERR_INVALID_ARG;
+    }
+  freePool(c->lightAllocs);
+  c->lightAllocs = fresh;
+  L = rt_ctx::Lights{};
+  L.bound = numTrig; L.dSources = const_cast<rt_light_source*>(dSrc); L.dCounter = dCounter;
+  L.stats.bound = numTrig;
+  return RT_OK;
+}
+
+int rt_lights_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_lights_readback: no scene uploaded");
+  const void* src = nullptr; size_t want = 0;
+  switch(which) {
+    case RT_LIGHTS_TRIG: src = c->ds.trigLights; want = size_t(c->ds.lightInfo.trigLightSize) * sizeof(rt_trig_light); break;
+    case RT_LIGHTS_PUNC: src = c->ds.puncLights; want = size_t(c->ds.lightInfo.puncLightSize) * sizeof(rt_punc_light); break;
+    default: return fail(c, RT_ERR_INVALID_ARG, "rt_lights_readback: which must be RT_LIGHTS_TRIG / _PUNC");
+  }
+  if(bytes != want || (want && !dst)) return fail(c, RT_ERR_INVALID_ARG, "rt_lights_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(want) RT_HIP(c, hipMemcpy(dst, src, want, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_get_light_stats(rt_ctx* c, rt_light_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->lights.stats;
   return RT_OK;
 }
 

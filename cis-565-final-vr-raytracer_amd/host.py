@@ -22,6 +22,7 @@ def host_lib():
         L.rth_env_create.restype = C.c_void_p
         L.rth_env_integral.restype = C.c_float
         L.rth_env_average.restype = C.c_float
+        L.rth_scene_light_sources.restype = C.c_uint32
         for name, args in {
             "rth_scene_destroy": [C.c_void_p], "rth_scene_load": [C.c_void_p, C.c_char_p],
             "rth_scene_make_procedural": [C.c_void_p, C.c_int, C.c_float, C.c_uint32], "rth_scene_save_gltf": [C.c_void_p, C.c_char_p], "rth_decode_jpeg": [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t],
@@ -31,6 +32,7 @@ def host_lib():
             "rth_scene_get_camera": [C.c_void_p, C.c_void_p], "rth_scene_light_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_scene_update_instances": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+            "rth_scene_light_sources": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_env_destroy": [C.c_void_p], "rth_env_load": [C.c_void_p, C.c_char_p], "rth_env_set": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
             "rth_env_make_sky": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint32], "rth_env_integral": [C.c_void_p], "rth_env_average": [C.c_void_p],
@@ -121,6 +123,14 @@ class Scene:
         assert rows.size % 32 == 0
         if host_lib().rth_scene_update_vertices(self._h, int(prim_mesh), int(first), rows.size // 32, rows.ctypes.data) != 0:
             raise ValueError("Scene.updateVertices: prim mesh or vertex range out of bounds")
+    def lightSources(self):
+        """Scene::lightSources: the (instance, triangle) every triangle-light record came from, in record order (abi.LIGHT_SOURCE_DT rows): what
+        Renderer.set_light_sources takes"""
+        n = host_lib().rth_scene_light_sources(self._h, None, 0)
+        out = np.zeros(n, dtype=abi.LIGHT_SOURCE_DT)
+        if n:
+            host_lib().rth_scene_light_sources(self._h, out.ctypes.data, n)
+        return out
     def desc(self, env=None):
         d = abi.SceneDesc()
         host_lib().rth_scene_desc(self._h, env._h if env is not None else None, C.byref(d))

@@ -1,6 +1,8 @@
 // host_capi.cpp — plain-C handles over Scene / HdrSampling for the Python tests, bench.py and smoke().
 #include "scene.hpp"
 #include "alias_table.hpp"
+#include <algorithm>
+#include <cstring>
 #include <new>
 
 using namespace rth;
@@ -75,6 +77,16 @@ int rth_scene_update_instances(void* s, const uint32_t* ids, const float* transf
 int rth_scene_update_vertices(void* s, uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows)
 {
   return static_cast<Scene*>(s)->updateVertices(primMesh, first, count, rows) ? 0 : -1;
+}
+// Scene::lightSources: returns the number of sources; copies min(cap, number) {instance, triangle} pairs into out (out may be NULL with cap 0: the count alone)
+uint32_t rth_scene_light_sources(void* s, rt_light_source* out, uint32_t cap)
+{
+  try {
+    const std::vector<rt_light_source> v = static_cast<Scene*>(s)->lightSources();
+    const size_t n = std::min<size_t>(v.size(), cap);
+    if(out && n) memcpy(out, v.data(), n * sizeof(rt_light_source));
+    return uint32_t(v.size());
+  } catch(...) { return 0u; }
 }
 void rth_scene_desc(void* s, void* env, rt_scene_desc* out) { *out = static_cast<Scene*>(s)->getDesc(static_cast<HdrSampling*>(env)); }
 

@@ -19,6 +19,13 @@ class AccelStructure {
   {
     rt_scene_desc d = scene.getDesc(env);
     if(rt_upload_scene(m_ctx, &d) != RT_OK || rt_build_accel(m_ctx) != RT_OK) { fprintf(stderr, "AccelStructure::create: %s\n", rt_last_error(m_ctx)); return false; }
+    // the scene knows which triangle every triangle-light record came from (include/rt_abi.h "Light sources"): bound here, the update calls move the emitters'
+    // records with the geometry on the GPU, and skins on emissive meshes are accepted
+    const std::vector<rt_light_source> src = scene.lightSources();
+    if(d.trigLights && !src.empty() && rt_set_light_sources(m_ctx, uint32_t(src.size()), src.data()) != RT_OK) {
+      fprintf(stderr, "AccelStructure::create: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
     return true;
   }
   // Move instances without a rebuild (include/rt_abi.h "Moving instances"): ids + count x 12 floats (3 x 4 row-major).  The reference rebuilds its TLAS per frame

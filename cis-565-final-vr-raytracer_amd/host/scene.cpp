@@ -235,6 +235,20 @@ void Scene::createTrigLightBuffer()  // scene.cpp:355-409 + createTrigLightImptS
   m_lightBufInfo.trigLightSize = uint32_t(m_trigLights.size());
 }
 
+std::vector<rt_light_source> Scene::lightSources() const
+{
+  const GltfScene& g = m_gltf;
+  std::vector<rt_light_source> out;
+  for(size_t n = 0; n < g.nodes.size(); n++) {   // the loops and the light rule of createTrigLightBuffer
+    const GltfPrimMesh& pm = g.primMeshes[g.nodes[n].primMesh];
+    const GltfMaterial& mat = g.materials[size_t(std::max(0, pm.materialIndex))];
+    if(luminance(mat.emissiveFactor) > 1e-2f)
+      for(uint32_t idx = pm.firstIndex; idx + 1 < pm.firstIndex + pm.indexCount; idx += 3)  // (quirk 11)
+        out.push_back(rt_light_source{uint32_t(n), (idx - pm.firstIndex) / 3u});
+  }
+  return out;
+}
+
 void Scene::updateCamera(int width, int height)  // scene.cpp:777-795
 {
   const float aspect = float(width) / float(height);

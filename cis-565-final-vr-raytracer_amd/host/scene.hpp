@@ -93,6 +93,10 @@ class Scene {
   // positions in the loader's arrays, and the triangle-light records are recomputed as by updateInstances, so a deformed emitter lights from its new shape
   // (rt_update_vertices takes the same rows, rt_update_lights the records from getDesc()).  False (nothing changed) for a mesh or a range out of bounds.
   bool updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows);
+  // The source of every triangle-light record, in the order createTrigLightBuffer emits them (include/rt_abi.h "Light sources"): record k is triangle
+  // sources[k].triangle (index-list position / 3, relative to the prim mesh) of node = instance sources[k].instance.  rt_set_light_sources takes the list; the
+  // update calls then move the records with the geometry on the device, and updateInstances / updateVertices + rt_update_lights are no longer needed for emitters.
+  std::vector<rt_light_source> lightSources() const;
 
   float m_puncLightWeight = 0.f, m_trigLightWeight = 0.f;  // scene.hpp:79-80
   rt_light_buf_info m_lightBufInfo{};                      // scene.hpp:113 (zero-initialised here: quirk 10)

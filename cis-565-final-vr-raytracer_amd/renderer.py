@@ -24,6 +24,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
+               "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -135,6 +136,10 @@ def hip_lib():
             L.rt_update_skins.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rt_vertices_readback.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
             L.rt_get_deform_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_light_sources"):   # light sources (absent from older A/B libraries)
+            L.rt_set_light_sources.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+            L.rt_lights_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.rt_get_light_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -483,6 +488,26 @@ class Renderer:
     def deform_stats(self):
         s = abi.DeformStats()
         self._chk(hip_lib().rt_get_deform_stats(self._h, C.byref(s)), "rt_get_deform_stats")
+        return s
+
+    # ---- light sources (include/rt_abi.h "Light sources")
+    def set_light_sources(self, sources):
+        """rt_set_light_sources: sources = abi.LIGHT_SOURCE_DT records, one per uploaded triangle-light record (host.Scene.lightSources()); the update calls then
+        rewrite the records of the instances they refit on the GPU.  Empty: removes the binding"""
+        src = np.ascontiguousarray(sources, dtype=abi.LIGHT_SOURCE_DT).reshape(-1)
+        self._chk(hip_lib().rt_set_light_sources(self._h, src.size, src.ctypes.data), "rt_set_light_sources")
+
+    def lights_readback(self, which=abi.LIGHTS_TRIG, count=None):
+        """the device light array as it is now: abi.TRIG_LIGHT_DT (96 B) or abi.PUNC_LIGHT_DT (80 B) records; count defaults to the bound record count"""
+        if count is None:
+            count = self.light_stats().bound
+        out = np.zeros(int(count), dtype=abi.TRIG_LIGHT_DT if which == abi.LIGHTS_TRIG else abi.PUNC_LIGHT_DT)
+        self._chk(hip_lib().rt_lights_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_lights_readback")
+        return out
+
+    def light_stats(self):
+        s = abi.LightStats()
+        self._chk(hip_lib().rt_get_light_stats(self._h, C.byref(s)), "rt_get_light_stats")
         return s
 
     # ---- object motion vectors (include/rt_abi.h "Object motion vectors", DESIGN.md §20)

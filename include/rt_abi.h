@@ -693,7 +693,7 @@ int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases
  *   Ordering: v1 drains the pipeline — the call joins the frames in flight, runs its kernels on the context's main stream and returns after they completed.
  *   Scope: the single-GPU context only.  rt_mgpu_* contexts and the row-tiled hosts (restir_amd/tiled.py) have no update path: they upload the moved scene.
  * rt_update_lights: overwrites the device light arrays in place, for a host that moved an emissive instance (its Scene recomputes the triangle-light records; without
- *   this call a moved emitter keeps lighting from its old place).  numTrig / numPunc and info's sizes must equal the uploaded counts, and the records pass the index
+ *   this call a moved emitter keeps lighting from its old place, unless rt_set_light_sources has bound the records to their triangles).  numTrig / numPunc and info's sizes must equal the uploaded counts, and the records pass the index
  *   checks of rt_upload_scene, else RT_ERR_INVALID_ARG and nothing changes.  info->trigSampProb replaces the uploaded one.  Resets the reference-mode sums; drains the pipeline.
  * rt_get_refit_stats: what the last rt_update_instances did.
  * rt_accel_readback: the device tree as it is now, for tests and diagnostics: RT_ACCEL_NODES (80 B per node, rt_accel_stats' node count), RT_ACCEL_TRIS (64 B per
@@ -805,14 +805,16 @@ int rt_object_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
  *   whose bits differ from the uploaded row (the alpha records and opacity micro-maps were derived from it, and the tangent's handedness bit lives there) or a mesh
  *   that has a skin refuses the WHOLE call with RT_ERR_INVALID_ARG and changes nothing.  Position, normal, tangent and colour may change.  count == 0 is a valid call
  *   that changes no vertex.  The rows also replace the context's copy of the scene (a later rt_build_accel builds the deformed scene).
- *   Emitters: the triangle-light records hold world positions; a host that deforms an emissive mesh recomputes them and calls rt_update_lights.
+ *   Emitters: the triangle-light records hold world positions; a host that deforms an emissive mesh recomputes them and calls rt_update_lights, or binds the
+ *   records to their triangles once (rt_set_light_sources, "Light sources" below): the call then rewrites them on the device.
  * rt_set_skins(ctx, numSkins, skins, numInfluences, influences): valid after rt_upload_scene.  Replaces all skins (numSkins == 0 removes them).  Skin k poses prim
  *   mesh skins[k].primMesh with jointCount matrices; its vertex v has the influence row influences[firstInfluence + v] (vertexCount rows).  The call captures the rest
  *   pose — the context's current rows of those meshes — into a device buffer of its own and allocates a staging range of the same size for the posed rows.
  *   RT_ERR_INVALID_ARG, nothing changed, for: a prim mesh out of range or listed twice; jointCount == 0 or > 65536; an influence range that lies outside the array
  *   (it is vertexCount rows long); a joint index >= jointCount; a non-finite weight; a mesh whose material is emissive by the scene's light rule (luminance of
- *   emissiveFactor > 1e-2): its triangle-light records hold world positions the host could no longer supply.  That is a limit of this version; host-deformed
- *   emitters go through rt_update_vertices + rt_update_lights.  rt_upload_scene drops the skins; rt_build_accel and rt_rebuild_accel keep them.
+ *   emissiveFactor > 1e-2) while no light-source binding is set: its triangle-light records hold world positions the host could no longer supply.  With
+ *   rt_set_light_sources the context rewrites those records itself and the mesh is accepted; without it host-deformed emitters go through rt_update_vertices +
+ *   rt_update_lights.  rt_upload_scene drops the skins; rt_build_accel and rt_rebuild_accel keep them.
  * rt_update_skins(ctx, count, skinIds, jointMatrices): re-poses the listed skins from the rest pose on the GPU.  jointMatrices = for every listed skin, in the
  *   order listed, jointCount x 12 floats (3 x 4 row-major, the layout of rt_instance::objectToWorld), concatenated.  Valid after rt_build_accel.  No skins set, an id
  *   out of range or listed twice, a non-finite matrix entry, or a pose that yields a non-finite position refuses the WHOLE call with RT_ERR_INVALID_ARG: the kernel
@@ -855,6 +857,49 @@ int rt_set_skins(rt_ctx* ctx, uint32_t numSkins, const rt_skin* skins, uint64_t 
 int rt_update_skins(rt_ctx* ctx, uint32_t count, const uint32_t* skinIds, const float* jointMatrices);
 int rt_vertices_readback(rt_ctx* ctx, uint64_t firstVertex, uint64_t count, rt_vertex* dst);
 int rt_get_deform_stats(rt_ctx* ctx, rt_deform_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Light sources (added within ABI 2.4, no version bump; csrc/light_records.hip).  A triangle-light record (rt_trig_light) holds WORLD positions
+ * v0 v1 v2, and the context does not know which triangle a record came from: rt_update_instances on an emissive instance moves the surface and leaves its light
+ * where it was until the host recomputes every record and calls rt_update_lights, and rt_set_skins refuses an emissive mesh.  A BINDING tells the context the
+ * source of every record; the update calls then rewrite the records of the instances they refit on the GPU, in the same refit tail, with no bus traffic.
+ * Only the 36 bytes v0 v1 v2 of a record depend on the matrix or the positions: the light pick is weighted by luminance(emissiveFactor), not by area, so impSamp
+ * (the alias table) and lightInfo.trigSampProb never change under motion or deformation, and texcoords keep their bits under rt_update_vertices and skinning.
+ *
+ * rt_set_light_sources(ctx, numTrig, sources): sources[k] = {instance, triangle}: trigLights[k] is triangle `triangle` (position in the index list / 3, relative
+ *   to the prim mesh) of instance `instance`.  Valid after rt_upload_scene (RT_ERR_NO_SCENE otherwise), before or after rt_build_accel.  numTrig == 0 removes the
+ *   binding.  Otherwise RT_ERR_INVALID_ARG, nothing changed, for: numTrig != the uploaded trigLightSize; NULL sources; an instance index out of range; a
+ *   triangle >= indexCount / 3 of the instance's prim mesh; a record whose matIndex differs from that prim mesh's materialIndex; and a binding that does not
+ *   describe the records: the call evaluates the update kernel for ALL records into a scratch array and compares v0 v1 v2 with the device records bit for bit, and
+ *   the message names the first record that differs.  So switching the binding on never changes a bit of a consistent scene; a host whose records went stale (it
+ *   moved an emitter without rt_update_lights) calls rt_update_lights first.  Records may be listed in any order, the records of one instance need not be
+ *   contiguous, and two records may name the same triangle.  Removing the binding while a skin on an emissive mesh exists is RT_ERR_INVALID_ARG.
+ *   Drains the pipeline; does not reset the reference-mode sums (no byte of the scene changes).
+ * With a binding set, rt_update_instances, rt_update_vertices and rt_update_skins rewrite v0 v1 v2 of every bound record whose instance they refit:
+ *   v_k = ((m[r][0] x + m[r][1] y) + m[r][2] z) + m[r][3] per row r of the instance's objectToWorld (xformPointRaw; fp32, no contraction) with (x, y, z) the
+ *   position of vertex indices[firstIndex + 3 triangle + k] + vertexOffset — the expression of the leaf records and of the host Scene's createTrigLightBuffer.
+ *   matIndex, transformIndex, uv0..uv2, impSamp and pad keep their bytes; records of other instances keep all 96 bytes; trigSampProb is untouched.  The kernel runs
+ *   on the main stream after the instance rows and the vertex commit are in place; a refused update (a pose with a non-finite position included) writes no record.
+ *   rt_set_skins accepts an emissive mesh while a binding is set (without one it refuses as before).  rt_update_lights still works and leaves the binding in
+ *   place; punctual lights stay the host's business.  rt_build_accel and rt_rebuild_accel keep the binding, rt_upload_scene drops it (as it drops skins),
+ *   rt_resize does not touch it.  Without a binding no call launches the kernel: the default path is unchanged.
+ *   A reused reservoir's light sample is one frame stale on a moving emitter: ReSTIR's own lag.
+ *   Scope: the single-GPU context only.  rt_mgpu_* contexts, rt_run_stage hosts and restir_amd/tiled.py are unchanged: they upload the moved scene.
+ * rt_lights_readback(ctx, which, dst, bytes): the device light arrays as they are now: RT_LIGHTS_TRIG (96 B per record) or RT_LIGHTS_PUNC (80 B per record).
+ *   Valid after rt_upload_scene; `bytes` must be the exact size (RT_ERR_INVALID_ARG otherwise).  Synchronous.
+ * rt_get_light_stats: the binding, and what the last update call did to the light records (rt_update_lights: rewritten = 0, lightBytesCopied = the bytes uploaded).
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t instance, triangle; } rt_light_source;   /* 8 B */
+typedef struct {
+  uint32_t bound;            /* records that have a source (0: no binding) */
+  uint32_t rewritten;        /* records whose v0 v1 v2 the last update call rewrote */
+  uint32_t lightBytesCopied; /* light bytes the last update call moved across the bus (0 on the device path) */
+  float    ms;               /* HIP-event time of the light kernel in that call */
+  uint32_t reserved[4];
+} rt_light_stats;            /* 32 B */
+enum { RT_LIGHTS_TRIG = 0, RT_LIGHTS_PUNC = 1 };
+int rt_set_light_sources(rt_ctx* ctx, uint32_t numTrig, const rt_light_source* sources);
+int rt_lights_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+int rt_get_light_stats(rt_ctx* ctx, rt_light_stats* out);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
@@ -887,6 +932,8 @@ static_assert(sizeof(rt_taa) == 32, "rt_taa");
 static_assert(sizeof(rt_refit_stats) == 32, "rt_refit_stats");
 static_assert(sizeof(rt_deform_stats) == 32, "rt_deform_stats");
 static_assert(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
+static_assert(sizeof(rt_light_source) == 8, "rt_light_source");
+static_assert(sizeof(rt_light_stats) == 32, "rt_light_stats");
 #endif
 
 #endif /* RT_ABI_H */
