@@ -41,13 +41,17 @@ struct DevScene {
   uint32_t numTris, numNodes;
   const struct SkyPre* sky;         // != nullptr: procedural sun & sky replaces the HDR map (_sunAndSky.in_use == 1)
   int32_t stackEntries;             // traversal stack entries per lane held in LDS (8 B each); entries beyond that live in stackOvf
-  int32_t coopLive;                 // traversal: cooperative triangle steps when at most this many rays of a wave are live (0 = off)
+  int32_t coopLive;                 // traversal: cooperative triangle steps when at most this many rays of a wave are live (0 = off).  In the ray pools of the
+                                    // indirect stage the wide tail (wideTail below) takes the last rays of a full wave first, so there this serves partial waves
+                                    // only; the direct stage's primary and shadow traces end on it as before
   float triPad;                     // box padding of the build (2e-5 x largest |coordinate|): an accepted hit point lies inside its triangle's padded box
   int32_t stackTotal;               // stack entries a ray of this tree can need (multiple of 4, > max depth); stackTotal - stackEntries per thread sit in HBM
   // overflow part of the traversal stacks: (stackTotal - stackEntries) entries per thread of a launch, thread = blockIdx.x * blockDim.x + threadIdx.x.
   // Two areas, because a direct-kind and an indirect-kind kernel can be in flight together; the launchers point stackOvf at the one of their stage.
   uint2* stackOvf; uint2* stackOvfInd;
   uint32_t stackOvfThreads;
+  int32_t wideTail;                 // throughput build, ray pools: a full wave whose pool is dry and whose live rays are at most this many (<= 8) finishes them
+                                    // eight lanes per ray (traverse.h wideTail); 0 = off.  RESTIR_WIDE_TAIL
   int32_t gangMax;                  // latency build: at most this many live rays in a wave whose pool is dry -> its idle ray slots work for them (traverse.h gangTail); 0 = off
 };
 

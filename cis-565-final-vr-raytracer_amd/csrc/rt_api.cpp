@@ -857,6 +857,7 @@ int rt_build_accel(rt_ctx* c)
   c->ds.stackEntries = c->ds.stackTotal;   // the launchers shorten it per launch (DevFrame::stackLds)
   c->ds.triPad = bo.pad;
   { const char* e = getenv("RESTIR_COOP"); c->ds.coopLive = e ? std::max(0, std::min(64, atoi(e))) : 4; }
+  { const char* e = getenv("RESTIR_WIDE_TAIL"); c->ds.wideTail = e ? std::max(0, std::min(8, atoi(e))) : 8; }   // throughput build: the last rays of a dry ray pool, eight lanes per ray (traverse.h wideTail)
   { const char* e = getenv("RESTIR_GANG"); c->ds.gangMax = e ? std::max(0, std::min(7, atoi(e))) : 4; }   // latency build: gang mode for the last rays of a wave (traverse.h)
   c->numNodes = bo.nodes.size(); c->numTris = bo.triRef.size(); c->maxDepth = bo.maxDepth;
   c->numRefs = bo.tris.size(); c->spatialSplits = size_t(bo.spatialSplits); c->sahNodeSteps = bo.sahNodeSteps; c->sahTriSteps = bo.sahTriSteps;

@@ -21,6 +21,10 @@ struct RayHit {
   float u, v;
 };
 
+// RT_LAT (compile-time): the latency build of the traced kernels, eight lanes per ray throughout (below; csrc/stages_lat.hip)
+#ifndef RT_LAT
+#define RT_LAT 0
+#endif
 // RT_WAVEPROF (compile-time, measurement builds only: scripts/wave_profile.py): per-wave cycle breakdown of the traversal rounds
 #ifndef RT_WAVEPROF
 #define RT_WAVEPROF 0
@@ -312,6 +316,14 @@ RT_DEV uint2* stackOverflowSlot(const DevScene& S, int sp)
   const size_t thread = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
   return S.stackOvf + (thread * size_t(S.stackTotal - S.stackEntries) + size_t(sp - S.stackEntries));
 }
+// the same LDS pointer as a new value (32 bits in one VGPR) that the compiler cannot trace back: see tracePool.  Whether it is still needed after a compiler update:
+// take the call out and run scripts/isa_loops.py stages.hip — the pool loops of k_indirect_stage (26 and 18 16-byte loads) must show no scratch access
+RT_DEV uint2* splitLdsPointer(uint2* p)
+{
+  uint32_t a = uint32_t(uintptr_t((RT_AS_LDS uint2*)p));
+  asm volatile("" : "+v"(a));
+  return (uint2*)((RT_AS_LDS uint2*)uintptr_t(a));
+}
 RT_DEV uint2 stackPop(const DevScene& S, Trav& T, uint2* stack)
 {
   --T.sp;
@@ -518,6 +530,13 @@ RT_DEV void travTriCoop(const DevScene& S, Trav& T, unsigned long long triMask, 
   }
 }
 
+// The wide tail (defined with the eight-lane step functions below): when at most S.wideTail rays of a full wave are live and none can join, they finish eight lanes
+// per ray.  Called by the ray pools of the indirect stage; the direct stage's traces keep the one-lane path (measured: DESIGN.md §9b, profiles/wide_tail_ab.txt).
+template <int MODE> RT_DEV void wideTail(const DevScene& S, Trav& T, bool live, unsigned long long liveMask, uint2* stack, TravCounters& tc);
+// largest live count at which a pool trace that starts here may enter the tail: S.wideTail when all 64 lanes of the wave are in the call, else 0 (a partial wave keeps
+// the one-lane path, travTriCoop included).  Wave-uniform; taken at the call's entry.
+RT_DEV int tailThreshold(const DevScene& S) { return (!RT_LAT && __ballot(1) == ~0ull) ? S.wideTail : 0; }
+
 // One scheduling round for a (partial) wave: every lane that is `live` votes for the kind of step it is ready for; the
 // majority kind runs, the other lanes wait one round.  Returns whether this lane still has work.
 template <int ANY>
@@ -647,6 +666,10 @@ RT_DEV void tracePool(const DevScene& S, float4* pool, bool hasC, bool hasS, uin
   int next = 0, mySlot = 0;
   bool live = false;
   Trav T;
+  const int tailAt = tailThreshold(S);
+  // (a value of its own for the loops below: the caller's pointer lives across all of its shading and is spilled there; without the split the register allocator
+  //  reloaded it from scratch at every stack pop and push of the loop once the tail had joined the function — scripts/isa_census.py, profiles/wide_tail_ab.txt)
+  stack = splitLdsPointer(stack);
   for(;;) {
     unsigned long long liveMask = __ballot(live ? 1 : 0);
     const unsigned long long idle = ~liveMask;   // every lane of the wave is in this loop
@@ -665,6 +688,11 @@ RT_DEV void tracePool(const DevScene& S, float4* pool, bool hasC, bool hasS, uin
     if(liveMask == 0ull) {
       if(next >= n) break;
       continue;
+    }
+    if(next >= n && __popcll(liveMask) <= tailAt) {   // the pool is dry: nobody joins the last rays
+      wideTail<2>(S, T, live, liveMask, stack, tc);
+      if(live) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
+      break;
     }
     const bool still = travRoundMasked<2>(S, T, live, liveMask, stack, tc);
     if(live && !still) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
@@ -695,6 +723,7 @@ RT_DEV void tracePoolTiles(const DevScene& S, float4* pool, uint32_t have /* bit
   int next = 0, mySlot = 0;
   bool live = false;
   Trav T;
+  const int tailAt = tailThreshold(S);
   for(;;) {
     unsigned long long liveMask = __ballot(live ? 1 : 0);
     const unsigned long long idle = ~liveMask;   // every lane of the wave is in this loop
@@ -712,6 +741,11 @@ RT_DEV void tracePoolTiles(const DevScene& S, float4* pool, uint32_t have /* bit
     if(liveMask == 0ull) {
       if(next >= n) break;
       continue;
+    }
+    if(next >= n && __popcll(liveMask) <= tailAt) {   // the pool is dry: nobody joins the last rays
+      wideTail<ANY>(S, T, live, liveMask, stack, tc);
+      if(live) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
+      break;
     }
     const bool still = travRoundMasked<ANY>(S, T, live, liveMask, stack, tc);
     if(live && !still) pool[mySlot * POOL_SLOT_F4] = make_float4(T.hit.t, rt_u2f(T.hit.gid), T.hit.u, T.hit.v);
@@ -732,10 +766,8 @@ RT_DEV void tracePoolTiles(const DevScene& S, float4* pool, uint32_t have /* bit
 //   * the ray's state is replicated in its eight lanes, its stack is one column in LDS.
 // A wave carries 8 rays; the waves of a workgroup share an LDS ray pool and pull rays group by group as theirs finish (tracePoolWide).  Verdicts are functions
 // of (ray, triangle) and the closest hit is a minimum over (t, id), so the result is bit-identical to the one-lane-per-ray traversal.
-#ifndef RT_LAT
-#define RT_LAT 0
-#endif
-#if RT_LAT
+// The step functions of a group (travNodeTestW, travTriW, the DPP reductions) are compiled into every build: the throughput build finishes the last rays of a
+// wave with them (wideTail, below).
 constexpr int WIDE_G = 8;            // lanes per ray
 constexpr int WIDE_RAYS = 64 / WIDE_G;  // rays per wave = stack columns per wave
 // DPP controls (gfx9): quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror (lane i <-> 7 - i inside each group of eight)
@@ -762,6 +794,7 @@ template <int CTRL> RT_DEV void candMinStep(WideCand& c)
 // lexicographic minimum of (t, gid) over the group, with its (u, v)
 RT_DEV void groupMinCand(WideCand& c) { candMinStep<RT_DPP_XOR1>(c); candMinStep<RT_DPP_XOR2>(c); candMinStep<RT_DPP_HALF_MIRROR>(c); }
 
+#if RT_LAT
 // the ray's stack: one 8-byte column per ray, stride WIDE_RAYS entries (every lane of the group reads the same address; lane 0 of the group writes)
 RT_DEV uint2 stackPopW(Trav& T, const uint2* stack) { --T.sp; return ldsLoadU2(stack + T.sp * WIDE_RAYS); }
 RT_DEV void stackPushW(Trav& T, uint2* stack, uint2 g, int j) { if(j == 0) ldsStoreU2(stack + T.sp * WIDE_RAYS, g); T.sp++; }
@@ -778,6 +811,7 @@ RT_DEV uint32_t travNodeSelectW(Trav& T, uint2* stack, int j)
   T.ngroup.y = 0u;
   return ngroup.x + rel;
 }
+#endif  // RT_LAT
 RT_DEV uint32_t byteOf(uint32_t lo, uint32_t hi, int j) { return ((j < 4 ? lo : hi) >> (8 * (j & 3))) & 0xffu; }
 // lane j of the group tests child j of the fetched node (the arithmetic of travNodeTest for that child)
 RT_DEV void travNodeTestW(Trav& T, const NodeRegs& N, int j)
@@ -805,10 +839,13 @@ RT_DEV void travNodeTestW(Trav& T, const NodeRegs& N, int j)
   T.tgroup = make_uint2(n1.y, hitmask & 0x00FFFFFFu);
 }
 // lane j tests the j-th pending triangle (list order: highest bit first); up to eight per step, the rest stay pending
-template <int MODE>
+// TAIL (wideTail): the any-hit range is read from T.hit.t instead of T.tmax — the same number while an any-hit ray is alive (travInit; its first accepted
+// hit ends it), and one register less in the tail's loop
+template <int MODE, bool TAIL = false>
 RT_DEV void travTriW(const DevScene& S, Trav& T, int j, TravCounters& tc)
 {
   const bool ANY = MODE == 2 ? T.isAny : MODE == 1;
+  const float tmax = TAIL ? T.hit.t : T.tmax;
   uint32_t rem = T.tgroup.y;
   int mine = -1;
 #pragma unroll
@@ -829,13 +866,14 @@ RT_DEV void travTriW(const DevScene& S, Trav& T, int j, TravCounters& tc)
 #define RT_PH(k)
 #endif
   if(mine >= 0) {
+    if(TAIL) tc.tris++;   // per triangle tested (counting builds of the throughput kernels; the latency build has none and counts nothing)
     float t, u, v; uint32_t gid, alphaIdx;
     const uint32_t ti = T.tgroup.x + uint32_t(mine);
     const TriRegs Q = triLoad(S, ti);
     const uint4* ap = reinterpret_cast<const uint4*>(S.alphaByTri + ti);   // fetched with the record, whether needed or not: no second dependent access
     AlphaRegs A; A.r0 = gLoadU4(ap); A.r1 = gLoadU4(ap + 1); A.r2 = gLoadU4(ap + 2); A.r3 = gLoadU4(ap + 3);
     RT_PH(0)   // record + AlphaRec arrive
-    const int s = triCandidateGeom(S, Q, T.o, T.d, ANY, T.tmax, T.hit.t, T.hit.gid, T.seed, t, u, v, gid, alphaIdx, tc);
+    const int s = triCandidateGeom(S, Q, T.o, T.d, ANY, tmax, T.hit.t, T.hit.gid, T.seed, t, u, v, gid, alphaIdx, tc);
     ok = s == 1;
     RT_PH(1)   // intersection, padded-box check, opacity micro-map
     if(s == 2) {
@@ -863,6 +901,114 @@ RT_DEV void travTriW(const DevScene& S, Trav& T, int j, TravCounters& tc)
 #undef RT_PH
   (void)ok;
 }
+
+// ---- wide tail of the throughput build ----------------------------------------------------------------------------------------------------------------
+// When at most S.wideTail (<= 8) rays of a full wave are live and no ray can join them, a one-lane-per-ray round still costs a 64-lane step for a handful of
+// lanes (profiles/r05_pool_order_ab.txt: 25 % of the direct stage's rounds, 36 % of the indirect stage's).  wideTail() moves those rays ONCE to the eight-lane
+// form of the latency build — group g of the wave takes the state of the g-th live lane with one ds_bpermute per dword — and runs them to the end with
+// travNodeTestW / travTriW: a node round is ~70 instructions instead of ~230, a triangle round tests up to eight pending triangles of a ray.  No stack moves:
+// the eight lanes of a group read the OWNER lane's LDS column (one address in eight lanes: a broadcast) and the owner thread's HBM overflow slots, lane 0 of the
+// group writes.  At the end the owner lane takes hit / found / rec back from lane 0 of its group.  Verdicts are functions of (ray, triangle, seed) and the
+// closest hit is the minimum of (t, globalId), so the result is the one-lane one bit for bit; an any-hit ray reports the closest of the candidates its last
+// step accepted instead of the first in list order — every any-hit consumer reads the verdict only (shading.h AnyHit, the pool slots in stages.hip).
+RT_DEV uint32_t bpermU(int srcLane, uint32_t v) { return uint32_t(__builtin_amdgcn_ds_bpermute(srcLane << 2, int(v))); }
+RT_DEV float bpermF(int srcLane, float v) { return rt_u2f(bpermU(srcLane, rt_f2u(v))); }
+// the stack of a ray as its group sees it: the owner lane's LDS column (entry stride 64) and the owner thread's overflow area in HBM (entry S.stackEntries first)
+struct OwnerStack { uint2* col; int delta; };   // delta: owner lane - this lane (the overflow slots are addressed by thread)
+RT_DEV uint2* ownerOverflowSlot(const DevScene& S, const OwnerStack& K, int sp)
+{
+  const size_t thread = size_t(blockIdx.x) * blockDim.x + size_t(int(threadIdx.x) + K.delta);
+  return S.stackOvf + (thread * size_t(S.stackTotal - S.stackEntries) + size_t(sp - S.stackEntries));
+}
+RT_DEV uint2 stackPopO(const DevScene& S, Trav& T, const OwnerStack& K)
+{
+  --T.sp;
+  if(__builtin_expect(T.sp < S.stackEntries, 1)) return ldsLoadU2(K.col + T.sp * 64);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // (written by another lane of this wave)
+  return gLoadU2(ownerOverflowSlot(S, K, T.sp));
+}
+RT_DEV void stackPushO(const DevScene& S, Trav& T, const OwnerStack& K, uint2 g, int j)
+{
+  if(__builtin_expect(T.sp < S.stackEntries, 1)) { if(j == 0) ldsStoreU2(K.col + T.sp * 64, g); T.sp++; }
+  else if(T.sp < S.stackTotal) { if(j == 0) gStoreU2(ownerOverflowSlot(S, K, T.sp), g); __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); T.sp++; }
+}
+RT_DEV uint32_t travNodeSelectO(const DevScene& S, Trav& T, const OwnerStack& K, int j)
+{
+  uint2 ngroup = T.ngroup;
+  if(ngroup.y <= 0x00FFFFFFu) ngroup = stackPopO(S, T, K);
+  const uint32_t hits = ngroup.y;
+  const uint32_t bit = 31u - uint32_t(__clz(int(hits)));
+  ngroup.y &= ~(1u << bit);
+  if(ngroup.y > 0x00FFFFFFu) stackPushO(S, T, K, ngroup, j);
+  const uint32_t slot = (bit - 24u) ^ T.octinv;
+  const uint32_t rel = uint32_t(__popc(hits & ~(0xFFFFFFFFu << slot) & 0xFFu));
+  T.ngroup.y = 0u;
+  return ngroup.x + rel;
+}
+// Wave-uniform call: all 64 lanes of the wave, 1 <= popcount(liveMask) <= 8, liveMask = the lanes whose `live` is set.  `stack` = this lane's LDS column of
+// one array of 64 columns (every caller's s_stack + lane), so the owner's column is a lane difference away.  On return every ray is finished.
+template <int MODE>
+RT_DEV void wideTail(const DevScene& S, Trav& T, bool live, unsigned long long liveMask, uint2* stack, TravCounters& tc)
+{
+  const int lane = int(threadIdx.x) & 63, j = lane & (WIDE_G - 1), g = lane >> 3;
+  int owner = lane;   // the g-th live lane
+  bool wl = false;    // this group carries a ray, and the ray is live
+  {
+    unsigned long long m = liveMask;
+#pragma unroll
+    for(int k = 0; k < WIDE_RAYS; k++) {
+      if(m != 0ull) { if(g == k) { owner = __builtin_ctzll(m); wl = true; } m &= m - 1ull; }
+    }
+  }
+  Trav W;
+  W.o = mk3(bpermF(owner, T.o.x), bpermF(owner, T.o.y), bpermF(owner, T.o.z));
+  W.d = mk3(bpermF(owner, T.d.x), bpermF(owner, T.d.y), bpermF(owner, T.d.z));
+  W.idx = bpermF(owner, T.idx); W.idy = bpermF(owner, T.idy); W.idz = bpermF(owner, T.idz);
+  W.octinv = bpermU(owner, T.octinv);
+  W.ngroup = make_uint2(bpermU(owner, T.ngroup.x), bpermU(owner, T.ngroup.y));
+  W.tgroup = make_uint2(bpermU(owner, T.tgroup.x), bpermU(owner, T.tgroup.y));
+  W.sp = int(bpermU(owner, uint32_t(T.sp)));
+  W.tmax = 0.0f;   // (travTriW<MODE, true> reads W.hit.t)
+  W.seed = bpermU(owner, T.seed);
+  W.hit.t = bpermF(owner, T.hit.t); W.hit.gid = bpermU(owner, T.hit.gid); W.hit.u = bpermF(owner, T.hit.u); W.hit.v = bpermF(owner, T.hit.v);
+  W.rec = bpermU(owner, T.rec);
+  W.isAny = MODE == 2 ? (bpermU(owner, T.isAny ? 1u : 0u) != 0u) : false;
+  W.found = false;
+  OwnerStack K;
+  K.delta = owner - lane;
+  K.col = stack + K.delta;
+  unsigned long long wm = __ballot(wl ? 1 : 0);
+  while(wm != 0ull) {
+    if(j == 0) { tc.rounds++; tc.live += wl ? 1u : 0u; }   // lane 0 of a group counts for its ray slot (counting builds): rounds, live rounds, node steps
+    bool wantTri = wl && travHasTris(W);
+    bool wantNode = wl && !wantTri;
+    {  // one kind of step per round, by vote of the tail's rays, as travRoundW (every ray taking the step it is ready for: frame +1.5 %, profiles/wide_tail_ab.txt)
+      const int nT = __popcll(__ballot(wantTri ? 1 : 0)), nN = __popcll(wm) - nT;
+      if(nT >= nN) wantNode = false; else wantTri = false;
+    }
+#if RT_WAVEPROF
+    const uint64_t c0 = clock64();
+    const int ex = __popcll(__ballot((wantTri || wantNode) ? 1 : 0));
+#endif
+    if(wantTri) travTriW<MODE, true>(S, W, j, tc);
+    if(wantNode) {
+      if(j == 0) tc.nodes++;
+      const NodeRegs N = nodeLoad(S, travNodeSelectO(S, W, K, j));
+      travNodeTestW(W, N, j);
+    }
+#if RT_WAVEPROF
+    { tc.rC++; tc.cC += uint32_t(clock64() - c0); tc.hl[(__popcll(wm) / WIDE_G - 1) >> 3]++; tc.he[(max(ex, 1) - 1) >> 3]++; }   // live RAYS, executing LANES
+#endif
+    wl = wl && (travHasTris(W) || travHasNodes(W));
+    wm = __ballot(wl ? 1 : 0);
+  }
+  // results go home: lane 0 of the group that ran this lane's ray (the groups were dealt in lane order)
+  const int src = live ? __popcll(liveMask & ((1ull << lane) - 1ull)) * WIDE_G : lane;
+  const float ht = bpermF(src, W.hit.t), hu = bpermF(src, W.hit.u), hv = bpermF(src, W.hit.v);
+  const uint32_t hg = bpermU(src, W.hit.gid), hr = bpermU(src, W.rec), hf = bpermU(src, W.found ? 1u : 0u);
+  if(live) { T.hit.t = ht; T.hit.gid = hg; T.hit.u = hu; T.hit.v = hv; T.rec = hr; T.found = T.found || hf != 0u; }
+}
+#if RT_LAT
 // one round of a wave: a ray wants a triangle step if it has pending triangles, a node step otherwise; the wave takes the kind most of its rays want
 template <int MODE>
 RT_DEV bool travRoundW(const DevScene& S, Trav& T, bool live, int j, uint2* stack, TravCounters& tc)
