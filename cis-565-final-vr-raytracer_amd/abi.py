@@ -154,6 +154,20 @@ SKIN_INFLUENCE_DT = np.dtype([("joint", "<u2", 4), ("weight", "<f4", 4)])
 VERTEX_DT = np.dtype([("position", "<f4", 3), ("normal", "<u4"), ("texcoord", "<f4", 2), ("tangent", "<u4"), ("color", "<u4")])
 
 
+# rt_set_morph_targets / rt_update_morphs: rt_morph_set (16 B) and rt_morph_delta (16 B) as numpy rows
+MORPH_NORMALS, MORPH_TANGENTS = 1, 2
+MORPH_SET_DT = np.dtype([("primMesh", "<u4"), ("targetCount", "<u4"), ("firstDelta", "<u4"), ("planes", "<u4")])
+MORPH_DELTA_DT = np.dtype([("d", "<f4", 3), ("pad", "<f4")])
+
+
+class MorphStats(C.Structure):  # rt_morph_stats, 32 B
+    _fields_ = [("sets", C.c_uint32), ("vertices", C.c_uint32), ("targetsApplied", C.c_uint32), ("instances", C.c_uint32), ("morphMs", C.c_float), ("ms", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+assert MORPH_SET_DT.itemsize == 16 and MORPH_DELTA_DT.itemsize == 16 and C.sizeof(MorphStats) == 32
+
+
 class LightStats(C.Structure):  # rt_light_stats, 32 B
     _fields_ = [("bound", C.c_uint32), ("rewritten", C.c_uint32), ("lightBytesCopied", C.c_uint32), ("ms", C.c_float), ("reserved", C.c_uint32 * 4)]
 

@@ -27,6 +27,7 @@
 #include "refit.h"
 #include "accel_build.h"
 #include "deform.h"
+#include "morph.h"
 #include "light_records.h"
 #include "dev_math.h"
 
@@ -160,6 +161,23 @@ struct rt_ctx {
   } deform;
   std::vector<void*> skinAllocs, deformAllocs;
   hipEvent_t evDeform[2] = {nullptr, nullptr};   // start / end of the skinning kernel and its commit copy
+  // rt_set_morph_targets / rt_update_morphs (csrc/morph.hip).  The deltas, the rest pose and staging range of the morph-only meshes (a mesh with a
+  // skin uses the skin's), and the per-call job and active-target tables live in morphAllocs: replaced by rt_set_morph_targets, dropped by rt_upload_scene.
+  // weights[k]: the stored weights of set k; stale[k]: the device rows of a morph-only set's mesh are newer than c->vertices (a skinned mesh marks its skin).
+  // skinMats[s]: the joint matrices of the last successful rt_update_skins that listed skin s (empty: never posed); kept with the skins, used by morph-then-skin.
+  struct Morph {
+    std::vector<rt_morph_set> sets;
+    std::vector<int32_t> setOfMesh;              // per prim mesh: its set, or -1 (empty: no sets)
+    std::vector<uint32_t> restFirst;             // per set: first row of its mesh in dRest / dStaged (morph-only meshes; unused where the mesh has a skin)
+    std::vector<std::vector<float>> weights;
+    std::vector<uint8_t> stale;
+    rt_vertex* dRest = nullptr; rt_vertex* dStaged = nullptr; rt_morph_delta* dDeltas = nullptr;
+    MorphJob* dJobs = nullptr; MorphActive* dActive = nullptr;
+    rt_morph_stats stats{};
+  } morph;
+  std::vector<std::vector<float>> skinMats;
+  std::vector<void*> morphAllocs;
+  hipEvent_t evMorph[2] = {nullptr, nullptr};    // start / end of the morph kernel
   // rt_set_light_sources (csrc/light_records.hip).  The binding (one source per triangle-light record), the scratch records of the bind-time check
   // and the counter live in lightAllocs: replaced by rt_set_light_sources, dropped by rt_upload_scene.  The context keeps no host copy of the light records.
   struct Lights {
@@ -512,7 +530,7 @@ int rt_destroy(rt_ctx* c)
   (void)hipSetDevice(c->device);
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
-  freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs);
+  freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
@@ -536,6 +554,7 @@ int rt_destroy(rt_ctx* c)
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
   for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evDeform) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evMorph) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evLights) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   delete c;
@@ -610,6 +629,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   LoadTimer lt;
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->rebuildAllocs);
   freePool(c->skinAllocs); freePool(c->deformAllocs);   // a new scene has no skins
+  freePool(c->morphAllocs);   // ... and no morph sets
+  c->morph = rt_ctx::Morph{}; c->skinMats.clear();
   freePool(c->lightAllocs);   // ... and no light-source binding
   c->lights = rt_ctx::Lights{};
   c->deform = rt_ctx::Deform{};
@@ -2386,6 +2407,13 @@ static int syncHostVertices(rt_ctx* c, int mesh)
     if(pm.vertexCount) RT_HIP(c, hipMemcpy(c->vertices.data() + pm.vertexOffset, c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToHost));
     D.stale[k] = 0;
   }
+  rt_ctx::Morph& M = c->morph;   // morph-only meshes (a morphed mesh that has a skin marks the skin)
+  for(size_t k = 0; k < M.sets.size(); k++) {
+    if(!M.stale[k] || (mesh >= 0 && uint32_t(mesh) != M.sets[k].primMesh)) continue;
+    const rt_prim_mesh& pm = c->primMeshes[M.sets[k].primMesh];
+    if(pm.vertexCount) RT_HIP(c, hipMemcpy(c->vertices.data() + pm.vertexOffset, c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToHost));
+    M.stale[k] = 0;
+  }
   return RT_OK;
 }
 
@@ -2401,51 +2429,66 @@ static int ensureDeformBuffers(rt_ctx* c)
   return RT_OK;
 }
 
-// What rt_update_vertices and rt_update_skins share.  `meshes`: the deformed prim meshes.  skinJobs != nullptr: the pose is in the staging range (k_skin has been
-// enqueued after evRefit[0] / evDeform[0]); it is committed to the live array only when no staged position is non-finite, else the call is refused with nothing changed.
-// Then the coordinate maxima of every instance of those meshes (k_inst_coord_max) go into R.instMax, and refitTail does the rest as for rt_update_instances.
-static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& meshes, const std::vector<SkinJob>* skinJobs, const std::vector<uint32_t>* skinIds,
-                       uint32_t verticesWritten, uint32_t bytesCopied)
+// the posed rows of one deformed mesh before their commit: `count` rows from pool[first] (the skins' staging buffer, or the morph pool's for a morph-only mesh);
+// *stale is set by the commit (the context's copy of the mesh is then older than the device rows)
+struct StagedMesh { uint32_t mesh; const rt_vertex* pool; uint32_t first, count; uint8_t* stale; };
+
+// What rt_update_vertices, rt_update_skins and rt_update_morphs share.  `meshes`: the deformed prim meshes.  staged != nullptr: the pose is in staging rows (the
+// kernels have been enqueued after evRefit[0] / evDeform[0]), one entry per mesh; it is committed to the live array only when no staged position is non-finite,
+// else the call is refused with nothing changed.  Then the coordinate maxima of every instance of those meshes (k_inst_coord_max, one launch per staging pool)
+// go into R.instMax, and refitTail does the rest as for rt_update_instances.
+static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& meshes, const std::vector<StagedMesh>* staged, uint32_t verticesWritten, uint32_t bytesCopied)
 {
   rt_ctx::Refit& R = c->refit;
   rt_ctx::Deform& D = c->deform;
   const size_t nInst = c->instances.size();
   hipStream_t s = c->stream;
-  std::vector<uint8_t> deformed(c->primMeshes.size(), 0);
-  for(uint32_t m : meshes) deformed[m] = 1;
+  std::vector<int32_t> deformed(c->primMeshes.size(), -1);   // -1: not deformed; else the mesh's entry in `staged` (0 without staging)
+  for(size_t k = 0; k < meshes.size(); k++) deformed[meshes[k]] = staged ? int32_t(k) : 0;
+  std::vector<const rt_vertex*> pools;                        // the arrays the coordinate maxima are read from
+  if(!staged) pools.push_back(c->ds.vertices);
+  else for(const StagedMesh& sm : *staged) if(std::find(pools.begin(), pools.end(), sm.pool) == pools.end()) pools.push_back(sm.pool);
   std::vector<CoordJob> jobs;
   std::vector<uint8_t> dirty(nInst, 0);
-  uint32_t threads = 0;
-  for(uint32_t i = 0; i < nInst; i++) {
-    const uint32_t m = c->instances[i].primMesh;
-    if(!deformed[m]) continue;
-    dirty[i] = 1;
-    const rt_prim_mesh& pm = c->primMeshes[m];
-    CoordJob j{};
-    j.threadBase = threads; j.indexCount = pm.indexCount; j.firstIndex = pm.firstIndex; j.instance = i;
-    j.vertexBase = skinJobs ? D.restFirst[size_t(D.skinOfMesh[m])] : pm.vertexOffset;
-    jobs.push_back(j);
-    threads += (pm.indexCount + 63u) & ~63u;
+  struct Launch { size_t first, count; uint32_t threads; };
+  std::vector<Launch> launches;
+  for(const rt_vertex* pool : pools) {
+    Launch l{jobs.size(), 0, 0};
+    for(uint32_t i = 0; i < nInst; i++) {
+      const uint32_t m = c->instances[i].primMesh;
+      if(deformed[m] < 0 || (staged && (*staged)[size_t(deformed[m])].pool != pool)) continue;
+      dirty[i] = 1;
+      const rt_prim_mesh& pm = c->primMeshes[m];
+      CoordJob j{};
+      j.threadBase = l.threads; j.indexCount = pm.indexCount; j.firstIndex = pm.firstIndex; j.instance = i;
+      j.vertexBase = staged ? (*staged)[size_t(deformed[m])].first : pm.vertexOffset;
+      jobs.push_back(j);
+      l.threads += (pm.indexCount + 63u) & ~63u;
+    }
+    l.count = jobs.size() - l.first;
+    launches.push_back(l);
   }
   std::vector<uint32_t> out(jobs.size() + 1, 0u);
-  if(!skinJobs) RT_HIP(c, hipMemsetAsync(D.dOut, 0, 4, s));   // (the skin path cleared the counter ahead of k_skin)
+  if(!staged) RT_HIP(c, hipMemsetAsync(D.dOut, 0, 4, s));   // (the staged paths cleared the counter ahead of their kernels)
   if(!jobs.empty()) {
     RT_HIP(c, hipMemsetAsync(D.dOut + 1, 0, jobs.size() * 4, s));
     RT_HIP(c, hipMemcpyAsync(D.dCoordJobs, jobs.data(), jobs.size() * sizeof(CoordJob), hipMemcpyHostToDevice, s));
-    CoordMaxArgs ca{};
-    ca.vertices = skinJobs ? D.dStaged : c->ds.vertices; ca.indices = c->ds.indices; ca.instances = c->ds.instances; ca.jobs = D.dCoordJobs;
-    ca.numJobs = uint32_t(jobs.size()); ca.numThreads = threads; ca.out = D.dOut + 1;
-    RT_HIP(c, launchInstCoordMax(s, ca));
+    for(size_t p = 0; p < pools.size(); p++) {
+      if(!launches[p].count) continue;
+      CoordMaxArgs ca{};
+      ca.vertices = pools[p]; ca.indices = c->ds.indices; ca.instances = c->ds.instances; ca.jobs = D.dCoordJobs + launches[p].first;
+      ca.numJobs = uint32_t(launches[p].count); ca.numThreads = launches[p].threads; ca.out = D.dOut + 1 + launches[p].first;
+      RT_HIP(c, launchInstCoordMax(s, ca));
+    }
   }
   RT_HIP(c, hipMemcpyAsync(out.data(), D.dOut, out.size() * 4, hipMemcpyDeviceToHost, s));
   RT_HIP(c, hipStreamSynchronize(s));
-  if(skinJobs && out[0] != 0u) { c->err = std::string(who) + ": the pose yields a non-finite position"; return RT_ERR_INVALID_ARG; }   // only the staging range was written
-  if(skinJobs) {   // commit: staging range -> live rows, on the stream ahead of the refit
-    for(size_t k = 0; k < skinJobs->size(); k++) {
-      const SkinJob& j = (*skinJobs)[k];
-      const rt_prim_mesh& pm = c->primMeshes[D.skins[(*skinIds)[k]].primMesh];
-      if(j.count) RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + pm.vertexOffset, D.dStaged + j.restFirst, size_t(j.count) * sizeof(rt_vertex), hipMemcpyDeviceToDevice, s));
-      D.stale[(*skinIds)[k]] = 1;
+  if(staged && out[0] != 0u) { c->err = std::string(who) + ": the pose yields a non-finite position"; return RT_ERR_INVALID_ARG; }   // only staging rows were written
+  if(staged) {   // commit: staging rows -> live rows, on the stream ahead of the refit
+    for(const StagedMesh& sm : *staged) {
+      const rt_prim_mesh& pm = c->primMeshes[sm.mesh];
+      if(sm.count) RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + pm.vertexOffset, sm.pool + sm.first, size_t(sm.count) * sizeof(rt_vertex), hipMemcpyDeviceToDevice, s));
+      *sm.stale = 1;
     }
     RT_HIP(c, hipEventRecord(c->evDeform[1], s));
   }
@@ -2454,8 +2497,94 @@ static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& 
   D.stats = rt_deform_stats{};
   D.stats.meshes = uint32_t(meshes.size()); D.stats.vertices = verticesWritten; D.stats.instances = uint32_t(jobs.size()); D.stats.vertexBytesCopied = bytesCopied;
   D.stats.ms = R.stats.ms;
-  if(skinJobs) (void)hipEventElapsedTime(&D.stats.skinMs, c->evDeform[0], c->evDeform[1]);
+  if(staged) (void)hipEventElapsedTime(&D.stats.skinMs, c->evDeform[0], c->evDeform[1]);
   return RT_OK;
+}
+
+// The posing kernels of a call that involves morph sets, then deformRefit.  One item per mesh: its skin (or -1) with the joint matrices to use, its morph set (or
+// -1) with the weights to use.  A set poses with k_morph when it has an active target or when its mesh has no skin (no active target: the rest rows are copied);
+// a skin poses with k_skin from the staging range in place when k_morph wrote it, else from the rest pose as rt_update_skins always did.
+struct PoseItem { int32_t skin; const float* mats; int32_t set; const float* weights; };
+
+static int poseAndRefit(rt_ctx* c, const char* who, const std::vector<PoseItem>& items, uint32_t* activeOut)
+{
+  rt_ctx::Deform& D = c->deform;
+  rt_ctx::Morph& M = c->morph;
+  std::vector<MorphJob> mjobs;
+  std::vector<MorphActive> active;
+  std::vector<SkinJob> fromRest, inPlace;
+  std::vector<float> matsRest, matsInPlace;
+  std::vector<StagedMesh> staged;
+  std::vector<uint32_t> meshes;
+  uint32_t mthreads = 0, vertices = 0;
+  for(const PoseItem& it : items) {
+    const uint32_t mesh = it.skin >= 0 ? D.skins[size_t(it.skin)].primMesh : M.sets[size_t(it.set)].primMesh;
+    const uint32_t V = c->primMeshes[mesh].vertexCount;
+    const uint32_t first = it.skin >= 0 ? D.restFirst[size_t(it.skin)] : M.restFirst[size_t(it.set)];
+    bool morphed = false;
+    if(it.set >= 0) {
+      const rt_morph_set& ms = M.sets[size_t(it.set)];
+      MorphJob j{};
+      j.threadBase = mthreads; j.count = V; j.restFirst = first; j.firstDelta = ms.firstDelta; j.firstActive = uint32_t(active.size()); j.planes = ms.planes;
+      j.pool = it.skin >= 0 ? 0u : 1u;
+      for(uint32_t t = 0; t < ms.targetCount; t++) if(it.weights[t] != 0.0f) active.push_back(MorphActive{t, it.weights[t]});
+      j.numActive = uint32_t(active.size()) - j.firstActive;
+      morphed = j.numActive != 0u || it.skin < 0;
+      if(morphed) { mjobs.push_back(j); mthreads += (V + 63u) & ~63u; }
+    }
+    if(it.skin >= 0) {
+      const rt_skin& sk = D.skins[size_t(it.skin)];
+      std::vector<SkinJob>& jobs = morphed ? inPlace : fromRest;
+      std::vector<float>& mats = morphed ? matsInPlace : matsRest;
+      SkinJob j{};
+      j.threadBase = jobs.empty() ? 0u : jobs.back().threadBase + jobs.back().count;
+      j.count = V; j.restFirst = first; j.firstInfluence = sk.firstInfluence; j.firstJoint = uint32_t(mats.size() / 12);
+      jobs.push_back(j);
+      mats.insert(mats.end(), it.mats, it.mats + size_t(sk.jointCount) * 12);
+    }
+    staged.push_back(StagedMesh{mesh, it.skin >= 0 ? D.dStaged : M.dStaged, first, V, it.skin >= 0 ? &D.stale[size_t(it.skin)] : &M.stale[size_t(it.set)]});
+    meshes.push_back(mesh);
+    vertices += V;
+  }
+  if(activeOut) *activeOut = uint32_t(active.size());
+  for(SkinJob& j : inPlace) j.firstJoint += uint32_t(matsRest.size() / 12);   // one matrix array: the from-rest skins' first
+  matsRest.insert(matsRest.end(), matsInPlace.begin(), matsInPlace.end());
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // v1: joins the frames in flight
+  int rc;
+  if((rc = ensureRefitState(c))) return rc;
+  if((rc = ensureDeformBuffers(c))) return rc;
+  for(hipEvent_t& e : c->evMorph) if(!e) RT_HIP(c, hipEventCreate(&e));
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evRefit[0], s));
+  RT_HIP(c, hipEventRecord(c->evDeform[0], s));
+  RT_HIP(c, hipMemsetAsync(D.dOut, 0, 4, s));
+  RT_HIP(c, hipEventRecord(c->evMorph[0], s));
+  if(!mjobs.empty()) {
+    RT_HIP(c, hipMemcpyAsync(M.dJobs, mjobs.data(), mjobs.size() * sizeof(MorphJob), hipMemcpyHostToDevice, s));
+    if(!active.empty()) RT_HIP(c, hipMemcpyAsync(M.dActive, active.data(), active.size() * sizeof(MorphActive), hipMemcpyHostToDevice, s));
+    MorphArgs a{};
+    a.rest0 = D.dRest; a.staged0 = D.dStaged; a.rest1 = M.dRest; a.staged1 = M.dStaged; a.deltas = M.dDeltas; a.active = M.dActive; a.jobs = M.dJobs;
+    a.numJobs = uint32_t(mjobs.size()); a.numThreads = mthreads; a.nonFinite = D.dOut;
+    RT_HIP(c, launchMorph(s, a));
+  }
+  RT_HIP(c, hipEventRecord(c->evMorph[1], s));
+  if(!fromRest.empty() || !inPlace.empty()) {
+    RT_HIP(c, hipMemcpyAsync(D.dJoints, matsRest.data(), matsRest.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    if(!fromRest.empty()) RT_HIP(c, hipMemcpyAsync(D.dSkinJobs, fromRest.data(), fromRest.size() * sizeof(SkinJob), hipMemcpyHostToDevice, s));
+    if(!inPlace.empty()) RT_HIP(c, hipMemcpyAsync(D.dSkinJobs + fromRest.size(), inPlace.data(), inPlace.size() * sizeof(SkinJob), hipMemcpyHostToDevice, s));
+    SkinArgs a{};
+    a.influences = D.dInfluences; a.joints = D.dJoints; a.nonFinite = D.dOut; a.staged = D.dStaged;
+    if(!fromRest.empty()) {
+      a.rest = D.dRest; a.jobs = D.dSkinJobs; a.numJobs = uint32_t(fromRest.size()); a.numThreads = fromRest.back().threadBase + fromRest.back().count;
+      RT_HIP(c, launchSkin(s, a));
+    }
+    if(!inPlace.empty()) {   // the morphed rows are the skin's input: every thread reads and writes its own staging row
+      a.rest = D.dStaged; a.jobs = D.dSkinJobs + fromRest.size(); a.numJobs = uint32_t(inPlace.size()); a.numThreads = inPlace.back().threadBase + inPlace.back().count;
+      RT_HIP(c, launchSkin(s, a));
+    }
+  }
+  return deformRefit(c, who, meshes, &staged, vertices, 0u);
 }
 
 extern "C" {
@@ -2468,6 +2597,7 @@ int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint3
   if(uint64_t(firstVertex) + count > pm.vertexCount) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: vertex range outside the prim mesh");
   if(count && !rows) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: NULL rows");
   if(!c->deform.skinOfMesh.empty() && c->deform.skinOfMesh[primMesh] >= 0) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: the prim mesh has a skin");
+  if(!c->morph.setOfMesh.empty() && c->morph.setOfMesh[primMesh] >= 0) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: the prim mesh has a morph set");
   const size_t base = size_t(pm.vertexOffset) + firstVertex;
   for(uint32_t k = 0; k < count; k++) {
     const rt_vertex& v = rows[k];
@@ -2488,7 +2618,7 @@ int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint3
     RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + base, c->vertices.data() + base, size_t(count) * sizeof(rt_vertex), hipMemcpyHostToDevice, s));
     meshes.push_back(primMesh);
   }
-  return deformRefit(c, "rt_update_vertices", meshes, nullptr, nullptr, count, count * uint32_t(sizeof(rt_vertex)));
+  return deformRefit(c, "rt_update_vertices", meshes, nullptr, count, count * uint32_t(sizeof(rt_vertex)));
 }
 
 int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t numInfluences, const rt_skin_influence* influences)
@@ -2496,6 +2626,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
   if(!c) return RT_ERR_INVALID_ARG;
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_skins: no scene uploaded");
   if(numSkins && !skins) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: NULL skins");
+  if(!c->morph.sets.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: morph sets exist (skins first: remove the sets with rt_set_morph_targets, set the skins, set the sets again)");
   std::vector<int32_t> skinOfMesh(c->primMeshes.size(), -1);
   std::vector<uint32_t> restFirst(numSkins, 0u);
   uint64_t totalVerts = 0, totalJoints = 0;
@@ -2529,6 +2660,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
   freePool(c->skinAllocs);
   D.skins.clear(); D.restFirst.clear(); D.skinOfMesh.clear(); D.stale.clear();
   D.dRest = D.dStaged = nullptr; D.dInfluences = nullptr; D.dJoints = nullptr; D.dSkinJobs = nullptr;
+  c->skinMats.assign(numSkins, std::vector<float>());
   c->refN = 0;
   if(numSkins == 0) return RT_OK;
   const rt_skin_influence* ip = nullptr;
@@ -2573,6 +2705,35 @@ int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const fl
       meshes.push_back(sk.primMesh);
     }
   }
+  // the matrices become the skin's stored pose once the call has succeeded (rt_update_morphs re-poses a morphed skin with them)
+  const auto keepMats = [&]() {
+    size_t at = 0;
+    for(uint32_t k = 0; k < count; k++) {
+      const size_t n = size_t(D.skins[ids[k]].jointCount) * 12;
+      c->skinMats[ids[k]].assign(mats + at, mats + at + n);
+      at += n;
+    }
+  };
+  {   // a listed skin whose mesh has a morph set with a stored weight that is not zero: morph, then skin.  Otherwise the path below, as without morph sets.
+    const rt_ctx::Morph& M = c->morph;
+    bool morphed = false;
+    for(uint32_t k = 0; k < count && !M.sets.empty(); k++) {
+      const int32_t set = M.setOfMesh[D.skins[ids[k]].primMesh];
+      if(set >= 0) for(float w : M.weights[size_t(set)]) morphed = morphed || w != 0.0f;
+    }
+    if(morphed) {
+      std::vector<PoseItem> items;
+      size_t at = 0;
+      for(uint32_t k = 0; k < count; k++) {
+        const int32_t set = M.setOfMesh[D.skins[ids[k]].primMesh];
+        items.push_back(PoseItem{int32_t(ids[k]), mats + at, set, set >= 0 ? M.weights[size_t(set)].data() : nullptr});
+        at += size_t(D.skins[ids[k]].jointCount) * 12;
+      }
+      if(const int rc = poseAndRefit(c, "rt_update_skins", items, nullptr)) return rc;
+      keepMats();
+      return RT_OK;
+    }
+  }
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));   // v1: joins the frames in flight
   int rc;
@@ -2590,7 +2751,118 @@ int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const fl
     a.numJobs = count; a.numThreads = threads; a.nonFinite = D.dOut;
     RT_HIP(c, launchSkin(s, a));
   }
-  return deformRefit(c, "rt_update_skins", meshes, &jobs, &ids, threads, 0u);
+  std::vector<StagedMesh> staged(count);
+  for(uint32_t k = 0; k < count; k++) staged[k] = StagedMesh{meshes[k], D.dStaged, jobs[k].restFirst, jobs[k].count, &D.stale[ids[k]]};
+  if((rc = deformRefit(c, "rt_update_skins", meshes, &staged, threads, 0u))) return rc;
+  keepMats();
+  return RT_OK;
+}
+
+/* ---- morph targets (include/rt_abi.h "Morph targets", csrc/morph.hip) ---- */
+int rt_set_morph_targets(rt_ctx* c, uint32_t numSets, const rt_morph_set* sets, uint64_t numDeltas, const rt_morph_delta* deltas)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_morph_targets: no scene uploaded");
+  if(numSets && !sets) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: NULL sets");
+  const rt_ctx::Deform& D = c->deform;
+  std::vector<int32_t> setOfMesh(c->primMeshes.size(), -1);
+  std::vector<uint32_t> restFirst(numSets, 0u);
+  uint64_t poolVerts = 0, totalTargets = 0;
+  for(uint32_t k = 0; k < numSets; k++) {
+    const rt_morph_set& ms = sets[k];
+    if(ms.primMesh >= c->primMeshes.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: prim mesh out of range");
+    if(setOfMesh[ms.primMesh] >= 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: prim mesh listed twice");
+    setOfMesh[ms.primMesh] = int32_t(k);
+    if(ms.targetCount == 0 || ms.targetCount > 4096u) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: targetCount must be 1 .. 4096");
+    if(ms.planes & ~uint32_t(RT_MORPH_NORMALS | RT_MORPH_TANGENTS)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: unknown planes bits");
+    const rt_prim_mesh& pm = c->primMeshes[ms.primMesh];
+    const uint64_t P = 1u + ((ms.planes & RT_MORPH_NORMALS) ? 1u : 0u) + ((ms.planes & RT_MORPH_TANGENTS) ? 1u : 0u);
+    const uint64_t rows = uint64_t(ms.targetCount) * P * pm.vertexCount;
+    if(uint64_t(ms.firstDelta) + rows > numDeltas || (rows && !deltas)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: delta range outside the array");
+    for(uint64_t r = 0; r < rows; r++) {
+      const float* d = deltas[size_t(ms.firstDelta + r)].d;
+      if(!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: non-finite delta");
+    }
+    const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
+    if(c->lights.bound == 0 && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
+    if(D.skinOfMesh.empty() || D.skinOfMesh[ms.primMesh] < 0) { restFirst[k] = uint32_t(poolVerts); poolVerts += pm.vertexCount; }
+    totalTargets += ms.targetCount;
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  int rc;
+  if((rc = syncHostVertices(c))) return rc;   // the stale marks go with the old sets
+  rt_ctx::Morph& M = c->morph;
+  const rt_morph_stats keep = M.stats;
+  freePool(c->morphAllocs);
+  M = rt_ctx::Morph{};
+  M.stats = keep;
+  c->refN = 0;
+  if(numSets == 0) return RT_OK;
+  const rt_morph_delta* dp = nullptr;
+  if((rc = upload(c, c->morphAllocs, deltas, size_t(numDeltas), &dp))) return rc;
+  M.dDeltas = const_cast<rt_morph_delta*>(dp);
+  if((rc = allocZeroed(c, c->morphAllocs, size_t(poolVerts), &M.dRest))) return rc;
+  if((rc = allocZeroed(c, c->morphAllocs, size_t(poolVerts), &M.dStaged))) return rc;
+  if((rc = allocZeroed(c, c->morphAllocs, numSets, &M.dJobs))) return rc;
+  if((rc = allocZeroed(c, c->morphAllocs, size_t(totalTargets), &M.dActive))) return rc;
+  for(uint32_t k = 0; k < numSets; k++) {   // the rest pose of a morph-only mesh: the context's current rows
+    const rt_prim_mesh& pm = c->primMeshes[sets[k].primMesh];
+    if(!D.skinOfMesh.empty() && D.skinOfMesh[sets[k].primMesh] >= 0) continue;
+    if(pm.vertexCount) RT_HIP(c, hipMemcpy(M.dRest + restFirst[k], c->ds.vertices + pm.vertexOffset, size_t(pm.vertexCount) * sizeof(rt_vertex), hipMemcpyDeviceToDevice));
+  }
+  RT_HIP(c, hipDeviceSynchronize());
+  M.sets.assign(sets, sets + numSets);
+  M.setOfMesh = setOfMesh; M.restFirst = restFirst; M.stale.assign(numSets, 0);
+  M.weights.resize(numSets);
+  for(uint32_t k = 0; k < numSets; k++) M.weights[k].assign(sets[k].targetCount, 0.0f);
+  return RT_OK;
+}
+
+int rt_update_morphs(rt_ctx* c, uint32_t count, const uint32_t* setIds, const float* weights)
+{
+  if(int rc = needTree(c, "rt_update_morphs")) return rc;
+  rt_ctx::Morph& M = c->morph;
+  const rt_ctx::Deform& D = c->deform;
+  if(M.sets.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: no morph sets (rt_set_morph_targets)");
+  if(count && (!setIds || !weights)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: NULL ids / weights");
+  std::vector<PoseItem> items;
+  std::vector<size_t> at(count, 0);
+  size_t total = 0;
+  {
+    std::vector<bool> seen(M.sets.size(), false);
+    for(uint32_t k = 0; k < count; k++) {
+      const uint32_t id = setIds[k];
+      if(id >= M.sets.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: set id out of range");
+      if(seen[id]) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: duplicate set id");
+      seen[id] = true;
+      const rt_morph_set& ms = M.sets[id];
+      for(uint32_t t = 0; t < ms.targetCount; t++)
+        if(!std::isfinite(weights[total + t])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: non-finite weight");
+      const int32_t skin = D.skinOfMesh.empty() ? -1 : D.skinOfMesh[ms.primMesh];
+      if(skin >= 0 && c->skinMats[size_t(skin)].empty())
+        return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: the set's prim mesh has a skin that rt_update_skins has not posed yet (pose the skin first)");
+      items.push_back(PoseItem{skin, skin >= 0 ? c->skinMats[size_t(skin)].data() : nullptr, int32_t(id), weights + total});
+      at[k] = total;
+      total += ms.targetCount;
+    }
+  }
+  uint32_t activeTargets = 0;
+  if(const int rc = poseAndRefit(c, "rt_update_morphs", items, &activeTargets)) return rc;   // (refused: only staging rows were written)
+  for(uint32_t k = 0; k < count; k++) M.weights[setIds[k]].assign(weights + at[k], weights + at[k] + M.sets[setIds[k]].targetCount);
+  M.stats = rt_morph_stats{};
+  M.stats.sets = count; M.stats.vertices = D.stats.vertices; M.stats.targetsApplied = activeTargets; M.stats.instances = D.stats.instances;
+  M.stats.ms = D.stats.ms;
+  (void)hipEventElapsedTime(&M.stats.morphMs, c->evMorph[0], c->evMorph[1]);
+  return RT_OK;
+}
+
+int rt_get_morph_stats(rt_ctx* c, rt_morph_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->morph.stats;
+  return RT_OK;
 }
 
 int rt_vertices_readback(rt_ctx* c, uint64_t firstVertex, uint64_t count, rt_vertex* dst)
@@ -2623,6 +2895,12 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
       const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
       if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
         return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a skin on an emissive prim mesh needs the binding (remove the skin first)");
+    }
+    for(const rt_morph_set& ms : c->morph.sets) {
+      const rt_prim_mesh& pm = c->primMeshes[ms.primMesh];
+      const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
+      if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)
+        return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a morph set on an emissive prim mesh needs the binding (remove the set first)");
     }
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, syncAll(c));

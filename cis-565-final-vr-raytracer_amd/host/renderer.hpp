@@ -70,6 +70,18 @@ class AccelStructure {
     if(rt_update_skins(m_ctx, count, skinIds, jointMatrices) != RT_OK) { fprintf(stderr, "AccelStructure::updateSkins: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
+  // Morph targets (include/rt_abi.h "Morph targets"): deltas once (after setSkins where a mesh has both), weights per frame; a morphed mesh that has a skin is
+  // skinned with the matrices of its last updateSkins.
+  bool setMorphTargets(const std::vector<rt_morph_set>& sets, const std::vector<rt_morph_delta>& deltas)
+  {
+    if(rt_set_morph_targets(m_ctx, uint32_t(sets.size()), sets.data(), deltas.size(), deltas.data()) != RT_OK) { fprintf(stderr, "AccelStructure::setMorphTargets: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  bool updateMorphs(const uint32_t* setIds, const float* weights, uint32_t count)
+  {
+    if(rt_update_morphs(m_ctx, count, setIds, weights) != RT_OK) { fprintf(stderr, "AccelStructure::updateMorphs: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
   // A new topology for the moved scene, built on the GPU (include/rt_abi.h "Rebuilding on the device"): the host's remedy when rt_refit_stats::fullRefit is set
   // or the refitted tree has become slow.  The previous tree stays in place when it fails.
   bool rebuild()

@@ -25,6 +25,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
+               "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -140,6 +141,10 @@ def hip_lib():
             L.rt_set_light_sources.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
             L.rt_lights_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
             L.rt_get_light_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_morph_targets"):   # morph targets (absent from older A/B libraries)
+            L.rt_set_morph_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+            L.rt_update_morphs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rt_get_morph_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -488,6 +493,31 @@ class Renderer:
     def deform_stats(self):
         s = abi.DeformStats()
         self._chk(hip_lib().rt_get_deform_stats(self._h, C.byref(s)), "rt_get_deform_stats")
+        return s
+
+    # ---- morph targets (include/rt_abi.h "Morph targets")
+    def set_morph_targets(self, sets, deltas):
+        """rt_set_morph_targets: sets = abi.MORPH_SET_DT records (one per morphed prim mesh), deltas = abi.MORPH_DELTA_DT rows (or n x 3 / n x 4 floats), target-major:
+        per target the position plane, then the normal plane, then the tangent plane, vertexCount rows each.  Skins first.  Empty: removes the sets"""
+        st = np.ascontiguousarray(sets, dtype=abi.MORPH_SET_DT).reshape(-1)
+        d = np.asarray(deltas)
+        if d.dtype != abi.MORPH_DELTA_DT:
+            f = np.asarray(d, dtype=np.float32).reshape(-1, d.shape[-1] if d.ndim > 1 else 4)
+            d = np.zeros(len(f), abi.MORPH_DELTA_DT)
+            d["d"] = f[:, :3]
+        d = np.ascontiguousarray(d).reshape(-1)
+        self._chk(hip_lib().rt_set_morph_targets(self._h, st.size, st.ctypes.data, d.size, d.ctypes.data), "rt_set_morph_targets")
+
+    def update_morphs(self, set_ids, weights):
+        """rt_update_morphs: stores the weights (per listed set targetCount floats, concatenated) and re-poses the listed meshes from their rest pose on the GPU;
+        a mesh that also has a skin is skinned with the matrices of its last update_skins"""
+        ids = np.ascontiguousarray(set_ids, dtype=np.uint32).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        self._chk(hip_lib().rt_update_morphs(self._h, ids.size, ids.ctypes.data, w.ctypes.data), "rt_update_morphs")
+
+    def morph_stats(self):
+        s = abi.MorphStats()
+        self._chk(hip_lib().rt_get_morph_stats(self._h, C.byref(s)), "rt_get_morph_stats")
         return s
 
     # ---- light sources (include/rt_abi.h "Light sources", DESIGN.md §22)

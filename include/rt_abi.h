@@ -794,7 +794,7 @@ int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectTo
 int rt_object_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
 /* ------------------------------------------------------------------------------------------------------------------
  * Deforming meshes (added within ABI 2.4, no version bump; csrc/deform.hip).  rt_update_instances moves rigid instances; these calls change the
- * VERTICES of a prim mesh on the device — rows supplied by the host (rt_update_vertices: cloth, morph targets, anything the host computes) or posed on the GPU from
+ * VERTICES of a prim mesh on the device — rows supplied by the host (rt_update_vertices: cloth, anything the host computes; morph targets have a device path of their own, "Morph targets" below) or posed on the GPU from
  * a rest pose and a few joint matrices (rt_set_skins once, rt_update_skins per frame) — then rewrite the leaf records of every instance of that mesh and refit the
  * BVH8 above them with the kernels of rt_update_instances.  No upload of the scene, no rebuild, no re-derived alpha records or micro-maps.  Results are a function of
  * the triangle set only: frames and ray queries afterwards are bit for bit those of a context that uploaded and built the deformed scene.
@@ -900,6 +900,62 @@ enum { RT_LIGHTS_TRIG = 0, RT_LIGHTS_PUNC = 1 };
 int rt_set_light_sources(rt_ctx* ctx, uint32_t numTrig, const rt_light_source* sources);
 int rt_lights_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 int rt_get_light_stats(rt_ctx* ctx, rt_light_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Morph targets (added within ABI 2.4, no version bump; csrc/morph.hip).  glTF's second deformation mechanism (blend shapes: faces, correctives,
+ * cloth presets) on the GPU: a prim mesh has a SET of targets, a target is a plane of position deltas (plus, optionally, a plane of normal deltas and one of
+ * tangent deltas), and a pose is one weight per target.  rt_set_morph_targets uploads the deltas once; rt_update_morphs takes weights, re-poses the meshes from
+ * their rest pose on the device and refits like rt_update_skins.  A mesh may be morphed AND skinned (a character): morph, then skin.
+ *
+ * Delta layout, target-major: with P = 1 + (planes & RT_MORPH_NORMALS ? 1 : 0) + (planes & RT_MORPH_TANGENTS ? 1 : 0) and V = the prim mesh's vertexCount, target
+ *   t of set k occupies rows [firstDelta + t P V, firstDelta + (t + 1) P V) of `deltas`: the position plane (V rows, row v belongs to vertex v), then the normal
+ *   plane if present, then the tangent plane if present.  A row is 16 bytes; `pad` is not read as a value.
+ * rt_set_morph_targets(ctx, numSets, sets, numDeltas, deltas): valid after rt_upload_scene (RT_ERR_NO_SCENE otherwise).  Replaces all sets (numSets == 0 removes
+ *   them); every set starts with all weights zero.  RT_ERR_INVALID_ARG, nothing changed, for: a prim mesh out of range or listed twice; targetCount == 0 or
+ *   > 4096; unknown `planes` bits; a delta range (targetCount P V rows from firstDelta) outside the array; a non-finite d[]; a mesh whose material is emissive by
+ *   the scene's light rule while no light-source binding is set (the rule and the message of rt_set_skins).
+ *   Rest pose: a mesh that has a skin uses the skin's rest pose and staging range; for any other mesh the call captures the context's current rows, as
+ *   rt_set_skins does, into a pool of its own with a staging range of the same size.  Order: skins first.  rt_set_skins while any morph set exists is
+ *   RT_ERR_INVALID_ARG (remove the sets, set the skins, set the sets again).  rt_update_vertices on a mesh that has a morph set is RT_ERR_INVALID_ARG, as it is for
+ *   a skin.  rt_set_light_sources(numTrig == 0) while a morph set on an emissive mesh exists is RT_ERR_INVALID_ARG, like a skin.  rt_upload_scene drops the sets;
+ *   rt_build_accel, rt_rebuild_accel and rt_resize keep them (and their weights).
+ * rt_update_morphs(ctx, count, setIds, weights): weights = for every listed set, in the order listed, targetCount floats, concatenated.  Valid after
+ *   rt_build_accel.  RT_ERR_INVALID_ARG for: no sets; an id out of range or listed twice; a non-finite weight; a set whose mesh has a skin that no successful
+ *   rt_update_skins has listed yet ("pose the skin first"); a pose that yields a non-finite position (the staged-then-commit rule and the counter of
+ *   rt_update_skins).  A refused call leaves the stored weights, the vertices, the tree, the light records and the stats as they were.  Otherwise the call stores
+ *   the weights in the context and re-poses every listed mesh from its rest pose.
+ *   Morph then skin: when the mesh also has a skin, the morphed rows are the skin's input, with the joint matrices of the last successful rt_update_skins that
+ *   listed that skin (the context keeps them per skin).  Conversely rt_update_skins on a mesh that has a morph set applies the stored weights first; with all
+ *   stored weights zero (or -0) it runs exactly the path it runs without morph sets and produces the same bits.
+ *   The arithmetic, fp32, no contraction, in the order written, for a vertex with rest row (p, normal, texcoord, tangent, colour): the ACTIVE targets of a set are
+ *   those whose weight is not zero (w != 0.0f, so -0 is inactive), in ascending target index a < b < ...; inactive targets are skipped, not multiplied by zero
+ *   (-0 + 0 d would differ), and the kernel never sees them: the host builds the active list.
+ *     p' = (((p + w_a dP_a) + w_b dP_b) + ...) per component, each product rounded before its add;
+ *     with the normal plane and normal != 0xffffffff: n = decompress_unit_vec(normal), m = ((n + w_a dN_a) + ...), then the rule of rt_update_skins:
+ *     d = (m.x m.x + m.y m.y) + m.z m.z, q = 1 / sqrt(d), packed' = compress_unit_vec(m q), but the rest value is kept when d is not > 0, d is infinite or q is
+ *     infinite.  Without the plane, with the sentinel, or when the set has NO active target the packed value is copied: no decode / encode round trip.
+ *     The tangent follows the same rules with its plane.  texcoord (with the handedness bit) and colour are copied.
+ *   A set with no active target yields the rest row bit for bit.
+ *   Everything else — joining the frames in flight, the reference-mode reset, the histories, the object-motion state, the refit, the pad, the light records
+ *   (with a binding) and the host-copy refresh — follows the "All three:" paragraph of "Deforming meshes".  No vertex crosses the bus: rt_get_deform_stats
+ *   afterwards describes the call like an rt_update_skins (vertexBytesCopied = 0; skinMs = the morph kernel, the skinning kernel and the commit copy).
+ *   Scope: the single-GPU context only, like skins.
+ * rt_get_morph_stats: what the last rt_update_morphs that succeeded did.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t primMesh, targetCount, firstDelta, planes; } rt_morph_set;   /* 16 B; planes: bit 0 = normal deltas, bit 1 = tangent deltas */
+typedef struct { float d[3]; float pad; } rt_morph_delta;                              /* 16 B; pad is not read as a value */
+typedef struct {
+  uint32_t sets;             /* sets the call listed */
+  uint32_t vertices;         /* vertices posed */
+  uint32_t targetsApplied;   /* active targets (weight != 0) over the listed sets */
+  uint32_t instances;        /* instances refitted */
+  float    morphMs;          /* HIP-event time of the morph kernel */
+  float    ms;               /* HIP-event time of the whole call on the main stream */
+  uint32_t reserved[2];
+} rt_morph_stats;            /* 32 B */
+enum { RT_MORPH_NORMALS = 1, RT_MORPH_TANGENTS = 2 };
+int rt_set_morph_targets(rt_ctx* ctx, uint32_t numSets, const rt_morph_set* sets, uint64_t numDeltas, const rt_morph_delta* deltas);
+int rt_update_morphs(rt_ctx* ctx, uint32_t count, const uint32_t* setIds, const float* weights);
+int rt_get_morph_stats(rt_ctx* ctx, rt_morph_stats* out);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
@@ -934,6 +990,9 @@ static_assert(sizeof(rt_deform_stats) == 32, "rt_deform_stats");
 static_assert(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 static_assert(sizeof(rt_light_source) == 8, "rt_light_source");
 static_assert(sizeof(rt_light_stats) == 32, "rt_light_stats");
+static_assert(sizeof(rt_morph_set) == 16, "rt_morph_set");
+static_assert(sizeof(rt_morph_delta) == 16, "rt_morph_delta");
+static_assert(sizeof(rt_morph_stats) == 32, "rt_morph_stats");
 #endif
 
 #endif /* RT_ABI_H */
