@@ -135,7 +135,7 @@ PROC_CORNELL, PROC_HELMET, PROC_SPONZA, PROC_BISTRO_EXT, PROC_BISTRO_INT, PROC_B
 # rt_accel_readback ids; record sizes of the device tree (csrc/bvh8.h, csrc/dev_scene.h)
 ACCEL_NODES, ACCEL_TRIS, ACCEL_INSTANCES = range(3)
 ACCEL_RECORD_BYTES = (80, 64, 112)
-OBJECT_MOTION_OFF, OBJECT_MOTION_ON = range(2)   # rt_set_object_motion
+OBJECT_MOTION_OFF, OBJECT_MOTION_ON, OBJECT_MOTION_VERTEX = 0, 1, 3   # rt_set_object_motion (VERTEX: per-vertex motion vectors; 2 is not a mode)
 
 
 class RebuildStats(C.Structure):  # rt_rebuild_stats, 32 B

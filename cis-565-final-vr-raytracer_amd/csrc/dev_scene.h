@@ -107,4 +107,19 @@ struct DevObjMotion {
   uint32_t numInst, pad;
 };
 
+// per-vertex motion vectors (rt_set_object_motion mode RT_OBJECT_MOTION_VERTEX; the RT_VM builds of stages.hip take it as a kernel argument of its own)
+struct VmRow {   // row i: the objectToWorld instance i had at the last rendered frame (its current one when it was not moved since) + flags — 64 B, 16-byte aligned
+  float P[12];
+  uint32_t flags;           // bit 0: the instance was moved since the last rendered frame, bit 1: its prim mesh was deformed since
+  uint32_t pad[3];
+};
+enum : uint32_t { VM_MOVED = 1u, VM_DEFORMED = 2u };
+struct DevVtxMotion {
+  uint32_t* instImage;      // as DevObjMotion::instImage (rt_object_motion_readback keeps its contract)
+  float4* delta;            // W x H: (x_prev - state.position, 0), zero at a miss; written by the direct stage, read by the indirect stage of the same frame at 2p
+  const VmRow* rows;        // numInst rows, or nullptr when nothing is in motion or deformed this frame (every pixel then takes the camera's values: delta 0)
+  const float4* prevPos;    // one row per scene vertex: the position at the last rendered frame, valid for the meshes whose instances carry VM_DEFORMED
+  uint32_t numInst, pad;
+};
+
 }  // namespace rt

@@ -200,6 +200,18 @@ struct rt_ctx {
   bool omInstValid = false;  // a frame has written omInst since rt_resize
   void* omTable = nullptr; size_t omTableRows = 0;
   std::vector<OmCamera> omHost;
+  // per-vertex motion vectors (mode RT_OBJECT_MOTION_VERTEX; the RT_VM builds of csrc/stages.hip, csrc/vmotion.hip).  Everything below exists once
+  // the mode has been switched on (vmEver).  vmPlane: one float4 per scene vertex; the first deforming call for a mesh after a rendered frame copies the mesh's
+  // live positions into it ahead of its commit and sets vmDeformed[mesh] (whether the mode is on or off, like omPrev); a rendered frame clears the flags.
+  // vmDelta: the delta image, lifetime and rotation of omInst.  vmTable: the per-instance rows, rewritten only by frames that follow a draining update.
+  bool vmEver = false;
+  void* vmPlane = nullptr;
+  std::vector<uint8_t> vmDeformed;
+  bool vmPending = false;    // some vmDeformed flag is set
+  void* vmDelta = nullptr; void* vmDeltaSpare = nullptr; void* vmDeltaSpare2 = nullptr;
+  bool vmDeltaValid = false; // a vertex-mode frame has written vmDelta since rt_resize
+  void* vmTable = nullptr; size_t vmTableRows = 0;
+  std::vector<VmRow> vmHost;
 };
 
 static void harvestTimings(rt_ctx* c)
@@ -292,6 +304,15 @@ static OmStageLauncher omStageLauncher(const rt_ctx* c, const rt_state& st, int 
   const bool lat = latencyBuild(c, st, stage, 0, 0);
   if(c->ds.sky) return lat ? rt::sky_lat_om::launchStage : rt::sky_om::launchStage;
   return lat ? rt::base_lat_om::launchStage : rt::base_om::launchStage;
+}
+
+// ... and with per-vertex motion vectors on: the four RT_VM builds
+typedef hipError_t (*VmStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const DevVtxMotion&, const rt_state&, const rt_scene_camera&, int, int, int, int);
+static VmStageLauncher vmStageLauncher(const rt_ctx* c, const rt_state& st, int stage)
+{
+  const bool lat = latencyBuild(c, st, stage, 0, 0);
+  if(c->ds.sky) return lat ? rt::sky_lat_vm::launchStage : rt::sky_vm::launchStage;
+  return lat ? rt::base_lat_vm::launchStage : rt::base_vm::launchStage;
 }
 
 // ---- host side of rt_build_accel, cached by scene content (buildHostAccel below) ---------------------------------------------------------------------
@@ -391,6 +412,31 @@ static void freeObjectMotion(rt_ctx* c)
   for(void** p : {&c->omInst, &c->omInstSpare, &c->omInstSpare2}) if(*p) { (void)hipFree(*p); *p = nullptr; }
   c->omInstValid = false;
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;
+  for(void** p : {&c->vmDelta, &c->vmDeltaSpare, &c->vmDeltaSpare2}) if(*p) { (void)hipFree(*p); *p = nullptr; }
+  c->vmDeltaValid = false;
+  std::fill(c->vmDeformed.begin(), c->vmDeformed.end(), uint8_t(0)); c->vmPending = false;   // (the plane is sized by the scene: it stays)
+}
+// The previous-position plane of per-vertex motion vectors: one float4 per vertex of the uploaded scene, zeroed (a row is read only after a capture wrote it).
+// Made by the call that first switches the mode on and again by every rt_upload_scene after it (callers have drained the context).
+static int allocVertexMotionPlane(rt_ctx* c)
+{
+  if(c->vmPlane || !c->haveScene) return RT_OK;
+  const size_t bytes = std::max<size_t>(c->vertices.size() * sizeof(float4), 256);
+  RT_HIP(c, hipMalloc(&c->vmPlane, bytes));
+  RT_HIP(c, hipMemset(c->vmPlane, 0, bytes));
+  RT_HIP(c, hipDeviceSynchronize());
+  c->vmDeformed.assign(c->primMeshes.size(), 0); c->vmPending = false;
+  return RT_OK;
+}
+// What a deforming call does for prim mesh `mesh` before it changes the live rows (on stream s, which the change follows): the first one after a rendered frame
+// copies the mesh's live positions into the plane; later ones before the next frame keep the rendered frame's positions, as omPrev keeps its matrices.
+static int capturePrevPositions(rt_ctx* c, hipStream_t s, uint32_t mesh)
+{
+  if(!c->vmPlane || mesh >= c->vmDeformed.size() || c->vmDeformed[mesh]) return RT_OK;
+  const rt_prim_mesh& pm = c->primMeshes[mesh];
+  RT_HIP(c, launchCapturePositions(s, c->ds.vertices, static_cast<float4*>(c->vmPlane), pm.vertexOffset, pm.vertexCount));
+  c->vmDeformed[mesh] = 1; c->vmPending = true;
+  return RT_OK;
 }
 // the TAA history (the caller has drained the context)
 static void freeTaaHistory(rt_ctx* c)
@@ -532,7 +578,8 @@ int rt_destroy(rt_ctx* c)
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
   freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
-  for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable}) if(p) (void)hipFree(p);
+  for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable, c->vmPlane, c->vmDelta, c->vmDeltaSpare,
+                  c->vmDeltaSpare2, c->vmTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
   for(hipStream_t& q : c->indStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
   for(hipStream_t& q : c->sideStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
@@ -641,6 +688,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->svgfValid = false;
   c->taaValid = false;
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // object motion: nothing of the new scene has moved
+  if(c->vmPlane) { (void)hipFree(c->vmPlane); c->vmPlane = nullptr; }   // ... or has been deformed; the plane is made again for the new vertex array below
+  c->vmDeformed.clear(); c->vmPending = false;
   c->ds = DevScene{};
   c->ds.sky = (c->sunAndSky.in_use == 1) ? static_cast<const SkyPre*>(c->dSky) : nullptr;
   c->primMeshes.assign(d->primMeshes, d->primMeshes + d->numPrimMeshes);
@@ -720,6 +769,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   RT_HIP(c, hipDeviceSynchronize());
   c->haveScene = true;
   reopenPriorityDecision(c);   // (the context is drained: syncAll above / hipDeviceSynchronize below)
+  if(c->vmEver && (rc = allocVertexMotionPlane(c))) return rc;
   return resetSeedPlane(c);
 }
 
@@ -955,7 +1005,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   RT_HIP(c, hipDeviceSynchronize());  // memsets above ran on the null stream; the ctx stream does not wait for it implicitly
   c->W = w; c->H = h;
   if((rc = resetSeedPlane(c))) return rc;
-  if(c->objMotion != RT_OBJECT_MOTION_OFF && (rc = allocObjectMotion(c))) return rc;
+  if((c->objMotion != RT_OBJECT_MOTION_OFF || c->vmEver) && (rc = allocObjectMotion(c))) return rc;
   return ensureStackOverflow(c);
 }
 
@@ -1091,6 +1141,14 @@ static int allocObjectMotion(rt_ctx* c)
     if(*p) continue;
     RT_HIP(c, hipMalloc(p, std::max<size_t>(bytes, 256)));
     RT_HIP(c, hipMemset(*p, 0xff, std::max<size_t>(bytes, 256)));
+  }
+  if(c->vmEver) {   // the delta images of per-vertex motion vectors: zero = "nothing moved"
+    const size_t db = std::max<size_t>(size_t(c->W) * c->H * sizeof(float4), 256);
+    for(void** p : {&c->vmDelta, &c->vmDeltaSpare, &c->vmDeltaSpare2}) {
+      if(*p) continue;
+      RT_HIP(c, hipMalloc(p, db));
+      RT_HIP(c, hipMemset(*p, 0, db));
+    }
   }
   RT_HIP(c, hipDeviceSynchronize());
   return RT_OK;
@@ -1253,6 +1311,38 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       }
     }
   }
+  // Per-vertex motion vectors (mode RT_OBJECT_MOTION_VERTEX): the two stages come from the RT_VM builds, which write the instance image and the delta image; when
+  // an instance is in motion or its mesh was deformed since the last rendered frame they also read the per-instance rows {previous objectToWorld, flags}, filled
+  // here and uploaded like the camera table, and the previous-position plane the deforming calls filled.
+  const bool vm = c->objMotion == RT_OBJECT_MOTION_VERTEX && !c->counting && c->omInst && c->vmDelta;
+  bool vmMotion = false;
+  if(c->objMotion == RT_OBJECT_MOTION_VERTEX) {
+    const size_t nInst = c->instances.size();
+    const bool moves = c->omPending && c->omMoved.size() == nInst, bends = c->vmPending && c->vmPlane;
+    auto flagsOf = [&](size_t i) -> uint32_t {
+      uint32_t f = 0;
+      if(moves && c->omMoved[i] && std::memcmp(c->omPrev[i].data(), c->instances[i].objectToWorld, 48) != 0) f |= VM_MOVED;
+      if(bends && c->vmDeformed[c->instances[i].primMesh]) f |= VM_DEFORMED;
+      return f;
+    };
+    if(moves || bends) for(size_t i = 0; i < nInst && !vmMotion; i++) vmMotion = flagsOf(i) != 0u;
+    if(vmMotion && c->counting)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_render_frame: instances are in motion or meshes deformed with per-vertex motion vectors on (rt_set_object_motion) and counting on (rt_set_counting): the counting build has no motion-vector form");
+    if(vmMotion) {
+      if(c->vmTableRows < nInst) {
+        RT_HIP(c, syncAll(c));
+        if(c->vmTable) { (void)hipFree(c->vmTable); c->vmTable = nullptr; c->vmTableRows = 0; }
+        RT_HIP(c, hipMalloc(&c->vmTable, nInst * sizeof(VmRow)));
+        c->vmTableRows = nInst;
+      }
+      c->vmHost.resize(nInst);
+      for(size_t i = 0; i < nInst; i++) {
+        VmRow& r = c->vmHost[i];
+        r.flags = flagsOf(i); r.pad[0] = r.pad[1] = r.pad[2] = 0u;
+        memcpy(r.P, (r.flags & VM_MOVED) ? c->omPrev[i].data() : c->instances[i].objectToWorld, 48);
+      }
+    }
+  }
   const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
@@ -1270,17 +1360,21 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       void*& g = c->bufs[RT_BUF_GBUFFER0 + (frames & 1)]; void* t = g; g = c->spareG; c->spareG = c->spareG2; c->spareG2 = t;
       void*& m = c->bufs[RT_BUF_MOTION]; t = m; m = c->spareMotion; c->spareMotion = c->spareMotion2; c->spareMotion2 = t;
       if(c->omInst) { t = c->omInst; c->omInst = c->omInstSpare; c->omInstSpare = c->omInstSpare2; c->omInstSpare2 = t; }
+      if(c->vmDelta) { t = c->vmDelta; c->vmDelta = c->vmDeltaSpare; c->vmDeltaSpare = c->vmDeltaSpare2; c->vmDeltaSpare2 = t; }
       std::swap(c->bufs[RT_BUF_DIRECT_RESULT0 + (frames & 1)], c->spareDirRes);
     } else {
       std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
       std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
       if(c->omInst) std::swap(c->omInst, c->omInstSpare);
+      if(c->vmDelta) std::swap(c->vmDelta, c->vmDeltaSpare);
     }
   } else {
     RT_HIP(c, joinInFlight(c));
   }
   const DevFrame F = makeFrame(c, frames);
   const DevObjMotion OM{static_cast<uint32_t*>(c->omInst), omMotion ? static_cast<const OmCamera*>(c->omTable) : nullptr, uint32_t(c->instances.size()), 0u};
+  const DevVtxMotion VM{static_cast<uint32_t*>(c->omInst), static_cast<float4*>(c->vmDelta), vmMotion ? static_cast<const VmRow*>(c->vmTable) : nullptr,
+                        static_cast<const float4*>(c->vmPlane), uint32_t(c->instances.size()), 0u};
   int k = 0, lastMain = 0, lastSide = 0, lastInd = 0;
   auto record = [&](hipStream_t strm, int stage) -> int {   // end-of-launch timestamp, timed against the previous one of the stream
     const hipError_t e = hipEventRecord(E.ev[k], strm);
@@ -1290,8 +1384,10 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     return RT_OK;
   };
   auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    hipError_t e = (om && (stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT)) ? omStageLauncher(c, *st, stage)(strm, c->ds, F, OM, *st, cam, stage, level, 0, 0)
-                                                                                     : stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
+    const bool traced = stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT;
+    hipError_t e = (om && traced) ? omStageLauncher(c, *st, stage)(strm, c->ds, F, OM, *st, cam, stage, level, 0, 0)
+                 : (vm && traced) ? vmStageLauncher(c, *st, stage)(strm, c->ds, F, VM, *st, cam, stage, level, 0, 0)
+                                  : stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
     if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     return record(strm, stage);
   };
@@ -1302,9 +1398,12 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   // Once the stage is issued the frame has been rendered as far as the motion state goes: every previous matrix becomes the current one.
   auto direct = [&](hipStream_t strm) -> int {
     if(om && omMotion) RT_HIP(c, hipMemcpyAsync(c->omTable, c->omHost.data(), c->omHost.size() * sizeof(OmCamera), hipMemcpyHostToDevice, strm));
+    if(vm && vmMotion) RT_HIP(c, hipMemcpyAsync(c->vmTable, c->vmHost.data(), c->vmHost.size() * sizeof(VmRow), hipMemcpyHostToDevice, strm));
     const int r = run(strm, RT_STAGE_DIRECT, 0);
     if(r == RT_OK) {
       if(om) c->omInstValid = true;
+      if(vm) c->omInstValid = c->vmDeltaValid = true;
+      if(c->vmPending) { std::fill(c->vmDeformed.begin(), c->vmDeformed.end(), uint8_t(0)); c->vmPending = false; }   // every mesh is undeformed for the next frame
       if(c->omPending) { std::fill(c->omMoved.begin(), c->omMoved.end(), uint8_t(0)); c->omPending = false; }
     }
     return r;
@@ -1583,6 +1682,7 @@ int rt_rotate_buffers(rt_ctx* c, int frames)
   std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
   std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
   if(c->omInst) std::swap(c->omInst, c->omInstSpare);
+  if(c->vmDelta) std::swap(c->vmDelta, c->vmDeltaSpare);
   return RT_OK;
 }
 
@@ -1918,15 +2018,31 @@ int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases
 int rt_set_object_motion(rt_ctx* c, int mode)
 {
   if(!c) return RT_ERR_INVALID_ARG;
-  if(mode != RT_OBJECT_MOTION_OFF && mode != RT_OBJECT_MOTION_ON) return fail(c, RT_ERR_INVALID_ARG, "rt_set_object_motion: mode must be RT_OBJECT_MOTION_OFF or RT_OBJECT_MOTION_ON");
+  if(mode != RT_OBJECT_MOTION_OFF && mode != RT_OBJECT_MOTION_ON && mode != RT_OBJECT_MOTION_VERTEX)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_set_object_motion: mode must be RT_OBJECT_MOTION_OFF, RT_OBJECT_MOTION_ON or RT_OBJECT_MOTION_VERTEX");
   if(mode == c->objMotion) return RT_OK;
-  if(mode == RT_OBJECT_MOTION_ON && c->W > 0 && !c->omInst) {   // (a context that was resized before the mode was first switched on)
+  const bool firstVertex = mode == RT_OBJECT_MOTION_VERTEX && !c->vmEver;
+  if(firstVertex || (mode != RT_OBJECT_MOTION_OFF && c->W > 0 && (!c->omInst || (mode == RT_OBJECT_MOTION_VERTEX && !c->vmDelta)))) {
+    // (a context that was resized, or given its scene, before the mode was first switched on)
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, syncAll(c));
+    if(mode == RT_OBJECT_MOTION_VERTEX) c->vmEver = true;
     int rc;
-    if((rc = allocObjectMotion(c))) return rc;
+    if(mode == RT_OBJECT_MOTION_VERTEX && (rc = allocVertexMotionPlane(c))) return rc;
+    if(c->W > 0 && (rc = allocObjectMotion(c))) return rc;
   }
   c->objMotion = mode;
+  return RT_OK;
+}
+
+int rt_vertex_motion_readback(rt_ctx* c, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(!c->vmDelta || !c->vmDeltaValid) return fail(c, RT_ERR_NO_TARGET, "rt_vertex_motion_readback: no frame has been rendered with per-vertex motion vectors on since the last rt_resize");
+  if(bytes != size_t(c->W) * c->H * sizeof(float4)) return fail(c, RT_ERR_INVALID_ARG, "rt_vertex_motion_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, c->vmDelta, bytes, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 
@@ -2487,6 +2603,7 @@ static int deformRefit(rt_ctx* c, const char* who, const std::vector<uint32_t>& 
   if(staged) {   // commit: staging rows -> live rows, on the stream ahead of the refit
     for(const StagedMesh& sm : *staged) {
       const rt_prim_mesh& pm = c->primMeshes[sm.mesh];
+      if(sm.count) if(const int rc = capturePrevPositions(c, s, sm.mesh)) return rc;   // per-vertex motion vectors: the rendered frame's positions, ahead of the commit
       if(sm.count) RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + pm.vertexOffset, sm.pool + sm.first, size_t(sm.count) * sizeof(rt_vertex), hipMemcpyDeviceToDevice, s));
       *sm.stale = 1;
     }
@@ -2615,6 +2732,7 @@ int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint3
   std::vector<uint32_t> meshes;
   if(count) {
     memcpy(c->vertices.data() + base, rows, size_t(count) * sizeof(rt_vertex));
+    if((rc = capturePrevPositions(c, s, primMesh))) return rc;   // per-vertex motion vectors: the rendered frame's positions, ahead of the new rows
     RT_HIP(c, hipMemcpyAsync(const_cast<rt_vertex*>(c->ds.vertices) + base, c->vertices.data() + base, size_t(count) * sizeof(rt_vertex), hipMemcpyHostToDevice, s));
     meshes.push_back(primMesh);
   }
@@ -2943,7 +3061,8 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
     LightRecArgs la{};
     la.records = dScratch; la.sources = dSrc; la.instances = dInst; la.primMeshes = c->ds.primMeshes; la.vertices = c->ds.vertices; la.indices = c->ds.indices;
     la.dirtyBits = nullptr; la.counter = dCounter; la.numRecs = numTrig; la.all = 1u;
-    he = launchLightRecords(c->stream, la);
+    he = hipDeviceSynchronize();   // allocZeroed cleared dScratch and dCounter on the null stream; the context's stream does not wait for it implicitly (as in rt_resize)
+    if(he == hipSuccess) he = launchLightRecords(c->stream, la);
     if(he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if(he == hipSuccess) he = hipMemcpy(eval.data(), dScratch, size_t(numTrig) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
     for(hipEvent_t& e : c->evLights) if(he == hipSuccess && !e) he = hipEventCreate(&e);

@@ -169,6 +169,34 @@ RT_DEV f3 omLastPosition(const DevObjMotion& OM, const rt_scene_camera& cam, uin
   const float4 v = gLoadF4(&OM.cams[inst].lastPosition);
   return mk3(v.x, v.y, v.z);
 }
+// ---- per-vertex motion vectors (the RT_VM builds of stages.hip) ------------------------------------
+// x_prev of the primary hit in c.hit: GetState's expression for state.position with the previous frame's vertices and the previous frame's objectToWorld,
+//   x_prev = xformPoint(P, (q0 * bary.x + q1 * bary.y) + q2 * bary.z)
+// computed only for a pixel whose instance carries a flag; every other pixel gets `cur` (state.position) back, copied.  The flags word comes first and an
+// unflagged instance skips every gather (the branch diverges within a wave and changes no result).  The row and the previous positions are read per lane
+// (neighbouring pixels see different instances and triangles): vector loads from the global address space, one dword for the flags, 3 x dwordx4 for P and one
+// dwordx4 per vertex (the plane row, or the live vertex row of an instance that only moved).
+RT_DEV f3 vmPrevPosition(const Ctx& c, const DevVtxMotion& VM, uint32_t inst, f3 cur)
+{
+  if(VM.rows == nullptr || inst >= VM.numInst) return cur;
+  const VmRow* row = VM.rows + inst;
+  const uint32_t flags = gLoadU32(&row->flags);
+  if(flags == 0u) return cur;
+  float P[12];
+#pragma unroll
+  for(int k = 0; k < 3; k++) { const float4 v = gLoadF4(row->P + 4 * k); P[4 * k] = v.x; P[4 * k + 1] = v.y; P[4 * k + 2] = v.z; P[4 * k + 3] = v.w; }
+  const uint32_t prim = gLoadU32(&c.S.triRef[c.hit.gid].prim);
+  const rt_prim_mesh* geo = c.S.primMeshes + gLoadU32(&c.S.instances[inst].primMesh);
+  const uint32_t vertexOffset = gLoadU32(&geo->vertexOffset);
+  const uint32_t* tri = c.S.indices + (size_t(gLoadU32(&geo->firstIndex)) + 3u * size_t(prim));
+  const size_t v0 = size_t(vertexOffset) + gLoadU32(tri), v1 = size_t(vertexOffset) + gLoadU32(tri + 1), v2 = size_t(vertexOffset) + gLoadU32(tri + 2);
+  float4 a, b, d;
+  if(flags & VM_DEFORMED) { a = gLoadF4(VM.prevPos + v0); b = gLoadF4(VM.prevPos + v1); d = gLoadF4(VM.prevPos + v2); }
+  else { a = gLoadF4(c.S.vertices + v0); b = gLoadF4(c.S.vertices + v1); d = gLoadF4(c.S.vertices + v2); }   // (position + the packed normal of the 32-byte row)
+  const f3 bary = mk3((1.0f - c.hit.u) - c.hit.v, c.hit.u, c.hit.v);
+  const f3 q = (mk3(a.x, a.y, a.z) * bary.x + mk3(b.x, b.y, b.z) * bary.y) + mk3(d.x, d.y, d.z) * bary.z;
+  return xformPoint(P, q);
+}
 // direct_stage.comp:47-84 == direct_reuse.comp:52-89
 RT_DEV bool findTemporalNeighborDirect(const DevFrame& F, const rt_state& st, f3 norm, float reprojDepth, uint32_t matId, i2 lastCoord,
                                        rt_direct_reservoir& resv, uint32_t& lid)

@@ -31,6 +31,19 @@ RT_DECL_LAUNCH_OM(sky_om)
 RT_DECL_LAUNCH_OM(base_lat_om)
 RT_DECL_LAUNCH_OM(sky_lat_om)
 #undef RT_DECL_LAUNCH_OM
+// the four per-vertex-motion builds (RT_VM, stages_*vm.hip): the same two stages, no counting form
+#define RT_DECL_LAUNCH_VM(ns)                                                                                                                                  \
+  namespace ns {                                                                                                                                               \
+  hipError_t launchStage(hipStream_t stream, const DevScene& S, const DevFrame& F, const DevVtxMotion& VM, const rt_state& st, const rt_scene_camera& cam,      \
+                         int stage, int level, int rowBegin, int rowEnd);                                                                                      \
+  }
+RT_DECL_LAUNCH_VM(base_vm)
+RT_DECL_LAUNCH_VM(sky_vm)
+RT_DECL_LAUNCH_VM(base_lat_vm)
+RT_DECL_LAUNCH_VM(sky_lat_vm)
+#undef RT_DECL_LAUNCH_VM
+// csrc/vmotion.hip: rows [first, first + count) of the previous-position plane <- the positions of the live vertex rows (the capture ahead of a deforming commit)
+hipError_t launchCapturePositions(hipStream_t stream, const rt_vertex* vertices, float4* plane, uint32_t first, uint32_t count);
 // filters.hip, compiled once: every other stage (both A-Trous chains, compose; hipErrorInvalidValue for a level outside the chain or any other stage), and the
 // tile-order pass that every build of the indirect stage launches ahead of k_indirect_stage
 hipError_t launchFilterStage(hipStream_t stream, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int rowBegin, int rowEnd);

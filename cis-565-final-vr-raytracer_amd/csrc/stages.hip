@@ -9,7 +9,8 @@
 // an XCD-aware tile order: consecutive workgroup ids land on different XCDs (observed b % 8), so XCD x gets the x-th
 // contiguous band of tile rows and its private 4 MiB L2 sees one compact screen region + the BVH subtrees under it.
 // This file is compiled six times: as is, and through stages_{sky,cnt,sky_cnt,lat,sky_lat}.hip with RT_SKY / RT_COUNT / RT_LAT set; what those switches do not reach is in filters.hip.
-// Four more builds, stages_{om,sky_om,lat_om,sky_lat_om}.hip, set RT_OM (below) for contexts with object motion vectors on.
+// Four more builds, stages_{om,sky_om,lat_om,sky_lat_om}.hip, set RT_OM (below) for contexts with object motion vectors on, and four,
+// stages_{vm,sky_vm,lat_vm,sky_lat_vm}.hip, set RT_VM for contexts with per-vertex motion vectors on.
 //   RT_SKY = 1    procedural sun & sky code paths compiled in.  Keeping sun_and_sky() out of the default kernels saves 13 VGPRs
 //                 in k_direct_stage — the procedural sky is the rarely used mode (default in_use = 0, sample_example.hpp:202).
 //   RT_COUNT = 1  traversal / shading counters (rt_set_counting) are flushed at the end of the traced kernels.  Without the
@@ -32,12 +33,25 @@
 #ifndef RT_OM
 #define RT_OM 0
 #endif
-#if RT_OM && RT_COUNT
+//   RT_VM = 1     per-vertex motion vectors (rt_set_object_motion mode RT_OBJECT_MOTION_VERTEX): the same two kernels take a DevVtxMotion, store the
+//                 instance image and the delta x_prev - state.position per pixel, and run the temporal lookups of both stages with the previous world position
+//                 of the material point under the pixel (stage_common.h vmPrevPosition) and the camera's own lastProjView / lastPosition.  Forwards like RT_OM.
+#ifndef RT_VM
+#define RT_VM 0
+#endif
+#if (RT_OM || RT_VM) && RT_COUNT
 #error "object motion vectors have no counting build"
+#endif
+#if RT_OM && RT_VM
+#error "RT_OM and RT_VM are two builds"
 #endif
 #if RT_OM
 #define RT_OM_PARAM , const DevObjMotion& OM
 #define RT_OM_KPARAM , DevObjMotion OM
+#define RT_OM_ARG , OM
+#elif RT_VM
+#define RT_OM_PARAM , const DevVtxMotion& OM
+#define RT_OM_KPARAM , DevVtxMotion OM
 #define RT_OM_ARG , OM
 #else
 #define RT_OM_PARAM
@@ -47,7 +61,19 @@
 #if RT_LAT && RT_COUNT
 #error "the counting build exists for the throughput kernels only"
 #endif
-#if RT_OM && RT_LAT && RT_SKY
+#if RT_VM && RT_LAT && RT_SKY
+#define RT_VARIANT sky_lat_vm
+#define RT_FORWARD sky
+#elif RT_VM && RT_LAT
+#define RT_VARIANT base_lat_vm
+#define RT_FORWARD base
+#elif RT_VM && RT_SKY
+#define RT_VARIANT sky_vm
+#define RT_FORWARD sky
+#elif RT_VM
+#define RT_VARIANT base_vm
+#define RT_FORWARD base
+#elif RT_OM && RT_LAT && RT_SKY
 #define RT_VARIANT sky_lat_om
 #define RT_FORWARD sky
 #elif RT_OM && RT_LAT
@@ -101,6 +127,8 @@ struct DirectCont {
   float pdf;     // kind 2: pdf of the single light sample (kept in resv.lightSample)
 #if RT_OM
   uint32_t inst; // instance of the primary hit
+#elif RT_VM
+  float reprojDepth;   // length(lastPosition - x_prev): all of x_prev that crosses the shadow-ray trace, beside motionIdx
 #endif
   int kind;      // 0: radiance is final (miss, emitter, debug view), 1: RIS reservoir, 2: single sample (ReSTIRState none)
 };
@@ -117,6 +145,9 @@ RT_DEV bool directPre(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st,
     storeMotion(F, px, i2{0, 0});
 #if RT_OM
     OM.instImage[index] = 0xffffffffu;
+#elif RT_VM
+    OM.instImage[index] = 0xffffffffu;
+    OM.delta[index] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 #endif
     K.radiance = c.EnvRadiance(r.direction);
     return false;
@@ -128,6 +159,16 @@ RT_DEV bool directPre(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st,
   K.inst = gLoadU32(&c.S.triRef[c.hit.gid].inst);
   OM.instImage[index] = K.inst;
   K.motionIdx = createMotionIndexOm(c, OM, K.inst, state.position);
+#elif RT_VM
+  {
+    const uint32_t inst = gLoadU32(&c.S.triRef[c.hit.gid].inst);
+    OM.instImage[index] = inst;
+    const f3 xPrev = vmPrevPosition(c, OM, inst, state.position);
+    const f3 d = xPrev - state.position;
+    OM.delta[index] = make_float4(d.x, d.y, d.z, 0.0f);
+    K.motionIdx = createMotionIndex(c, xPrev);
+    K.reprojDepth = length(mk3(c.cam.lastPosition) - xPrev);
+  }
 #else
   K.motionIdx = createMotionIndex(c, state.position);
 #endif
@@ -174,6 +215,8 @@ RT_DEV void directPost(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt_state& st
       if(st.ReSTIRState == RT_RESTIR_TEMPORAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL) {
 #if RT_OM
         const float reprojDepth = length(omLastPosition(OM, cam, K.inst) - state.position);
+#elif RT_VM
+        const float reprojDepth = K.reprojDepth;
 #else
         const float reprojDepth = length(mk3(cam.lastPosition) - state.position);
 #endif
@@ -361,7 +404,7 @@ __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, D
 }
 #endif
 
-#if !RT_LAT && !RT_OM   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency or an object-motion form)
+#if !RT_LAT && !RT_OM && !RT_VM   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency or an object-motion form)
 // Second half of direct_stage.comp's ReSTIRDirect for the spatial modes (:86-121, 236-262): two rounds of five neighbour
 // merges from the cached reservoirs, the final merge and the shading.  No rays.
 // The 10 x 10 block of cached reservoirs around the 8 x 8 tile (every neighbour lies within one pixel) is staged in LDS once and the
@@ -514,7 +557,7 @@ __global__ __launch_bounds__(64) void k_direct_reuse(DevScene S, DevFrame F, rt_
   storeImg(F.thisDirectResult, F, px, mk4(HDRToLDR(c.clampRadiance(direct)), 1.0f));
 }
 
-#endif  // !RT_LAT && !RT_OM
+#endif  // !RT_LAT && !RT_OM && !RT_VM
 
 // ------------------------------------------------------------------------------------------------------------
 // indirect_stage.comp
@@ -532,6 +575,9 @@ RT_DEV void restirIndirectFinish(Ctx& c, const DevFrame& F RT_OM_PARAM, const rt
   if(st.ReSTIRState == RT_RESTIR_TEMPORAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL) {
 #if RT_OM
     const float reprojDepth = length(omLastPosition(OM, cam, OM.instImage[size_t(px.y * 2) * F.W + px.x * 2]) - primState.position);
+#elif RT_VM
+    const float4 dv = gLoadF4(OM.delta + (size_t(px.y * 2) * F.W + px.x * 2));
+    const float reprojDepth = length(mk3(cam.lastPosition) - (primState.position + mk3(dv.x, dv.y, dv.z)));
 #else
     const float reprojDepth = length(mk3(cam.lastPosition) - primState.position);
 #endif
@@ -941,7 +987,7 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
 #else
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
       if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, block, lds, stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY);
-#if RT_OM
+#if RT_OM || RT_VM
       if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
 #else
       if(level != 1 && spatial) hipLaunchKernelGGL(k_direct_spatial, grid, block, 0, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
@@ -973,7 +1019,7 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
 #endif
       break;
     }
-#if !RT_LAT && !RT_OM   // the two stages the reference compiles but does not dispatch: throughput builds only
+#if !RT_LAT && !RT_OM && !RT_VM   // the two stages the reference compiles but does not dispatch: throughput builds only
     case RT_STAGE_DIRECT_GEN:
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
       hipLaunchKernelGGL(k_direct_gen, grid, block, lds, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);

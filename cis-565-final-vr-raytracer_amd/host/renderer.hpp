@@ -110,6 +110,12 @@ class Renderer {
     if(rt_set_object_motion(m_ctx, on ? RT_OBJECT_MOTION_ON : RT_OBJECT_MOTION_OFF) != RT_OK) { fprintf(stderr, "Renderer::setObjectMotion: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
+  // Per-vertex motion vectors (include/rt_abi.h "Per-vertex motion vectors"): temporal reuse follows deformed meshes as well as moved instances
+  bool setVertexMotion(bool on)
+  {
+    if(rt_set_object_motion(m_ctx, on ? RT_OBJECT_MOTION_VERTEX : RT_OBJECT_MOTION_OFF) != RT_OK) { fprintf(stderr, "Renderer::setVertexMotion: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
   // renderer.cpp:97-148: screen-space buffers for `size` (the reference also creates 7 pipelines + descriptor sets here)
   bool create(int width, int height, Scene* scene) { (void)scene; return update(width, height); }
   // renderer.cpp:154-206: the 12 dispatches of one frame

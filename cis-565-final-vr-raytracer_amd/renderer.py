@@ -22,7 +22,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
-               "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback",
+               "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
                "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats",
@@ -131,6 +131,8 @@ def hip_lib():
             L.rt_set_object_motion.argtypes = [C.c_void_p, C.c_int]
             L.rt_object_motion_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.rt_object_motion_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        if hasattr(L, "rt_vertex_motion_readback"):   # per-vertex motion vectors (absent from older A/B libraries)
+            L.rt_vertex_motion_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         if hasattr(L, "rt_update_vertices"):   # deforming meshes (absent from older A/B libraries)
             L.rt_update_vertices.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
             L.rt_set_skins.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -542,7 +544,7 @@ class Renderer:
 
     # ---- object motion vectors (include/rt_abi.h "Object motion vectors")
     def set_object_motion(self, mode):
-        """rt_set_object_motion: abi.OBJECT_MOTION_OFF (default) / OBJECT_MOTION_ON"""
+        """rt_set_object_motion: abi.OBJECT_MOTION_OFF (default) / OBJECT_MOTION_ON / OBJECT_MOTION_VERTEX (per-vertex motion vectors)"""
         self._chk(hip_lib().rt_set_object_motion(self._h, int(mode)), "rt_set_object_motion")
 
     def object_motion_readback(self):
@@ -550,6 +552,13 @@ class Renderer:
         nbytes = self.buffer_bytes(abi.BUF_MOTION)   # 4 B per full-resolution pixel
         out = np.empty(nbytes // 4, dtype=np.uint32)
         self._chk(hip_lib().rt_object_motion_readback(self._h, out.ctypes.data, out.nbytes), "rt_object_motion_readback")
+        return out
+
+    def vertex_motion_readback(self):
+        """the delta image of the last frame rendered with OBJECT_MOTION_VERTEX: (W * H, 4) float32, x_prev - position in .xyz, zero at a miss and where nothing moved"""
+        n = self.buffer_bytes(abi.BUF_MOTION) // 4
+        out = np.empty((n, 4), dtype=np.float32)
+        self._chk(hip_lib().rt_vertex_motion_readback(self._h, out.ctypes.data, out.nbytes), "rt_vertex_motion_readback")
         return out
 
     @staticmethod

@@ -768,7 +768,7 @@ int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
  *   q = (Pi[r][0] x + Pi[r][1] y + Pi[r][2] z) + Pi[r][3] of lastPosition, lastPosition_i = the same expression with cur applied to q.
  *   prev == cur bit for bit returns *cam bit for bit (copied, not computed); so does a prev or cur that is not finite, or whose determinant is zero or not
  *   finite, or whose inverse is not finite.  RT_ERR_INVALID_ARG only for a NULL pointer.
- * rt_set_object_motion(ctx, mode): RT_OBJECT_MOTION_OFF (default) / _ON.  A call that changes nothing does nothing; a change invalidates no history and does
+ * rt_set_object_motion(ctx, mode): RT_OBJECT_MOTION_OFF (default) / _ON / _VERTEX ("Per-vertex motion vectors" below).  A call that changes nothing does nothing; a change invalidates no history and does
  *   not re-open the stream-priority decision.  The context keeps, per instance, the objectToWorld of the last frame rt_render_frame rendered (whether the mode is
  *   on or off): rt_update_instances records it once, so several updates between two frames keep the rendered frame's matrix; issuing a frame's direct stage makes
  *   every previous matrix the current one.  rt_build_accel and rt_rebuild_accel keep this state; rt_upload_scene and rt_resize clear it.  An instance is IN
@@ -788,10 +788,42 @@ int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
  *   direct stage, read by the indirect stage of the same frame at 2p) and is rotated with it by the frames-in-flight schedules and rt_rotate_buffers; it is
  *   allocated by rt_resize once the mode has been switched on (or by the call that first switches it on).
  * ---------------------------------------------------------------------------------------------------------------- */
-enum { RT_OBJECT_MOTION_OFF = 0 /* default */, RT_OBJECT_MOTION_ON = 1 };
+enum { RT_OBJECT_MOTION_OFF = 0 /* default */, RT_OBJECT_MOTION_ON = 1, RT_OBJECT_MOTION_VERTEX = 3 /* per-vertex motion vectors, below; 2 is not a mode: RT_ERR_INVALID_ARG */ };
 int rt_set_object_motion(rt_ctx* ctx, int mode);
 int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectToWorld[12], const float curObjectToWorld[12], rt_scene_camera* out);
 int rt_object_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-vertex motion vectors (added within ABI 2.4, no version bump; the RT_VM builds of csrc/stages.hip, csrc/vmotion.hip): a third mode (value 3; 2 is not a mode and stays RT_ERR_INVALID_ARG) of
+ * rt_set_object_motion.  The per-instance camera of mode 1 cannot express a deformation (rt_update_vertices, rt_update_skins, rt_update_morphs): a bent surface
+ * has no single matrix.  Mode RT_OBJECT_MOTION_VERTEX runs both temporal lookups with the PREVIOUS WORLD POSITION OF THE MATERIAL POINT under the pixel, from the
+ * previous frame's vertices and the previous frame's objectToWorld; it covers rigid instance motion too, with no matrix inverse.  Modes 0 and 1 keep their
+ * meaning and their kernels.  For a full-resolution pixel p whose primary ray hits triangle (i0, i1, i2) of prim mesh m in instance i, bary = ((1 - u) - v, u, v):
+ *   q_k    = the position vertex i_k had at the last frame rt_render_frame rendered, when m was deformed since that frame by rt_update_vertices, rt_update_skins
+ *            or rt_update_morphs; else its live position.
+ *   P      = the objectToWorld instance i had at that frame when it was moved since (rt_update_instances; the state mode 1 keeps); else its current matrix.
+ *   x_prev = xformPoint(P, (q0 * bary.x + q1 * bary.y) + q2 * bary.z), every component of the interpolation in that order and
+ *            xformPoint(P, q)[r] = ((P[4r] * q.x + P[4r+1] * q.y) + P[4r+2] * q.z) + P[4r+3]: fp32, no contraction (include/rt_detmath.h) — the expression of
+ *            state.position with the previous data.  Computed only when i is in motion or m was deformed; otherwise x_prev = state.position, copied.
+ *   d(p)   = x_prev - state.position, component by component; 0 at a miss.
+ *   direct stage:   motionIdx = createMotionIndex(x_prev) with the camera's own lastProjView; reprojDepth = length(lastPosition - x_prev).
+ *   indirect stage at half-resolution pixel q: reprojDepth = length(lastPosition - (primState.position + d(2q))); the motion index is read from RT_BUF_MOTION
+ *            at 2q as before, and primState.position keeps its reconstruction from the half-resolution ray.
+ *   Everything else is untouched: the normal tests, the material hash, the column 0-1 exclusion, every quirk of DESIGN.md §6.  A bend of more than acos(0.9)
+ *   per frame still rejects the direct history (previous normals are not kept), and a reused sample is one frame stale.
+ * When no instance is in motion and no mesh was deformed since the last rendered frame no table exists, every pixel takes the camera's values and the frame
+ * equals the mode-off frame word for word; so do the pixels of static, undeformed instances in any frame.
+ * Context: once the mode has been switched on the context keeps one 16-byte row per scene vertex (the previous-position plane).  The first deforming call for a
+ * mesh after a rendered frame copies the mesh's live positions there ahead of its commit, whether the mode is on or off; later calls before the next frame do
+ * not (the rendered frame's positions stay, as the matrices of mode 1 do); issuing a frame's direct stage makes every mesh undeformed.  rt_build_accel and
+ * rt_rebuild_accel keep the state; rt_upload_scene and rt_resize clear it; switching the mode invalidates no history.  A frame with something in motion or
+ * deformed uploads one 64-byte row per instance {P, flags (bit 0 moved, bit 1 mesh deformed)} ahead of the direct stage.  Counting, rt_run_stage,
+ * restir_amd/tiled.py, rt_mgpu_*, SVGF and TAA: as mode 1 (a frame with something in motion or deformed under rt_set_counting is RT_ERR_INVALID_ARG).
+ * Frames of this mode also write the instance image, so rt_object_motion_readback keeps its contract.
+ * rt_vertex_motion_readback(ctx, dst, bytes): the delta image of the last frame rendered with this mode: float4 (d.xyz, 0) per full-resolution pixel, W * H * 16 B,
+ *   `bytes` must be exact (else RT_ERR_INVALID_ARG).  RT_ERR_NO_TARGET before the first such frame since rt_resize.  Synchronous.  The image has the lifetime of
+ *   the instance image: three copies rotated with RT_BUF_MOTION, allocated by rt_resize once this mode has been on (or by the call that first switches it on).
+ * ---------------------------------------------------------------------------------------------------------------- */
+int rt_vertex_motion_readback(rt_ctx* ctx, void* dst, size_t bytes);
 /* ------------------------------------------------------------------------------------------------------------------
  * Deforming meshes (added within ABI 2.4, no version bump; csrc/deform.hip).  rt_update_instances moves rigid instances; these calls change the
  * VERTICES of a prim mesh on the device — rows supplied by the host (rt_update_vertices: cloth, anything the host computes; morph targets have a device path of their own, "Morph targets" below) or posed on the GPU from
