@@ -168,6 +168,14 @@ class MorphStats(C.Structure):  # rt_morph_stats, 32 B
 assert MORPH_SET_DT.itemsize == 16 and MORPH_DELTA_DT.itemsize == 16 and C.sizeof(MorphStats) == 32
 
 
+class PrimaryReplayStats(C.Structure):  # rt_primary_replay_stats, 32 B
+    _fields_ = [("state", C.c_uint32), ("K", C.c_uint32), ("pixelsSettled", C.c_uint32), ("pixelsListed", C.c_uint32), ("pixelsOverflow", C.c_uint32),
+                ("launchesRecorded", C.c_uint32), ("launchesReplayed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(PrimaryReplayStats) == 32
+
+
 class LightStats(C.Structure):  # rt_light_stats, 32 B
     _fields_ = [("bound", C.c_uint32), ("rewritten", C.c_uint32), ("lightBytesCopied", C.c_uint32), ("ms", C.c_float), ("reserved", C.c_uint32 * 4)]
 

@@ -122,4 +122,15 @@ struct DevVtxMotion {
   uint32_t numInst, pad;
 };
 
+// settled primary visibility (the RT_REPLAY builds of stages.hip take it as a kernel argument of its own).  Three context-owned planes, one entry per
+// full-resolution pixel, written by a RECORD launch and read by REPLAY launches; whether they may be believed is host state alone (primary_replay.h).
+enum : uint32_t { VIS_NO_DET = 0xffffffffu, VIS_OVERFLOW = 0xffffffffu };
+struct DevVis {
+  uint32_t* det;            // leaf record (index into DevScene::tris) of the closest deterministic accept of the pixel's primary ray, VIS_NO_DET: none
+  uint32_t* count;          // stochastic candidates in front of it that `list` holds (0..K), VIS_OVERFLOW: more than K, the pixel keeps tracing
+  uint32_t* list;           // K planes of W x H: entry i of pixel p at list[i * W * H + p]
+  uint32_t K;
+  uint32_t record;          // 1: this launch records, 0: it replays
+};
+
 }  // namespace rt

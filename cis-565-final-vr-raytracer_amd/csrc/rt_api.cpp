@@ -20,6 +20,7 @@
 #include "../../include/rt_cpus.h"
 #include "bvh8_builder.h"
 #include "stages.h"
+#include "primary_replay.h"
 #include "reference.h"
 #include "svgf.h"
 #include "gi_spatial.h"
@@ -91,6 +92,13 @@ struct rt_ctx {
   int traversal = RT_TRAVERSAL_AUTO;     // rt_set_traversal: which build of the traced kernels a launch gets
   bool counting = false;
   unsigned long long* dCounters = nullptr;
+  // Settled primary visibility (primary_replay.h).  `replay` is all the trust there is: the planes of `vis` (allocated by the first recording, freed by
+  // rt_resize / rt_destroy) are read only by a launch for which primaryReplayStep said REPLAY.
+  rt::PrimaryReplayState replay;
+  rt::DevVis vis{};
+  bool replayOff = false;      // a rank context of an rt_mgpu_* host: never records
+  bool visAllocFailed = false; // the planes did not fit once: this target size keeps tracing
+  uint32_t replayRecorded = 0, replayReplayed = 0;   // launches, since rt_create
   // timing: per frame one event set; event 0 = frame start, event k = end of launch k.  Sets are harvested lazily.
   static constexpr int MAX_EV = 24, MAX_SETS = 1024;
   struct EvSet { hipEvent_t ev[MAX_EV]; int stage[MAX_EV]; int prev[MAX_EV]; int count; int last; };
@@ -313,6 +321,56 @@ static VmStageLauncher vmStageLauncher(const rt_ctx* c, const rt_state& st, int 
   const bool lat = latencyBuild(c, st, stage, 0, 0);
   if(c->ds.sky) return lat ? rt::sky_lat_vm::launchStage : rt::sky_vm::launchStage;
   return lat ? rt::base_lat_vm::launchStage : rt::base_vm::launchStage;
+}
+
+// ---- settled primary visibility (primary_replay.h) -------------------------------------------------------------------------------------------------
+// RESTIR_PRIMARY_REPLAY=0 switches it off, RESTIR_VIS_K sets the list length per pixel (1..64), RESTIR_VIS_REST_FRAMES the at-rest launches ahead of a recording (>= 2);
+// each is read once per process.
+static bool replayEnabled() { static const int v = envInt("RESTIR_PRIMARY_REPLAY"); return v != 0; }
+static uint32_t visListLength() { static const int v = envInt("RESTIR_VIS_K"); return uint32_t(v <= 0 ? RT_VIS_K_DEFAULT : std::min(v, 64)); }
+static int visRestFrames() { static const int v = envInt("RESTIR_VIS_REST_FRAMES"); return v < 2 ? 2 : v; }
+static void freeVis(rt_ctx* c)
+{
+  for(uint32_t** p : {&c->vis.det, &c->vis.count, &c->vis.list}) { if(*p) (void)hipFree(*p); *p = nullptr; }
+  c->vis.K = 0;
+  c->visAllocFailed = false;
+  rt::primaryReplayInvalidate(c->replay);
+}
+// whatever can change what a primary ray hits, or the order of the leaf records, calls this (the list is in DESIGN.md §25)
+static void dropPrimaryReplay(rt_ctx* c) { rt::primaryReplayInvalidate(c->replay); }
+// One direct launch passes through the rule.  Returns what it does; for RECORD / REPLAY `V` is the kernel argument.  A recording whose planes cannot be allocated
+// is a normal launch, and the target size stops asking.
+static rt::PrimaryReplayAction primaryReplayLaunch(rt_ctx* c, const rt_state& st, const rt_scene_camera& cam, bool fullFrame, bool eligible, rt::DevVis& V)
+{
+  rt::PrimaryReplayLaunch l{};
+  l.view = rt::primaryReplayViewOf(cam, st.size.x, st.size.y);
+  l.fullFrame = fullFrame;
+  l.eligible = eligible && replayEnabled() && !c->replayOff && !c->visAllocFailed && c->ds.numTris > 0;
+  rt::PrimaryReplayAction a = rt::primaryReplayStep(c->replay, l, visRestFrames());
+  if(a == rt::PRIMARY_REPLAY_RECORD && !c->vis.det) {
+    const size_t n = size_t(c->W) * size_t(c->H);
+    const uint32_t K = visListLength();
+    bool ok = hipMalloc(reinterpret_cast<void**>(&c->vis.det), n * 4) == hipSuccess && hipMalloc(reinterpret_cast<void**>(&c->vis.count), n * 4) == hipSuccess &&
+              hipMalloc(reinterpret_cast<void**>(&c->vis.list), n * 4 * K) == hipSuccess;
+    if(!ok) { (void)hipGetLastError(); freeVis(c); c->visAllocFailed = true; return rt::PRIMARY_REPLAY_NORMAL; }
+    c->vis.K = K;
+  }
+  V = c->vis;
+  V.record = a == rt::PRIMARY_REPLAY_RECORD ? 1u : 0u;
+  return a;
+}
+typedef hipError_t (*RpStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const rt::DevVis&, const rt_state&, const rt_scene_camera&, int, int, int, int);
+static RpStageLauncher rpStageLauncher(const rt_ctx* c)
+{
+  if(c->ds.sky) return c->counting ? rt::sky_rp_cnt::launchStage : rt::sky_rp::launchStage;
+  return c->counting ? rt::base_rp_cnt::launchStage : rt::base_rp::launchStage;
+}
+// after a RECORD / REPLAY launch was issued (or failed to be)
+static void primaryReplayIssued(rt_ctx* c, rt::PrimaryReplayAction a, bool ok)
+{
+  if(!ok) { dropPrimaryReplay(c); return; }
+  if(a == rt::PRIMARY_REPLAY_RECORD) c->replayRecorded++;
+  if(a == rt::PRIMARY_REPLAY_REPLAY) c->replayReplayed++;
 }
 
 // ---- host side of rt_build_accel, cached by scene content (buildHostAccel below) ---------------------------------------------------------------------
@@ -548,6 +606,7 @@ int rtCreateWithLevels(rt_ctx** out, int device, const int* levels)
   {
     prioSpec(c->prio); c->prioFromEnv = getenv("RESTIR_PRIO") != nullptr; c->prioDecided = c->prioFromEnv;
     if(levels) { for(int i = 0; i < 3; i++) c->prio[i] = std::max(-1, std::min(1, levels[i])); c->prioDecided = c->prioExplicit = true; }
+    c->replayOff = levels != nullptr;   // the rt_mgpu_* hosts render row bands and exchange history between devices: their contexts never record primary visibility
     bool ok = createStreamLevel(&c->ownStream, c->prio[0]) == hipSuccess;
     if(!ok) { g_createErr = "rt_create: hipStreamCreate failed"; rt_destroy(c); return RT_ERR_HIP; }
     c->mainIdx = g_streamsCreated.load() - 1;
@@ -587,6 +646,7 @@ int rt_destroy(rt_ctx* c)
   if(c->indStream) (void)hipStreamDestroy(c->indStream);
   for(int i = 0; i < 4; i++) { if(c->evD[i]) (void)hipEventDestroy(c->evD[i]); if(c->evI[i]) (void)hipEventDestroy(c->evI[i]); if(c->evDone[i]) (void)hipEventDestroy(c->evDone[i]); }
   if(c->dCounters) (void)hipFree(c->dCounters);
+  freeVis(c);
   if(c->dSky) (void)hipFree(c->dSky);
   if(c->dPick) (void)hipFree(c->dPick);
   if(c->refAcc) (void)hipFree(c->refAcc);
@@ -612,6 +672,7 @@ int rt_destroy(rt_ctx* c)
 int rt_set_stream(rt_ctx* c, void* s)
 {
   if(!c) return RT_ERR_INVALID_ARG;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   c->stream = s ? static_cast<hipStream_t>(s) : c->ownStream;
   return RT_OK;
 }
@@ -638,6 +699,7 @@ static int resetSeedPlane(rt_ctx* c)
 int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
 {
   if(!c) return RT_ERR_INVALID_ARG;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(!d || !d->primMeshes || !d->vertices || !d->indices || !d->instances || !d->materials || d->numMaterials == 0)
     return fail(c, RT_ERR_INVALID_ARG, "rt_upload_scene: missing geometry/material arrays");
   for(uint32_t i = 0; i < d->numInstances; i++)
@@ -875,6 +937,7 @@ static int buildHostAccel(rt_ctx* c, HostAccel& out)
 int rt_build_accel(rt_ctx* c)
 {
   if(!c) return RT_ERR_INVALID_ARG;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_build_accel: no scene uploaded");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
@@ -957,6 +1020,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   freeGiSpatial(c);
   freeTaaHistory(c);
   freeObjectMotion(c);
+  freeVis(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
   for(int i = 0; i < RT_BUF_COUNT; i++) {
     const size_t bytes = (halfRes(i) ? nh : n) * elemBytes(i);
@@ -1245,7 +1309,17 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
   DevFrame F = makeFrame(c, frames);
   if(stage == RT_STAGE_INDIRECT) F.histMiss = c->scratch.qcount + 251;  // per-stage-kind flag (rt_history_miss_stage)
   // (stage kinds share no scratch: a caller may spread them over several streams, tiled.PipelinedTiledFrame does)
-  const hipError_t e = stageLauncher(c, *st, stage, rowBegin, rowEnd)(c->stream, c->ds, F, *st, c->cam, stage, level, rowBegin, rowEnd);
+  hipError_t e;
+  rt::DevVis V{};
+  rt::PrimaryReplayAction act = rt::PRIMARY_REPLAY_NORMAL;
+  if(stage == RT_STAGE_DIRECT && level != 2) {   // (level 2 is the rayless half: it spawns no primary ray)
+    const bool fullFrame = rowBegin == 0 && (rowEnd <= 0 || rowEnd >= c->H);
+    act = primaryReplayLaunch(c, *st, c->cam, fullFrame, c->objMotion == RT_OBJECT_MOTION_OFF && !latencyBuild(c, *st, stage, rowBegin, rowEnd), V);
+  }
+  if(act != rt::PRIMARY_REPLAY_NORMAL) {
+    e = rpStageLauncher(c)(c->stream, c->ds, F, V, *st, c->cam, stage, level, rowBegin, rowEnd);
+    primaryReplayIssued(c, act, e == hipSuccess);
+  } else e = stageLauncher(c, *st, stage, rowBegin, rowEnd)(c->stream, c->ds, F, *st, c->cam, stage, level, rowBegin, rowEnd);
   if(e == hipErrorInvalidValue) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: level out of range for this stage (RT_STAGE_DIRECT levels 1 / 2 exist in the spatial modes only)");
   if(e == hipErrorInvalidConfiguration) return fail(c, RT_ERR_HIP, "rt_run_stage: the traversal-stack overflow area is missing or too small for this launch (internal sizing error)");
   RT_HIP(c, e);
@@ -1399,7 +1473,17 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   auto direct = [&](hipStream_t strm) -> int {
     if(om && omMotion) RT_HIP(c, hipMemcpyAsync(c->omTable, c->omHost.data(), c->omHost.size() * sizeof(OmCamera), hipMemcpyHostToDevice, strm));
     if(vm && vmMotion) RT_HIP(c, hipMemcpyAsync(c->vmTable, c->vmHost.data(), c->vmHost.size() * sizeof(VmRow), hipMemcpyHostToDevice, strm));
-    const int r = run(strm, RT_STAGE_DIRECT, 0);
+    // settled primary visibility: a frame of the throughput build without TAA and without a motion-vector mode passes through the rule (primary_replay.h)
+    rt::DevVis V{};
+    const rt::PrimaryReplayAction act = primaryReplayLaunch(c, *st, cam, true, c->taa.mode == RT_TAA_OFF && c->objMotion == RT_OBJECT_MOTION_OFF && !om && !vm &&
+                                                            !latencyBuild(c, *st, RT_STAGE_DIRECT, 0, 0), V);
+    int r;
+    if(act != rt::PRIMARY_REPLAY_NORMAL) {
+      const hipError_t e = rpStageLauncher(c)(strm, c->ds, F, V, *st, cam, RT_STAGE_DIRECT, 0, 0, 0);
+      primaryReplayIssued(c, act, e == hipSuccess);
+      if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+      r = record(strm, RT_STAGE_DIRECT);
+    } else r = run(strm, RT_STAGE_DIRECT, 0);
     if(r == RT_OK) {
       if(om) c->omInstValid = true;
       if(vm) c->omInstValid = c->vmDeltaValid = true;
@@ -1683,6 +1767,34 @@ int rt_rotate_buffers(rt_ctx* c, int frames)
   std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
   if(c->omInst) std::swap(c->omInst, c->omInstSpare);
   if(c->vmDelta) std::swap(c->vmDelta, c->vmDeltaSpare);
+  return RT_OK;
+}
+
+int rt_get_primary_replay_stats(rt_ctx* c, rt_primary_replay_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  std::memset(out, 0, sizeof *out);
+  out->state = uint32_t(c->replay.state);
+  out->K = c->vis.K ? c->vis.K : visListLength();
+  out->launchesRecorded = c->replayRecorded; out->launchesReplayed = c->replayReplayed;
+  if(c->replay.state == rt::PRIMARY_REPLAY_VALID && c->vis.count && c->W > 0) {   // the pixel classes of the recording in force
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    std::vector<uint32_t> cnt(size_t(c->W) * size_t(c->H));
+    RT_HIP(c, hipMemcpy(cnt.data(), c->vis.count, cnt.size() * 4, hipMemcpyDeviceToHost));
+    for(uint32_t v : cnt) { if(v == rt::VIS_OVERFLOW) out->pixelsOverflow++; else if(v == 0u) out->pixelsSettled++; else out->pixelsListed++; }
+  }
+  return RT_OK;
+}
+
+int rt_primary_replay_readback(rt_ctx* c, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(c->replay.state != rt::PRIMARY_REPLAY_VALID || !c->vis.count) return fail(c, RT_ERR_INVALID_ARG, "rt_primary_replay_readback: no recording in force");
+  if(bytes != size_t(c->W) * size_t(c->H) * 4) return fail(c, RT_ERR_INVALID_ARG, "rt_primary_replay_readback: size mismatch (W x H x 4 bytes)");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  RT_HIP(c, hipMemcpy(dst, c->vis.count, bytes, hipMemcpyDeviceToHost));
   return RT_OK;
 }
 
@@ -2256,6 +2368,7 @@ static int ensureRefitState(rt_ctx* c)
 // the dirty and flip words, the cleared node marks and counters, k_refit_tris, k_refit_level deepest level first, the counters, evRefit[1], one synchronise.
 static int refitTail(rt_ctx* c, const std::vector<uint8_t>& dirty)
 {
+  dropPrimaryReplay(c);   // leaf records are about to be rewritten
   rt_ctx::Refit& R = c->refit;
   const uint32_t count = uint32_t(dirty.size() - std::count(dirty.begin(), dirty.end(), uint8_t(0)));   // the predicate of the dirty bits: != 0
   const std::vector<uint32_t> dirtyBits = instanceBits(dirty.size(), [&](size_t i) { return dirty[i] != 0; });
@@ -2315,6 +2428,7 @@ extern "C" {
 int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const float* xf)
 {
   if(int rc = needTree(c, "rt_update_instances")) return rc;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(count && (!ids || !xf)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: NULL ids / matrices");
   const size_t nInst = c->instances.size();
   // the whole call is checked before anything changes
@@ -2392,6 +2506,7 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
 int rt_rebuild_accel(rt_ctx* c)
 {
   if(int rc = needTree(c, "rt_rebuild_accel")) return rc;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));   // drains the frames in flight, like rt_update_instances
   int rc;
@@ -2709,6 +2824,7 @@ extern "C" {
 int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint32_t count, const rt_vertex* rows)
 {
   if(int rc = needTree(c, "rt_update_vertices")) return rc;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(primMesh >= c->primMeshes.size()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: prim mesh out of range");
   const rt_prim_mesh& pm = c->primMeshes[primMesh];
   if(uint64_t(firstVertex) + count > pm.vertexCount) return fail(c, RT_ERR_INVALID_ARG, "rt_update_vertices: vertex range outside the prim mesh");
@@ -2742,6 +2858,7 @@ int rt_update_vertices(rt_ctx* c, uint32_t primMesh, uint32_t firstVertex, uint3
 int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t numInfluences, const rt_skin_influence* influences)
 {
   if(!c) return RT_ERR_INVALID_ARG;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_skins: no scene uploaded");
   if(numSkins && !skins) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: NULL skins");
   if(!c->morph.sets.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: morph sets exist (skins first: remove the sets with rt_set_morph_targets, set the skins, set the sets again)");
@@ -2801,6 +2918,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
 int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const float* mats)
 {
   if(int rc = needTree(c, "rt_update_skins")) return rc;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   rt_ctx::Deform& D = c->deform;
   if(D.skins.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: no skins (rt_set_skins)");
   if(count && (!skinIds || !mats)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_skins: NULL ids / matrices");
@@ -2880,6 +2998,7 @@ int rt_update_skins(rt_ctx* c, uint32_t count, const uint32_t* skinIds, const fl
 int rt_set_morph_targets(rt_ctx* c, uint32_t numSets, const rt_morph_set* sets, uint64_t numDeltas, const rt_morph_delta* deltas)
 {
   if(!c) return RT_ERR_INVALID_ARG;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_morph_targets: no scene uploaded");
   if(numSets && !sets) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: NULL sets");
   const rt_ctx::Deform& D = c->deform;
@@ -2941,6 +3060,7 @@ int rt_set_morph_targets(rt_ctx* c, uint32_t numSets, const rt_morph_set* sets, 
 int rt_update_morphs(rt_ctx* c, uint32_t count, const uint32_t* setIds, const float* weights)
 {
   if(int rc = needTree(c, "rt_update_morphs")) return rc;
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
   rt_ctx::Morph& M = c->morph;
   const rt_ctx::Deform& D = c->deform;
   if(M.sets.empty()) return fail(c, RT_ERR_INVALID_ARG, "rt_update_morphs: no morph sets (rt_set_morph_targets)");

@@ -42,6 +42,17 @@ RT_DECL_LAUNCH_VM(sky_vm)
 RT_DECL_LAUNCH_VM(base_lat_vm)
 RT_DECL_LAUNCH_VM(sky_lat_vm)
 #undef RT_DECL_LAUNCH_VM
+// the four primary-replay builds (RT_REPLAY, stages_*rp*.hip): RT_STAGE_DIRECT only, base and sky, each with its counting form
+#define RT_DECL_LAUNCH_RP(ns)                                                                                                                                  \
+  namespace ns {                                                                                                                                               \
+  hipError_t launchStage(hipStream_t stream, const DevScene& S, const DevFrame& F, const DevVis& V, const rt_state& st, const rt_scene_camera& cam,             \
+                         int stage, int level, int rowBegin, int rowEnd);                                                                                      \
+  }
+RT_DECL_LAUNCH_RP(base_rp)
+RT_DECL_LAUNCH_RP(sky_rp)
+RT_DECL_LAUNCH_RP(base_rp_cnt)
+RT_DECL_LAUNCH_RP(sky_rp_cnt)
+#undef RT_DECL_LAUNCH_RP
 // csrc/vmotion.hip: rows [first, first + count) of the previous-position plane <- the positions of the live vertex rows (the capture ahead of a deforming commit)
 hipError_t launchCapturePositions(hipStream_t stream, const rt_vertex* vertices, float4* plane, uint32_t first, uint32_t count);
 // filters.hip, compiled once: every other stage (both A-Trous chains, compose; hipErrorInvalidValue for a level outside the chain or any other stage), and the

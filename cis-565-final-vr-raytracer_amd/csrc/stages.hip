@@ -10,7 +10,8 @@
 // contiguous band of tile rows and its private 4 MiB L2 sees one compact screen region + the BVH subtrees under it.
 // This file is compiled six times: as is, and through stages_{sky,cnt,sky_cnt,lat,sky_lat}.hip with RT_SKY / RT_COUNT / RT_LAT set; what those switches do not reach is in filters.hip.
 // Four more builds, stages_{om,sky_om,lat_om,sky_lat_om}.hip, set RT_OM (below) for contexts with object motion vectors on, and four,
-// stages_{vm,sky_vm,lat_vm,sky_lat_vm}.hip, set RT_VM for contexts with per-vertex motion vectors on.
+// stages_{vm,sky_vm,lat_vm,sky_lat_vm}.hip, set RT_VM for contexts with per-vertex motion vectors on.  Four thin ones, stages_{rp,sky_rp,rp_cnt,sky_rp_cnt}.hip, set
+// RT_REPLAY (below): the direct stage of a camera at rest.
 //   RT_SKY = 1    procedural sun & sky code paths compiled in.  Keeping sun_and_sky() out of the default kernels saves 13 VGPRs
 //                 in k_direct_stage — the procedural sky is the rarely used mode (default in_use = 0, sample_example.hpp:202).
 //   RT_COUNT = 1  traversal / shading counters (rt_set_counting) are flushed at the end of the traced kernels.  Without the
@@ -39,6 +40,16 @@
 #ifndef RT_VM
 #define RT_VM 0
 #endif
+//   RT_REPLAY = 1 settled primary visibility: k_direct_stage alone, taking a DevVis.  A RECORD launch traces the primary ray as every build does and
+//                 then once more, culling by deterministic accepts only, to store what a camera at rest needs to know of it; REPLAY launches re-test the stored
+//                 records with the frame's seed and run no traversal loop for the primary ray.  Base and sky, each with its counting form (stages_{rp,sky_rp,
+//                 rp_cnt,sky_rp_cnt}.hip); no latency or object-motion form.  Every other stage and the rayless half of the direct stage forward to the plain build.
+#ifndef RT_REPLAY
+#define RT_REPLAY 0
+#endif
+#if RT_REPLAY && (RT_OM || RT_VM || RT_LAT)
+#error "primary replay exists for the throughput builds without motion vectors only"
+#endif
 #if (RT_OM || RT_VM) && RT_COUNT
 #error "object motion vectors have no counting build"
 #endif
@@ -61,7 +72,19 @@
 #if RT_LAT && RT_COUNT
 #error "the counting build exists for the throughput kernels only"
 #endif
-#if RT_VM && RT_LAT && RT_SKY
+#if RT_REPLAY && RT_SKY && RT_COUNT
+#define RT_VARIANT sky_rp_cnt
+#define RT_FORWARD sky_cnt
+#elif RT_REPLAY && RT_SKY
+#define RT_VARIANT sky_rp
+#define RT_FORWARD sky
+#elif RT_REPLAY && RT_COUNT
+#define RT_VARIANT base_rp_cnt
+#define RT_FORWARD base_cnt
+#elif RT_REPLAY
+#define RT_VARIANT base_rp
+#define RT_FORWARD base
+#elif RT_VM && RT_LAT && RT_SKY
 #define RT_VARIANT sky_lat_vm
 #define RT_FORWARD sky
 #elif RT_VM && RT_LAT
@@ -367,6 +390,121 @@ __global__ __launch_bounds__(512, RT_LAT_DIRECT_WAVES) void k_direct_stage(DevSc
   }
 #endif
 }
+#elif RT_REPLAY
+// ---- settled primary visibility ----------------------------------------------------------------------------------------------------------------
+// For a fixed ray and scene every candidate that passes the geometric part of triCandidateGeom (intersection, range, padded box) is a DETERMINISTIC accept (opaque,
+// or opacity micro-map cell state 1) or STOCHASTIC (cell state 0 or 2: the verdict draws from (ray seed, triangle id)).  With d* the lexicographic minimum of
+// (t, globalId) over the deterministic accepts, the frame's hit is the minimum over the accepted members of R = {d*} + {stochastic candidates in front of d*}; R
+// depends on (ray, scene) only.  The kind of a candidate, by the tests and in the order of triCandidateGeom: 0 rejected, 1 deterministic accept, 2 stochastic.
+RT_DEV int recordCandidateKind(const DevScene& S, const TriRegs& Q, f3 o, f3 d, float curT, uint32_t curG, float& t, uint32_t& gid)
+{
+  const uint4 a = Q.a, b = Q.b, c = Q.c, om = Q.om;
+  Tri48 R;
+  R.v0x = rt_u2f(a.x); R.v0y = rt_u2f(a.y); R.v0z = rt_u2f(a.z); R.e1x = rt_u2f(a.w);
+  R.e1y = rt_u2f(b.x); R.e1z = rt_u2f(b.y); R.e2x = rt_u2f(b.z); R.e2y = rt_u2f(b.w);
+  R.e2z = rt_u2f(c.x); R.globalId = c.y; R.flags = c.z; R.alphaIdx = c.w;
+  gid = R.globalId;
+  float u, v;
+  if(!intersectTri(R, o, d, t, u, v)) return 0;
+  if(!(t > 0.0f && t < RT_INFINITY)) return 0;
+  if(!(t < curT || (t == curT && R.globalId < curG))) return 0;
+  if(!hitInsidePaddedBox(R, o, d, S.triPad, t)) return 0;
+  if(R.flags & TRI_OPAQUE) return 1;
+  const int ci = min(int(u * 8.0f), 7), cj = min(int(v * 8.0f), 7);
+  const int cell = cj * 8 + ci;
+  const uint32_t word = (cell < 16) ? om.x : ((cell < 32) ? om.y : ((cell < 48) ? om.z : om.w));
+  return ((word >> ((cell & 15) * 2)) & 3u) == 1u ? 1 : 2;
+}
+// The recording traversal: a closest-hit traversal whose best-so-far (T.hit.t, T.hit.gid) is the best DETERMINISTIC accept, so that the slab test and the range
+// test cull by those alone, and that appends every stochastic candidate it meets in front of it to the pixel's list.  A candidate appended early can end up behind
+// the final d*: the replay's closer-than-best rule rejects it.  One step per lane and iteration, no vote: this runs once per stay of the camera.
+RT_DEV void recordPrimary(const DevScene& S, const Ray& r, uint2* stack, const DevVis& V, uint32_t pix, uint32_t npix, TravCounters& tc)
+{
+  Trav T;
+  bool live = travInit<0>(T, r.origin, r.direction, RT_INFINITY, 0u);
+  uint32_t det = VIS_NO_DET, cnt = 0u;
+  bool overflow = false;
+  while(live) {
+    if(travHasTris(T)) {
+      const uint32_t bit = 31u - uint32_t(__clz(int(T.tgroup.y)));
+      T.tgroup.y &= ~(1u << bit);
+      tc.tris++;
+      const uint32_t idx = T.tgroup.x + bit;
+      float t; uint32_t gid;
+      const int kind = recordCandidateKind(S, triLoad(S, idx), T.o, T.d, T.hit.t, T.hit.gid, t, gid);
+      if(kind == 1) { T.hit.t = t; T.hit.gid = gid; det = idx; }
+      else if(kind == 2) {
+        if(cnt < V.K) { V.list[size_t(cnt) * npix + pix] = idx; cnt++; }
+        else overflow = true;
+      }
+    } else travNode(S, T, stack, tc);
+    live = travHasTris(T) || travHasNodes(T);
+  }
+  V.det[pix] = det;
+  V.count[pix] = overflow ? VIS_OVERFLOW : cnt;
+}
+// The replay: d* first, then the listed candidates, each through the ordinary triCandidate with this frame's seed and the ordinary closer-than-best rule — the
+// (t, gid, u, v) bits the traversal would return, with no node step.  Returns the record of the hit (the next frame's seed), 0xffffffff at a miss.
+RT_DEV uint32_t replayPrimary(Ctx& c, const Ray& r, const DevVis& V, uint32_t pix, uint32_t npix, uint32_t cnt)
+{
+  RayHit h; h.t = RT_INFINITY; h.gid = 0xffffffffu; h.u = 0.f; h.v = 0.f;
+  uint32_t rec = 0xffffffffu;
+  cnt = min(cnt, V.K);
+  for(uint32_t i = 0; i <= cnt; i++) {
+    const uint32_t e = gLoadU32(i == 0u ? V.det + pix : V.list + (size_t(i - 1u) * npix + pix));
+    if(e >= c.S.numTris) continue;   // VIS_NO_DET
+    c.tc.tris++;
+    float t, u, v; uint32_t gid;
+    if(triCandidate(c.S, e, r.origin, r.direction, false, RT_INFINITY, h.t, h.gid, c.seed, t, u, v, gid, c.tc)) { h.t = t; h.gid = gid; h.u = u; h.v = v; rec = e; }
+  }
+  c.hit = h;
+  return rec;
+}
+// Two kernels, so that the replay — the one that runs every frame — carries no recording traversal
+template <bool RECORD>
+__global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, DevFrame F, DevVis V, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
+{
+  extern __shared__ uint2 s_stack[];
+#if RT_WAVEPROF
+  const uint64_t prof_c0 = clock64(), prof_w0 = wall_clock64();
+#endif
+  const TileCoord tile = tileOf(tilesX, tilesY);
+  if(!tile.valid) return;
+  const int lane = int(threadIdx.x);
+  const i2 px{tile.x * 8 + (lane & 7), rowBegin + tile.y * 8 + (lane >> 3)};
+  if(px.x >= st.size.x || px.y >= rowEnd) return;
+
+  Ctx c(S, st, cam, s_stack + lane);
+  c.imageCoords = px;
+  c.seed = tea(uint32_t(st.size.x) * uint32_t(px.y) + uint32_t(px.x), st.time);  // :279
+  const Ray r = c.raySpawn(px, i2{st.size.x, st.size.y});
+  {  // The primary ray.  RECORD: today's seeded trace for this frame's hit, then the recording traversal.  REPLAY: a pixel whose list fits re-tests its records; a
+     // pixel in OVERFLOW runs today's seeded trace (in a partial wave, which the trace's ballots allow for).  A replayed query counts as a query (nClosest), and the
+     // seed plane is written every frame so that it is warm when motion starts.
+    const uint32_t pix = uint32_t(st.size.x) * uint32_t(px.y) + uint32_t(px.x), npix = uint32_t(st.size.x) * uint32_t(st.size.y);
+    const uint32_t cnt = RECORD ? VIS_OVERFLOW : gLoadU32(V.count + pix);
+    uint32_t rec;
+    if(cnt == VIS_OVERFLOW) {
+      const uint32_t seedTri = F.seedIn ? gLoadU32(F.seedIn + pix) : 0xffffffffu;
+      rec = c.ClosestHitSeeded(r, seedTri);
+    } else {
+      c.nClosest++;
+      rec = replayPrimary(c, r, V, pix, npix, cnt);
+    }
+    if(RECORD) recordPrimary(S, r, c.stack, V, pix, npix, c.tc);
+    F.seedOut[size_t(px.y) * st.size.x + px.x] = rec;
+  }
+  DirectCont K;
+  Ray shadowRay{mk3(0.0f), mk3(0.0f)};
+  float shadowDist = 0.0f;
+  const bool wantShadow = directPre(c, F, st, px, r, K, shadowRay, shadowDist);
+  const bool occluded = wantShadow && c.AnyHit(shadowRay, shadowDist);
+  directPost(c, F, st, cam, px, K, occluded);
+  flushCounters(F, c);
+#if RT_WAVEPROF
+  waveProfFlush(F, c, tile.x, tile.y, prof_c0, prof_w0);
+#endif
+}
 #else
 __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, DevFrame F RT_OM_KPARAM, rt_state st, rt_scene_camera cam, int rowBegin, int rowEnd, int tilesX, int tilesY)
 {
@@ -404,7 +542,7 @@ __global__ __launch_bounds__(64, RT_DIRECT_LB) void k_direct_stage(DevScene S, D
 }
 #endif
 
-#if !RT_LAT && !RT_OM && !RT_VM   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency or an object-motion form)
+#if !RT_LAT && !RT_OM && !RT_VM && !RT_REPLAY   // (to the end of k_direct_reuse: the throughput builds' three kernels without a latency or an object-motion form)
 // Second half of direct_stage.comp's ReSTIRDirect for the spatial modes (:86-121, 236-262): two rounds of five neighbour
 // merges from the cached reservoirs, the final merge and the shading.  No rays.
 // The 10 x 10 block of cached reservoirs around the 8 x 8 tile (every neighbour lies within one pixel) is staged in LDS once and the
@@ -557,8 +695,9 @@ __global__ __launch_bounds__(64) void k_direct_reuse(DevScene S, DevFrame F, rt_
   storeImg(F.thisDirectResult, F, px, mk4(HDRToLDR(c.clampRadiance(direct)), 1.0f));
 }
 
-#endif  // !RT_LAT && !RT_OM && !RT_VM
+#endif  // !RT_LAT && !RT_OM && !RT_VM && !RT_REPLAY
 
+#if !RT_REPLAY   // (to the end of k_indirect_stage: the replay builds hold the first half of the direct stage only)
 // ------------------------------------------------------------------------------------------------------------
 // indirect_stage.comp
 // ------------------------------------------------------------------------------------------------------------
@@ -949,9 +1088,39 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
   flushCounters(F, c);
 }
 
+#endif  // !RT_REPLAY
+
 // ------------------------------------------------------------------------------------------------------------
 // host-side launch (one entry of Renderer::run's dispatch list, renderer.cpp:163-205)
 // ------------------------------------------------------------------------------------------------------------
+#if RT_REPLAY
+// RT_STAGE_DIRECT only, sized as the plain build sizes it; the rayless half (spatial modes) is the plain build's kernel
+hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F, const DevVis& V, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
+                       int rowBegin, int rowEnd)
+{
+  if(stage != RT_STAGE_DIRECT) return hipErrorInvalidValue;
+  DevScene S = Sin;
+  S.stackEntries = F.stackLds > 0 ? std::min(F.stackLds, S.stackTotal) : S.stackTotal;
+  const bool needOvf = S.stackTotal > S.stackEntries;
+  const int gw = st.size.x, gh = st.size.y;
+  if(rowEnd <= 0 || rowEnd > gh) rowEnd = gh;
+  if(rowBegin < 0) rowBegin = 0;
+  if(rowBegin >= rowEnd || gw <= 0) return hipSuccess;
+  const int tilesX = (gw + 7) / 8, tilesY = (rowEnd - rowBegin + 7) / 8;
+  const dim3 grid(tileGrid(tilesX, tilesY)), block(64);
+  const size_t lds = size_t(S.stackEntries) * 64 * sizeof(uint2);
+  const bool spatial = st.ReSTIRState == RT_RESTIR_SPATIAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
+  if(level < 0 || level > 2 || (level != 0 && !spatial)) return hipErrorInvalidValue;
+  if(!V.det || !V.count || !V.list || rowBegin != 0 || rowEnd != gh) return hipErrorInvalidValue;   // full frames only: the planes are indexed by pixel
+  if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;
+  if(level != 2) {
+    if(V.record) hipLaunchKernelGGL(k_direct_stage<true>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+    else hipLaunchKernelGGL(k_direct_stage<false>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+  }
+  if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
+  return hipGetLastError();
+}
+#else
 hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
                        int rowBegin, int rowEnd)
 {
@@ -1030,6 +1199,7 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
   }
   return hipGetLastError();
 }
+#endif  // RT_REPLAY
 
 }  // namespace RT_VARIANT
 }  // namespace rt

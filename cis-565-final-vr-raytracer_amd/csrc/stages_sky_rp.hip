@@ -1,0 +1,4 @@
+// stages.hip's direct stage with settled primary visibility recorded and replayed with sun & sky (RT_REPLAY; see the note at the top of stages.hip)
+#define RT_SKY 1
+#define RT_REPLAY 1
+#include "stages.hip"

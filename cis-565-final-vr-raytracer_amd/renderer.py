@@ -25,7 +25,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
-               "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats",
+               "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -147,6 +147,9 @@ def hip_lib():
             L.rt_set_morph_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
             L.rt_update_morphs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rt_get_morph_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_get_primary_replay_stats"):   # settled primary visibility (absent from older A/B libraries)
+            L.rt_get_primary_replay_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_primary_replay_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rt_accel_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.rt_accel_quality.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
@@ -521,6 +524,18 @@ class Renderer:
         s = abi.MorphStats()
         self._chk(hip_lib().rt_get_morph_stats(self._h, C.byref(s)), "rt_get_morph_stats")
         return s
+
+    def primary_replay_stats(self):
+        """rt_get_primary_replay_stats: state, K, the pixel classes of the recording in force and the launches recorded / replayed"""
+        s = abi.PrimaryReplayStats()
+        self._chk(hip_lib().rt_get_primary_replay_stats(self._h, C.byref(s)), "rt_get_primary_replay_stats")
+        return s
+
+    def primary_replay_readback(self, width, height):
+        """rt_primary_replay_readback: the count plane of the recording in force, (height, width) uint32 — listed candidates per pixel, 0xffffffff = overflow"""
+        out = np.empty((height, width), dtype=np.uint32)
+        self._chk(hip_lib().rt_primary_replay_readback(self._h, out.ctypes.data, out.nbytes), "rt_primary_replay_readback")
+        return out
 
     # ---- light sources (include/rt_abi.h "Light sources", DESIGN.md §22)
     def set_light_sources(self, sources):

@@ -988,6 +988,30 @@ enum { RT_MORPH_NORMALS = 1, RT_MORPH_TANGENTS = 2 };
 int rt_set_morph_targets(rt_ctx* ctx, uint32_t numSets, const rt_morph_set* sets, uint64_t numDeltas, const rt_morph_delta* deltas);
 int rt_update_morphs(rt_ctx* ctx, uint32_t count, const uint32_t* setIds, const float* weights);
 int rt_get_morph_stats(rt_ctx* ctx, rt_morph_stats* out);
+/* ---- Settled primary visibility -------------------------------------------------------------------------------------------------------
+ * While the launch camera (viewInverse, projInverse, size: bitwise) and the scene stay what they were, full-frame direct launches of the throughput build stop
+ * tracing the primary ray: the third launch at a camera (RESTIR_VIS_REST_FRAMES at-rest launches, default and minimum 2) also RECORDS per pixel the leaf record of
+ * the closest deterministic accept and up to K (RESTIR_VIS_K, default RT_VIS_K_DEFAULT, at most 64) stochastic candidates in front of it; later launches REPLAY:
+ * they re-test those records with the frame's seed.  Frames are bit for bit what tracing gives.  A pixel with more than K such candidates keeps tracing.  A camera
+ * change, rt_resize, rt_upload_scene, rt_build_accel, rt_rebuild_accel, every rt_update_* / rt_set_skins / rt_set_morph_targets call, rt_set_stream, a row-band or
+ * latency-build launch, TAA or an object-motion mode on drop the state; the rt_mgpu_* hosts never record; RESTIR_PRIMARY_REPLAY=0 switches it off.  The three
+ * planes, (2 + K) x 4 B per pixel, are allocated by the first recording and freed by rt_resize / rt_destroy.
+ * rt_get_primary_replay_stats: state (0 none, 1 valid), K, and in state 1 the pixel classes of the recording in force (this drains the context); launches since
+ * rt_create.  A replayed query counts as a query in rt_counters.closestHitRays. */
+#define RT_VIS_K_DEFAULT 32
+typedef struct {
+  uint32_t state;             /* 0: none, 1: valid (the next at-rest launch replays) */
+  uint32_t K;                 /* list entries per pixel */
+  uint32_t pixelsSettled;     /* no stochastic candidate in front of the deterministic hit: one record test per frame */
+  uint32_t pixelsListed;      /* 1..K listed candidates */
+  uint32_t pixelsOverflow;    /* more than K: the pixel keeps tracing */
+  uint32_t launchesRecorded, launchesReplayed;
+  uint32_t reserved;
+} rt_primary_replay_stats;    /* 32 B */
+int rt_get_primary_replay_stats(rt_ctx* ctx, rt_primary_replay_stats* out);
+/* the count plane of the recording in force: W x H uint32, listed candidates per pixel (0..K), 0xffffffff = more than K (diagnostics: the histogram that chose
+ * RT_VIS_K_DEFAULT, scripts/primary_replay_probe.py); RT_ERR_INVALID_ARG in state 0.  Drains the context. */
+int rt_primary_replay_readback(rt_ctx* ctx, void* dst, size_t bytes);
 /* Wait for all work on the ctx stream. */
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
@@ -1025,6 +1049,7 @@ static_assert(sizeof(rt_light_stats) == 32, "rt_light_stats");
 static_assert(sizeof(rt_morph_set) == 16, "rt_morph_set");
 static_assert(sizeof(rt_morph_delta) == 16, "rt_morph_delta");
 static_assert(sizeof(rt_morph_stats) == 32, "rt_morph_stats");
+static_assert(sizeof(rt_primary_replay_stats) == 32, "rt_primary_replay_stats");
 #endif
 
 #endif /* RT_ABI_H */
