@@ -1,6 +1,7 @@
 """Randomised parity sweep (GPU vs oracle, every buffer, bit for bit) over scenes, odd image sizes, every RtxState field
 (all five ReSTIRStates, debug views), HDR / sun & sky / no environment, camera motion, both kernel organisations and the
 display pass.  As a test it runs RESTIR_FUZZ_CASES (default 24) configurations with seed RESTIR_FUZZ_SEED (default 1);
+test_random_configurations_bit_exact_veiled runs RESTIR_FUZZ_VEILED_CASES (default 12) of them on the blended variants of the scenes (tests/blend.py), six frames each;
 `python tests/test_gpu_fuzz.py 500 7` runs a longer sweep by hand (2400 configurations — seeds 7, 21, 22 and others — were clean on the final build of round 1)."""
 import os, sys, json
 import numpy as np
@@ -25,11 +26,17 @@ def _skip_case(rng):
     rng.integers(0, 2); rng.uniform(0.5, 1.5)
 
 
-def run_sweep(cases, seed, first=0):
+last_sweep = {}      # what the last run_sweep saw besides mismatches: {"replayed": cases with at least one replay launch}
+
+
+def run_sweep(cases, seed, first=0, veil=False, frames=3):
+    """veil: every case renders the blended variant of its scene (tests/blend.py; every material or every second one by the parity of the case index); frames: per
+    case.  Neither draws a random number: case N of a seed is the same configuration with and without them."""
     from restir_amd.renderer import Renderer
     from oracle.binding import Oracle
     rng = np.random.default_rng(seed)
     bad = 0
+    last_sweep["replayed"] = 0
     for ci in range(cases):
         if ci < first:
             _skip_case(rng)
@@ -47,6 +54,9 @@ def run_sweep(cases, seed, first=0):
         st.sigLuminDirect = float(rng.choice([0.4, 0.05, 3.0, 1e-7, 0.0])); st.sigDepthIndirect = float(rng.choice([1.0, 0.2, 2e6]))
         latency = bool(rng.integers(0, 2))
         desc = sc.desc(env)
+        if veil:
+            import blend
+            desc = blend.veil_desc(desc, every=1 + (ci & 1), alpha=0.5)
         o = Oracle(0); o.upload_scene(desc); o.resize(W, H)
         r = Renderer().setup(0); r.load_scene(desc); r.update(W, H); r.set_traversal(abi.TRAVERSAL_LATENCY if latency else abi.TRAVERSAL_THROUGHPUT)
         if env_kind == 2:
@@ -59,7 +69,7 @@ def run_sweep(cases, seed, first=0):
         desc_txt = dict(case=ci, kind=int(kind), W=W, H=H, env=int(env_kind), depth=st.maxDepth, M=st.RISSampleNum, restir=st.ReSTIRState, mis=st.MIS, den=st.denoise, mod=st.modulate,
                         dbg=st.debugging_mode, latency=latency)
         ok = True
-        for f in range(3):
+        for f in range(frames):
             st.time = 77 + f
             sc.setCamera(eye + vel * f, center, up, fov); sc.updateCamera(W, H)
             cam = sc.getCamera(); o.set_camera(cam); gpu.set_camera(cam)
@@ -72,11 +82,12 @@ def run_sweep(cases, seed, first=0):
                 print("MISMATCH", json.dumps(desc_txt), "frame", f, miss, flush=True)
                 break
         tm = abi.Tonemapper(autoExposure=int(rng.integers(0, 2)), contrast=float(rng.uniform(0.5, 1.5)))
-        o.tonemap(tm, st.debugging_mode, 2); r.tonemap(tm, st.debugging_mode, 2)
+        o.tonemap(tm, st.debugging_mode, frames - 1); r.tonemap(tm, st.debugging_mode, frames - 1)
         if ok and not np.array_equal(o.readback(abi.BUF_LDR), r.readback(abi.BUF_LDR)):
             bad += 1; print("MISMATCH tonemap", json.dumps(desc_txt), flush=True)
         elif ok:
             print("ok", json.dumps(desc_txt), flush=True)
+        last_sweep["replayed"] += 1 if r.primary_replay_stats().launchesReplayed else 0
         r.destroy()
     print("cases", cases, "mismatching", bad)
     return bad
@@ -86,6 +97,14 @@ def run_sweep(cases, seed, first=0):
 @pytest.mark.gpu
 def test_random_configurations_bit_exact():
     assert run_sweep(int(os.environ.get("RESTIR_FUZZ_CASES", "24")), int(os.environ.get("RESTIR_FUZZ_SEED", "1"))) == 0
+
+
+@pytest.mark.gpu
+def test_random_configurations_bit_exact_veiled():
+    """The sweep over blended scenes, six frames per case: the cases whose camera is at rest on the throughput build reach the recording launch of
+    settled primary visibility at their third frame and replay from the fourth on, under random RtxState fields."""
+    assert run_sweep(int(os.environ.get("RESTIR_FUZZ_VEILED_CASES", "12")), int(os.environ.get("RESTIR_FUZZ_SEED", "1")), veil=True, frames=6) == 0
+    assert last_sweep["replayed"] >= 1
 
 
 @pytest.mark.gpu

@@ -88,17 +88,22 @@ def launches(r):
 _refs = {}
 
 
-def reference(sky=False, w=W, h=H, offsets=OFFSETS):
-    """the oracle's frames (camera, {buffer: bytes}) of one sequence, rendered once and shared by the tests that need them"""
-    key = (sky, w, h, tuple(offsets))
+def street_at_the_foliage():
+    sc = refit.street()
+    desc = sc.desc()
+    return sc, desc, foliage_pose(sc, desc)
+
+
+def reference(sky=False, w=W, h=H, offsets=OFFSETS, scene=street_at_the_foliage):
+    """the oracle's frames (camera, {buffer: bytes}) of one sequence, rendered once and shared by the tests that need them; scene: a function that returns
+    (host scene, description, camera pose)"""
+    key = (sky, w, h, tuple(offsets), scene.__name__)
     if key not in _refs:
-        sc = refit.street()
-        desc = sc.desc()
+        sc, desc, pose = scene()
         st = state(sc, w, h)
         o = Oracle(0); o.upload_scene(desc); o.resize(w, h)
         if sky:
             o.set_sun_and_sky(abi.SunAndSky(in_use=1))
-        pose = foliage_pose(sc, desc)
         sc.updateCamera(w, h)
         frames = []
         for f, k in enumerate(offsets):
@@ -110,10 +115,10 @@ def reference(sky=False, w=W, h=H, offsets=OFFSETS):
     return _refs[key]
 
 
-def run_sequence(build, w=W, h=H, offsets=OFFSETS, expect=LAUNCHES, setup=None):
+def run_sequence(build, w=W, h=H, offsets=OFFSETS, expect=LAUNCHES, setup=None, scene=street_at_the_foliage):
     """the sequence on a fresh context; returns (problems, stats after the last frame).  expect: (recorded, replayed) after each frame"""
     sky = build == "sky"
-    sc, desc, frames = reference(sky, w, h, offsets)
+    sc, desc, frames = reference(sky, w, h, offsets, scene)
     st = state(sc, w, h)
     r = renderer(desc, w, h, overlap=0 if build == "serial" else None)
     if sky:

@@ -167,7 +167,7 @@ def f64_closest(rays, V, UV, opaque, nocull, flip, mat, mats, textures, chunk=25
                         acc = al > cut[mi]
                         if abs(al - cut[mi]) < 2e-3: margin[a + r] = 0.0  # the alpha verdict itself is within rounding: either answer is acceptable
                     else:
-                        margin[a + r] = 0.0; acc = al >= 1.0             # blended: stochastic in the path, not pinned here
+                        margin[a + r] = 0.0; acc = al >= 1.0             # blended: stochastic in the path; pinned by tests/test_blend_cpu.py and tests/test_gpu_blend.py
                 if acc:
                     if got == 0:
                         best_t[a + r], best_i[a + r] = tk, k; got = 1
