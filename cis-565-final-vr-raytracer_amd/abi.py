@@ -143,6 +143,17 @@ class RebuildStats(C.Structure):  # rt_rebuild_stats, 32 B
                 ("triPad", C.c_float), ("reserved", C.c_uint32)]
 
 
+class InstancesStats(C.Structure):  # rt_instances_stats, 32 B
+    _fields_ = [("instances", C.c_uint32), ("triangles", C.c_uint32), ("added", C.c_uint32), ("removed", C.c_uint32), ("bytesUploaded", C.c_uint32),
+                ("reallocated", C.c_uint32), ("expandMs", C.c_float), ("ms", C.c_float)]
+
+
+INSTANCE_DT = np.dtype([("objectToWorld", "<f4", 12), ("primMesh", "<u4"), ("flags", "<u4")])   # rt_instance, 56 B
+# int rt_set_instances(rt_ctx*, uint32_t numInstances, const rt_instance*); int rt_get_instances_stats(rt_ctx*, rt_instances_stats*)
+SET_INSTANCES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_void_p]
+GET_INSTANCES_STATS_ARGTYPES = [C.c_void_p, C.c_void_p]
+
+
 class DeformStats(C.Structure):  # rt_deform_stats, 32 B
     _fields_ = [("meshes", C.c_uint32), ("vertices", C.c_uint32), ("instances", C.c_uint32), ("vertexBytesCopied", C.c_uint32), ("skinMs", C.c_float), ("ms", C.c_float),
                 ("reserved", C.c_uint32 * 2)]

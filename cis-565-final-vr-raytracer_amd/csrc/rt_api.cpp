@@ -27,6 +27,7 @@
 #include "taa.h"
 #include "refit.h"
 #include "accel_build.h"
+#include "instances.h"
 #include "deform.h"
 #include "morph.h"
 #include "light_records.h"
@@ -151,9 +152,28 @@ struct rt_ctx {
     int cur = -1;                                // the set the context's tree lives in (-1: the host build's arrays)
     bool ready = false;
     rt_rebuild_stats stats{};
+    // rt_set_instances: what a new instance table is expanded into, twice (a call writes the ones the context does not use; they swap after a build that succeeded);
+    // work.table is table[icur].  Sized with slack (triCap / instCap) by the first call after a host build and by a call whose counts do not fit.
+    bool instReady = false;
+    int icur = 0;
+    uint32_t triCap = 0, instCap = 0;
+    Tri48* table[2] = {nullptr, nullptr}; TriRef* triRef[2] = {nullptr, nullptr}; DevInstance* inst[2] = {nullptr, nullptr};
+    uint32_t* prefix = nullptr;                  // instCap + 1 words (instances.h)
+    uint32_t* dDirty = nullptr; uint32_t* dFlip = nullptr; uint32_t* dCounters = nullptr;   // the refit state's device words at instance capacity
   } rebuild;
   std::vector<void*> rebuildAllocs;
   hipEvent_t evRebuild[4] = {nullptr, nullptr, nullptr, nullptr};   // start, sort begin, sort end, end
+  // rt_set_instances (csrc/instances.hip).  The templates: per triangle of every prim mesh one AlphaRec and one opacity micro-map at
+  // alphaIdx = meshAlphaBase[mesh] + triangle + 1, filled per mesh by the first table in which the mesh has an instance without RT_INST_FORCE_OPAQUE (meshMade).
+  // They live in instAllocs from the first call until rt_upload_scene; once a call has succeeded they are the context's alpha records (DevScene::alphaRec).
+  struct InstTemplates {
+    std::vector<uint32_t> meshAlphaBase;
+    std::vector<uint8_t> meshMade;
+    AlphaRec* dAlpha = nullptr; uint4* dOmm = nullptr; uint32_t* dMeshAlphaBase = nullptr;
+    rt_instances_stats stats{};
+  } inst;
+  std::vector<void*> instAllocs;
+  hipEvent_t evInst[2] = {nullptr, nullptr};     // around the expansion kernels
   // rt_update_vertices / rt_set_skins / rt_update_skins (csrc/deform.hip).  The skins' device buffers (rest pose, staging range, influences, the
   // per-call job and matrix tables) live in skinAllocs: replaced by rt_set_skins, dropped by rt_upload_scene.  The per-instance job table and the result words of
   // k_inst_coord_max live in deformAllocs, made by the first deforming call after an upload.  `stale[k]`: the device rows of skin k's mesh are newer than c->vertices.
@@ -165,6 +185,7 @@ struct rt_ctx {
     rt_vertex* dRest = nullptr; rt_vertex* dStaged = nullptr; rt_skin_influence* dInfluences = nullptr;
     float* dJoints = nullptr; SkinJob* dSkinJobs = nullptr;
     CoordJob* dCoordJobs = nullptr; uint32_t* dOut = nullptr;   // dOut[0]: non-finite staged positions; dOut[1 + j]: coordinate maximum of job j
+    size_t coordCap = 0;                         // instances dCoordJobs / dOut were sized for (rt_set_instances drops them when the table outgrows it)
     rt_deform_stats stats{};
   } deform;
   std::vector<void*> skinAllocs, deformAllocs;
@@ -190,6 +211,7 @@ struct rt_ctx {
   // and the counter live in lightAllocs: replaced by rt_set_light_sources, dropped by rt_upload_scene.  The context keeps no host copy of the light records.
   struct Lights {
     uint32_t bound = 0;                          // records that have a source (0: no binding)
+    std::vector<uint8_t> instances;              // per instance at binding time: 1 = a source names it (rt_set_instances keeps those in place)
     rt_light_source* dSources = nullptr;
     uint32_t* dCounter = nullptr;
     rt_light_stats stats{};
@@ -635,7 +657,7 @@ int rt_destroy(rt_ctx* c)
   (void)hipSetDevice(c->device);
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
-  freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs);
+  freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs); freePool(c->instAllocs);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable, c->vmPlane, c->vmDelta, c->vmDeltaSpare,
                   c->vmDeltaSpare2, c->vmTable}) if(p) (void)hipFree(p);
@@ -664,6 +686,7 @@ int rt_destroy(rt_ctx* c)
   for(hipEvent_t e : c->evMorph) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evLights) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evInst) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -742,6 +765,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->morph = rt_ctx::Morph{}; c->skinMats.clear();
   freePool(c->lightAllocs);   // ... and no light-source binding
   c->lights = rt_ctx::Lights{};
+  freePool(c->instAllocs);    // ... and no instance templates
+  c->inst = rt_ctx::InstTemplates{};
   c->deform = rt_ctx::Deform{};
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
@@ -870,6 +895,38 @@ static void sceneKey(const rt_ctx* c, uint64_t& h0, uint64_t& h1)
   }
 }
 #undef RT_HASH_VEC
+// What HitTest needs for triangle `prim` of prim mesh `pm`, from the mesh's texcoords and material alone (never from an instance): the alpha record (without the
+// texture address, which is per device: `tex` names the texture, -1 for none) and the opacity micro-map, cached per distinct (texture, uv triple, alpha parameters).
+// rt_build_accel makes them per non-opaque leaf record, rt_set_instances per triangle of a prim mesh.
+// (a hash map since round 6: 2 M lookups with 48-byte keys in a std::map were a second of the headline scene's load)
+struct OmmKeyHash { size_t operator()(const std::array<uint32_t, 12>& k) const { uint64_t h = 1469598103934665603ull; for(uint32_t w : k) { h ^= w; h *= 1099511628211ull; } return size_t(h ^ (h >> 29)); } };
+typedef std::unordered_map<std::array<uint32_t, 12>, std::array<uint32_t, 4>, OmmKeyHash> OmmCache;
+static void alphaTemplate(const rt_ctx* c, const rt_prim_mesh& pm, uint32_t prim, OmmCache& ommCache, AlphaRec& a, int32_t& tex, std::array<uint32_t, 4>& omm)
+{
+  const rt_material& m = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)];
+  const uint32_t* ix = &c->indices[pm.firstIndex + 3 * prim];
+  a = AlphaRec{};
+  tex = -1;
+  const rt_vec2 t0 = c->vertices[pm.vertexOffset + ix[0]].texcoord, t1 = c->vertices[pm.vertexOffset + ix[1]].texcoord, t2 = c->vertices[pm.vertexOffset + ix[2]].texcoord;
+  a.uv0x = t0.x; a.uv0y = t0.y; a.uv1x = t1.x; a.uv1y = t1.y; a.uv2x = t2.x; a.uv2y = t2.y;
+  a.baseAlpha = m.pbrBaseColorFactor.w; a.cutoff = m.alphaCutoff; a.alphaMode = m.alphaMode;
+  if(m.pbrBaseColorTexture > -1 && size_t(m.pbrBaseColorTexture) < c->devTextures.size()) {
+    const DevTexture& t = c->devTextures[size_t(m.pbrBaseColorTexture)];
+    tex = m.pbrBaseColorTexture; a.w = t.w; a.h = t.h; a.wrapS = t.wrapS; a.wrapT = t.wrapT; a.filter = t.filter;
+  }
+  std::array<uint32_t, 12> key{};
+  memcpy(key.data(), &a.uv0x, 8 * sizeof(float));
+  key[8] = uint32_t(m.pbrBaseColorTexture); key[9] = uint32_t(a.alphaMode); key[10] = uint32_t(a.wrapS) ^ (uint32_t(a.wrapT) << 16); key[11] = uint32_t(a.filter);
+  auto it = ommCache.find(key);
+  if(it == ommCache.end()) {
+    std::array<uint32_t, 4> o{};
+    const std::vector<uint8_t>* al = (tex >= 0 && size_t(tex) < c->hostAlpha.size()) ? &c->hostAlpha[size_t(m.pbrBaseColorTexture)] : nullptr;
+    buildOpacityMap(a, al, o.data());
+    it = ommCache.emplace(key, o).first;
+  }
+  omm = it->second;
+}
+
 static int buildHostAccel(rt_ctx* c, HostAccel& out)
 {
   LoadTimer lt;
@@ -891,9 +948,7 @@ static int buildHostAccel(rt_ctx* c, HostAccel& out)
   // alpha records for the triangles that go through HitTest (instances without FORCE_OPAQUE)
   std::vector<AlphaRec>& alpha = out.alpha; alpha.assign(1, AlphaRec{});
   std::vector<int32_t>& alphaTex = out.alphaTex; alphaTex.assign(1, -1);
-  // (a hash map since round 6: 2 M lookups with 48-byte keys in a std::map were a second of the headline scene's load)
-  struct KeyHash { size_t operator()(const std::array<uint32_t, 12>& k) const { uint64_t h = 1469598103934665603ull; for(uint32_t w : k) { h ^= w; h *= 1099511628211ull; } return size_t(h ^ (h >> 29)); } };
-  std::unordered_map<std::array<uint32_t, 12>, std::array<uint32_t, 4>, KeyHash> ommCache;
+  OmmCache ommCache;
   ommCache.reserve(1 << 16);
   std::vector<uint32_t> alphaOf;   // by globalId: the record of a triangle that has several references (spatial splits) is made once
   if(bo.tris.size() > bo.triRef.size()) alphaOf.assign(bo.triRef.size(), 0u);
@@ -902,33 +957,14 @@ static int buildHostAccel(rt_ctx* c, HostAccel& out)
     if(T.flags & TRI_OPAQUE) continue;
     if(!alphaOf.empty() && alphaOf[T.globalId]) { T.alphaIdx = alphaOf[T.globalId]; memcpy(T.omm, ommOf[T.alphaIdx].data(), sizeof(T.omm)); continue; }
     const TriRef ref = bo.triRef[T.globalId];
-    const rt_prim_mesh& pm = c->primMeshes[c->instances[ref.inst].primMesh];
-    const rt_material& m = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)];
-    const uint32_t* ix = &c->indices[pm.firstIndex + 3 * ref.prim];
     AlphaRec a{};
     int32_t tex = -1;
-    const rt_vec2 t0 = c->vertices[pm.vertexOffset + ix[0]].texcoord, t1 = c->vertices[pm.vertexOffset + ix[1]].texcoord, t2 = c->vertices[pm.vertexOffset + ix[2]].texcoord;
-    a.uv0x = t0.x; a.uv0y = t0.y; a.uv1x = t1.x; a.uv1y = t1.y; a.uv2x = t2.x; a.uv2y = t2.y;
-    a.baseAlpha = m.pbrBaseColorFactor.w; a.cutoff = m.alphaCutoff; a.alphaMode = m.alphaMode;
-    if(m.pbrBaseColorTexture > -1 && size_t(m.pbrBaseColorTexture) < c->devTextures.size()) {
-      const DevTexture& t = c->devTextures[size_t(m.pbrBaseColorTexture)];
-      tex = m.pbrBaseColorTexture; a.w = t.w; a.h = t.h; a.wrapS = t.wrapS; a.wrapT = t.wrapT; a.filter = t.filter;
-    }
+    std::array<uint32_t, 4> omm{};
+    alphaTemplate(c, c->primMeshes[c->instances[ref.inst].primMesh], ref.prim, ommCache, a, tex, omm);
     T.alphaIdx = uint32_t(alpha.size());
     alpha.push_back(a); alphaTex.push_back(tex);
-    // opacity micro-map, cached per distinct (texture, uv triple, alpha parameters)
-    std::array<uint32_t, 12> key{};
-    memcpy(key.data(), &a.uv0x, 8 * sizeof(float));
-    key[8] = uint32_t(m.pbrBaseColorTexture); key[9] = uint32_t(a.alphaMode); key[10] = uint32_t(a.wrapS) ^ (uint32_t(a.wrapT) << 16); key[11] = uint32_t(a.filter);
-    auto it = ommCache.find(key);
-    if(it == ommCache.end()) {
-      std::array<uint32_t, 4> o{};
-      const std::vector<uint8_t>* al = (tex >= 0 && size_t(tex) < c->hostAlpha.size()) ? &c->hostAlpha[size_t(m.pbrBaseColorTexture)] : nullptr;
-      buildOpacityMap(a, al, o.data());
-      it = ommCache.emplace(key, o).first;
-    }
-    memcpy(T.omm, it->second.data(), sizeof(T.omm));
-    if(!alphaOf.empty()) { alphaOf[T.globalId] = T.alphaIdx; ommOf.resize(alpha.size()); ommOf[T.alphaIdx] = it->second; }
+    memcpy(T.omm, omm.data(), sizeof(T.omm));
+    if(!alphaOf.empty()) { alphaOf[T.globalId] = T.alphaIdx; ommOf.resize(alpha.size()); ommOf[T.alphaIdx] = omm; }
   }
   lt.lap("alpha records + micro-maps");
   return RT_OK;
@@ -2298,9 +2334,9 @@ template <class P> static std::vector<uint32_t> instanceBits(size_t nInst, P pre
 }
 
 // largest |world coordinate| over the triangles of instance i under matrix m: the builder's expression (buildBvh8, flatten), per instance
-static float instanceCoordMax(const rt_ctx* c, uint32_t i, const float* m)
+static float meshCoordMax(const rt_ctx* c, uint32_t primMesh, const float* m)
 {
-  const rt_prim_mesh& pm = c->primMeshes[c->instances[i].primMesh];
+  const rt_prim_mesh& pm = c->primMeshes[primMesh];
   float sm = 0.f;
   for(uint32_t k = 0; k < pm.indexCount; k++) {
     const rt_vec3& q = c->vertices[pm.vertexOffset + c->indices[pm.firstIndex + k]].position;
@@ -2310,6 +2346,7 @@ static float instanceCoordMax(const rt_ctx* c, uint32_t i, const float* m)
   }
   return sm;
 }
+static float instanceCoordMax(const rt_ctx* c, uint32_t i, const float* m) { return meshCoordMax(c, c->instances[i].primMesh, m); }
 
 // what every update needs and no frame does, derived once per tree from the device arrays: the record -> node map, the level ranges, the per-instance maxima
 static int ensureRefitState(rt_ctx* c)
@@ -2502,6 +2539,34 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
   return RT_OK;
 }
 
+}  // extern "C"
+
+// The context adopts a tree the device builder has completed (rt_rebuild_accel, rt_set_instances): `next` is c->ds with the new arrays and pad; the node and record
+// counts, the traversal stack and rt_accel_stats' numbers follow from `res`.  Where the new stack cannot be allocated the previous tree stays, with its stack.
+static int adoptDeviceTree(rt_ctx* c, const DevScene& next, const AccelBuildResult& res, uint32_t n)
+{
+  const int depth = int(res.levels.size());
+  const int stackTotal = std::max(8, ((depth + 1 + 3) / 4) * 4);
+  const DevScene old = c->ds;
+  c->ds = next;
+  c->ds.numNodes = res.nodes; c->ds.numTris = n;
+  if(stackTotal != old.stackTotal) {
+    c->ds.stackTotal = stackTotal; c->ds.stackEntries = stackTotal;
+    if(const int rc = ensureStackOverflow(c)) {
+      const std::string msg = c->err;
+      c->ds = old; c->ds.stackOvf = c->ds.stackOvfInd = nullptr; c->ds.stackOvfThreads = 0;
+      (void)ensureStackOverflow(c);
+      c->err = msg;
+      return rc;
+    }
+  }
+  c->numNodes = res.nodes; c->numRefs = n; c->spatialSplits = 0; c->maxDepth = depth;
+  c->sahNodeSteps = c->sahTriSteps = 0;   // (the host builder's SAH expectation: not computed on the device)
+  return RT_OK;
+}
+
+extern "C" {
+
 /* ---- rebuilding on the device: LBVH -> BVH8 (include/rt_abi.h "Rebuilding on the device", csrc/accel_build.hip) ---- */
 int rt_rebuild_accel(rt_ctx* c)
 {
@@ -2562,24 +2627,10 @@ int rt_rebuild_accel(rt_ctx* c)
     RT_HIP(c, hipStreamSynchronize(s));
     // ---- swap ----
     const int depth = int(res.levels.size());
-    const int stackTotal = std::max(8, ((depth + 1 + 3) / 4) * 4);
-    const DevScene old = c->ds;
-    c->ds.nodes = T.nodes; c->ds.tris = T.tris; c->ds.alphaByTri = T.alphaByTri;
-    c->ds.numNodes = res.nodes; c->ds.numTris = n;
-    if(stackTotal != old.stackTotal) {
-      c->ds.stackTotal = stackTotal; c->ds.stackEntries = stackTotal;
-      if((rc = ensureStackOverflow(c))) {   // the previous tree stays, with its stack
-        const std::string msg = c->err;
-        c->ds = old; c->ds.stackOvf = c->ds.stackOvfInd = nullptr; c->ds.stackOvfThreads = 0;
-        (void)ensureStackOverflow(c);
-        c->err = msg;
-        return rc;
-      }
-    }
+    DevScene next = c->ds;
+    next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri; next.triPad = triPad;
+    if((rc = adoptDeviceTree(c, next, res, n))) return rc;
     B.cur = target;
-    c->ds.triPad = triPad;
-    c->numNodes = res.nodes; c->numRefs = n; c->spatialSplits = 0; c->maxDepth = depth;
-    c->sahNodeSteps = c->sahTriSteps = 0;   // (the host builder's SAH expectation: not computed on the device)
     // rt_update_instances works on the new tree: its maps come from the build
     R.levels = res.levels; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
     st.nodes = res.nodes; st.levels = uint32_t(depth); st.maxDepth = uint32_t(depth);
@@ -2597,6 +2648,237 @@ int rt_get_rebuild_stats(rt_ctx* c, rt_rebuild_stats* out)
 {
   if(!c || !out) return RT_ERR_INVALID_ARG;
   *out = c->rebuild.stats;
+  return RT_OK;
+}
+
+}  // extern "C"
+
+/* ---- adding and removing instances (include/rt_abi.h "Adding and removing instances", csrc/instances.hip) ---- */
+static bool emissiveMesh(const rt_ctx* c, uint32_t primMesh)   // the scene's light rule (host/scene.cpp createTrigLightBuffer), as rt_set_skins applies it
+{
+  const rt_prim_mesh& pm = c->primMeshes[primMesh];
+  const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
+  return e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f;
+}
+
+// the buffers of rt_set_instances at a capacity: the rebuild's working buffers and two trees, and what the expansion writes, twice
+static hipError_t allocInstanceBuffers(rt_ctx::Rebuild& B, uint32_t triCap, uint32_t instCap, std::vector<void*>& pool)
+{
+  hipError_t e = accelBuildAlloc(B.work, B.set, triCap, pool);
+  auto get = [&](size_t bytes, auto** out) {
+    if(e != hipSuccess) return;
+    void* p = nullptr;
+    e = hipMalloc(&p, bytes);
+    if(e == hipSuccess) { pool.push_back(p); *out = static_cast<std::remove_reference_t<decltype(**out)>*>(p); }
+  };
+  B.table[0] = B.work.table;
+  get(size_t(triCap) * sizeof(Tri48), &B.table[1]);
+  for(int k = 0; k < 2; k++) { get(size_t(triCap) * sizeof(TriRef), &B.triRef[k]); get(size_t(instCap) * sizeof(DevInstance), &B.inst[k]); }
+  get((size_t(instCap) + 1) * 4, &B.prefix);
+  get(instanceWords(instCap) * 4, &B.dDirty); get(instanceWords(instCap) * 4, &B.dFlip); get(16, &B.dCounters);
+  if(e == hipSuccess) { B.triCap = triCap; B.instCap = instCap; B.icur = 0; B.cur = -1; B.instReady = true; B.ready = true; }
+  return e;
+}
+
+// the templates of prim mesh `mesh` (alphaTemplate per triangle, texture addresses of this device) at their place in the device arrays
+static int makeMeshTemplates(rt_ctx* c, uint32_t mesh, uint32_t* bytesUploaded)
+{
+  rt_ctx::InstTemplates& TP = c->inst;
+  if(const int rc = syncHostVertices(c, int(mesh))) return rc;   // (the texcoords are read from the context's copy)
+  const rt_prim_mesh& pm = c->primMeshes[mesh];
+  const uint32_t nt = pm.indexCount / 3;
+  std::vector<AlphaRec> alpha(nt);
+  std::vector<std::array<uint32_t, 4>> omm(nt);
+  OmmCache cache;
+  for(uint32_t p = 0; p < nt; p++) {
+    int32_t tex = -1;
+    alphaTemplate(c, pm, p, cache, alpha[p], tex, omm[p]);
+    if(tex >= 0) alpha[p].bgra = c->devTextures[size_t(tex)].bgra;
+  }
+  const size_t first = size_t(TP.meshAlphaBase[mesh]) + 1;
+  if(nt) {
+    RT_HIP(c, hipMemcpy(TP.dAlpha + first, alpha.data(), size_t(nt) * sizeof(AlphaRec), hipMemcpyHostToDevice));
+    RT_HIP(c, hipMemcpy(TP.dOmm + first, omm.data(), size_t(nt) * 16, hipMemcpyHostToDevice));
+  }
+  *bytesUploaded += nt * uint32_t(sizeof(AlphaRec) + 16);
+  TP.meshMade[mesh] = 1;
+  return RT_OK;
+}
+
+extern "C" {
+
+int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instances)
+{
+  if(int rc = needTree(c, "rt_set_instances")) return rc;
+  // ---- the whole table is checked before anything changes
+  if(!instances) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: NULL instance table");
+  if(numInstances == 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: an instance table needs at least one instance");
+  const size_t nOld = c->instances.size();
+  std::vector<DevInstance> rows(numInstances);   // the builder's own expression (buildBvh8, flatten), inverse included
+  std::vector<uint32_t> prefix(size_t(numInstances) + 1, 0u);
+  uint64_t total = 0;
+  auto refuse = [&](uint32_t i, const char* what) { c->err = "rt_set_instances: instance " + std::to_string(i) + ": " + what; return RT_ERR_INVALID_ARG; };
+  for(uint32_t i = 0; i < numInstances; i++) {
+    const rt_instance& in = instances[i];
+    if(in.primMesh >= c->primMeshes.size()) return refuse(i, "prim mesh out of range");
+    for(int a = 0; a < 12; a++) if(!std::isfinite(in.objectToWorld[a])) return refuse(i, "non-finite matrix entry");
+    DevInstance& di = rows[i];
+    memcpy(di.o2w, in.objectToWorld, sizeof(di.o2w));
+    float det;
+    inverseAffine(di.o2w, di.w2o, &det);
+    if(!(det != 0.0f) || !std::isfinite(det)) return refuse(i, "singular matrix");
+    for(int a = 0; a < 12; a++) if(!std::isfinite(di.w2o[a])) return refuse(i, "the matrix has no finite inverse");
+    di.primMesh = in.primMesh; di.flags = in.flags; di.pad[0] = di.pad[1] = 0;
+    prefix[i] = uint32_t(total) | (det < 0.0f ? INST_PREFIX_FLIP : 0u);
+    total += c->primMeshes[in.primMesh].indexCount / 3;
+    if(total > uint64_t(INST_PREFIX_MASK)) return refuse(i, "the table has more than 2^31 - 1 triangles");
+  }
+  if(total == 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: the table has no triangles");
+  prefix[numInstances] = uint32_t(total);
+  if(c->ds.lightInfo.trigLightSize > 0) {   // the emitter rule: light records, alias table and binding name instances by index
+    for(uint32_t i = 0; i < nOld; i++)
+      if((emissiveMesh(c, c->instances[i].primMesh) || (i < c->lights.instances.size() && c->lights.instances[i])) && (i >= numInstances || memcmp(&c->instances[i], &instances[i], sizeof(rt_instance)) != 0))
+        return refuse(i, "an emissive instance must stay in place, byte for byte (move it with rt_update_instances)");
+    for(uint32_t i = 0; i < numInstances; i++)
+      if(emissiveMesh(c, instances[i].primMesh) && !(i < nOld && emissiveMesh(c, c->instances[i].primMesh)))
+        return refuse(i, "a new instance of an emissive prim mesh (its triangle-light records would be missing)");
+  }
+  const uint32_t n = uint32_t(total);
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // drains the frames in flight, like rt_rebuild_accel
+  rt_ctx::Refit& R = c->refit;
+  rt_ctx::Rebuild& B = c->rebuild;
+  rt_ctx::InstTemplates& TP = c->inst;
+  int rc;
+  rt_instances_stats st{};
+  st.instances = numInstances; st.triangles = n;
+  {
+    size_t same = 0;
+    while(same < nOld && same < numInstances && memcmp(&c->instances[same], &instances[same], sizeof(rt_instance)) == 0) same++;
+    st.added = uint32_t(numInstances - same); st.removed = uint32_t(nOld - same);
+  }
+  // ---- the pad: triPadOf over the new instances' maxima; an instance that stays where it was keeps the maximum the update calls maintain
+  std::vector<float> instMax(numInstances);
+  std::vector<uint8_t> flip(numInstances);
+  for(uint32_t i = 0; i < numInstances; i++) {
+    flip[i] = uint8_t(prefix[i] >> 31);
+    if(R.ready && i < nOld && memcmp(&c->instances[i], &instances[i], sizeof(rt_instance)) == 0) { instMax[i] = R.instMax[i]; continue; }
+    if((rc = syncHostVertices(c, int(instances[i].primMesh)))) return rc;   // meshCoordMax reads the context's copy: skinned and morphed meshes are current on the device only
+    instMax[i] = meshCoordMax(c, instances[i].primMesh, rows[i].o2w);
+  }
+  const float triPad = triPadOf(instMax);
+  // ---- templates, once per prim mesh
+  if(!TP.dAlpha) {
+    std::vector<uint32_t> base(c->primMeshes.size(), 0u);
+    uint64_t meshTris = 0;
+    for(size_t m = 0; m < c->primMeshes.size(); m++) { base[m] = uint32_t(meshTris); meshTris += c->primMeshes[m].indexCount / 3; }
+    if(meshTris >= 0xffffffffull) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: the prim meshes have more than 2^32 - 2 triangles");
+    const uint32_t* up = nullptr;
+    rc = allocZeroed(c, c->instAllocs, size_t(meshTris) + 1, &TP.dAlpha);
+    if(!rc) rc = allocZeroed(c, c->instAllocs, size_t(meshTris) + 1, &TP.dOmm);
+    if(!rc) rc = upload(c, c->instAllocs, base.data(), base.size(), &up);
+    if(rc) { freePool(c->instAllocs); TP = rt_ctx::InstTemplates{}; return rc; }
+    TP.dMeshAlphaBase = const_cast<uint32_t*>(up);
+    TP.meshAlphaBase = base; TP.meshMade.assign(base.size(), 0);
+    st.bytesUploaded += uint32_t(base.size() * 4);
+  }
+  for(uint32_t i = 0; i < numInstances; i++)
+    if(!(instances[i].flags & RT_INST_FORCE_OPAQUE) && !TP.meshMade[instances[i].primMesh])
+      if((rc = makeMeshTemplates(c, instances[i].primMesh, &st.bytesUploaded))) return rc;
+  // ---- capacity: a table that does not fit the buffers gets new ones; the old ones go once the new tree is in place
+  const bool fits = B.instReady && n <= B.triCap && numInstances <= B.instCap;
+  rt_ctx::Rebuild fresh;
+  std::vector<void*> freshPool;
+  if(!fits) {
+    const uint32_t triCap = uint32_t(std::min<uint64_t>(uint64_t(n) + n / 8, INST_PREFIX_MASK)), instCap = numInstances + numInstances / 8;
+    const hipError_t e = allocInstanceBuffers(fresh, triCap, instCap, freshPool);
+    if(e != hipSuccess) {
+      freePool(freshPool);
+      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+    st.reallocated = 1u;
+  }
+  rt_ctx::Rebuild& W = fits ? B : fresh;
+  // what a call that fails puts back: the shared working buffers describe the context's table again, new buffers go
+  auto giveUp = [&] { if(fits) { B.work.n = uint32_t(c->numTris); B.work.table = B.table[B.icur]; } else freePool(freshPool); };
+  for(hipEvent_t& e : c->evRebuild) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
+  for(hipEvent_t& e : c->evInst) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
+  for(hipEvent_t& e : c->evRefit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
+  const int ti = fits ? 1 - B.icur : 0, ts = fits ? (B.cur == 0 ? 1 : 0) : 0;
+  const AccelBuildSet& T = W.set[ts];
+  const size_t words = instanceWords(numInstances);
+  hipStream_t s = c->stream;
+  AccelBuildResult res;
+  hipError_t he = hipSuccess;
+  int br = ACCEL_BUILD_HIP;
+  do {   // (one pass: a HIP error leaves through `break` with `he` set)
+    if((he = hipEventRecord(c->evRebuild[0], s)) != hipSuccess) break;
+    if((he = hipMemcpyAsync(W.inst[ti], rows.data(), size_t(numInstances) * sizeof(DevInstance), hipMemcpyHostToDevice, s)) != hipSuccess) break;
+    if((he = hipMemcpyAsync(W.prefix, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) break;
+    if((he = hipEventRecord(c->evInst[0], s)) != hipSuccess) break;
+    InstExpandArgs x{};
+    x.prefix = W.prefix; x.instances = W.inst[ti]; x.meshAlphaBase = TP.dMeshAlphaBase; x.ommTemplate = TP.dOmm;
+    x.triRef = W.triRef[ti]; x.table = W.table[ti]; x.flipBits = W.dFlip; x.numInst = numInstances; x.numTris = n;
+    if((he = launchExpandInstances(s, x)) != hipSuccess) break;
+    if((he = hipEventRecord(c->evInst[1], s)) != hipSuccess) break;
+    if((he = hipMemsetAsync(W.dDirty, 0xff, words * 4, s)) != hipSuccess) break;   // every instance marked moved
+    if((he = hipMemsetAsync(W.dCounters, 0, 16, s)) != hipSuccess) break;
+    W.work.n = n; W.work.table = W.table[ti];
+    RefitArgs a{};
+    a.nodes = T.nodes; a.tris = T.tris; a.triRef = W.triRef[ti]; a.instances = W.inst[ti];
+    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+    a.dirtyBits = W.dDirty; a.flipBits = W.dFlip; a.recNode = T.recNode; a.nodeDirty = W.work.nodeDirty; a.counters = W.dCounters;
+    a.numRecs = n; a.pad = triPad; a.full = 1;
+    br = accelBuildRun(s, W.work, T, a, TP.dAlpha, STACK_MAX, c->evRebuild + 1, res, &he);
+    if(br != ACCEL_BUILD_OK) break;
+    br = ACCEL_BUILD_HIP;
+    if((he = hipEventRecord(c->evRebuild[3], s)) != hipSuccess) break;
+    if((he = hipStreamSynchronize(s)) != hipSuccess) break;
+    br = ACCEL_BUILD_OK;
+  } while(false);
+  if(br != ACCEL_BUILD_OK) {   // the context's table, tree and records were not written: only the spare ones and the working buffers
+    (void)hipStreamSynchronize(s);
+    giveUp();
+    if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_set_instances: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
+    if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: BVH8 deeper than the traversal stack");
+    c->err = std::string("rt_set_instances: ") + accelBuildWhy(br);
+    return RT_ERR_HIP;
+  }
+  st.bytesUploaded += uint32_t(size_t(numInstances) * sizeof(DevInstance) + prefix.size() * 4 + 24);   // (24: the seed of the build's centre bounds, accelBuildRun)
+  // ---- swap
+  DevScene next = c->ds;
+  next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri; next.triRef = W.triRef[ti]; next.instances = W.inst[ti];
+  next.alphaRec = TP.dAlpha; next.triPad = triPad;
+  if((rc = adoptDeviceTree(c, next, res, n))) { giveUp(); return rc; }
+  if(!fits) { freePool(c->rebuildAllocs); c->rebuildAllocs.swap(freshPool); B = fresh; }
+  B.icur = ti; B.cur = ts;
+  c->instances.assign(instances, instances + numInstances);
+  c->numTris = n;
+  // rt_update_instances and the deform calls work on the new tree: their maps come from the build, the per-instance state from the new table
+  R.ready = true;
+  R.inst = rows; R.instMax = instMax; R.flip = flip; R.levels = res.levels;
+  R.dDirty = B.dDirty; R.dFlip = B.dFlip; R.dCounters = B.dCounters; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
+  if(c->deform.dOut && numInstances > c->deform.coordCap) { freePool(c->deformAllocs); c->deform.dCoordJobs = nullptr; c->deform.dOut = nullptr; c->deform.coordCap = 0; }
+  c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // every instance's previous matrix is its current one
+  c->refN = 0;   // the reference sums start again
+  const int depth = int(res.levels.size());
+  rt_rebuild_stats rs{};
+  rs.triangles = n; rs.nodes = res.nodes; rs.levels = rs.maxDepth = uint32_t(depth); rs.triPad = triPad;
+  (void)hipEventElapsedTime(&rs.ms, c->evRebuild[0], c->evRebuild[3]);
+  (void)hipEventElapsedTime(&rs.sortMs, c->evRebuild[1], c->evRebuild[2]);
+  B.stats = rs;
+  st.ms = rs.ms;
+  (void)hipEventElapsedTime(&st.expandMs, c->evInst[0], c->evInst[1]);
+  TP.stats = st;
+  return resetSeedPlane(c);   // the records are in a new order
+}
+
+int rt_get_instances_stats(rt_ctx* c, rt_instances_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->inst.stats;
   return RT_OK;
 }
 
@@ -2656,6 +2938,7 @@ static int ensureDeformBuffers(rt_ctx* c)
   int rc;
   if((rc = allocZeroed(c, c->deformAllocs, std::max<size_t>(nInst, 1), &D.dCoordJobs))) return rc;
   if((rc = allocZeroed(c, c->deformAllocs, nInst + 1, &D.dOut))) return rc;
+  D.coordCap = nInst;
   for(hipEvent_t& e : c->evDeform) if(!e) RT_HIP(c, hipEventCreate(&e));
   return RT_OK;
 }
@@ -3205,6 +3488,8 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
   c->lightAllocs = fresh;
   L = rt_ctx::Lights{};
   L.bound = numTrig; L.dSources = const_cast<rt_light_source*>(dSrc); L.dCounter = dCounter;
+  L.instances.assign(nInst, 0);
+  for(uint32_t k = 0; k < numTrig; k++) L.instances[sources[k].instance] = 1;
   L.stats.bound = numTrig;
   return RT_OK;
 }

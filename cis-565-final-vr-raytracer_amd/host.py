@@ -31,6 +31,7 @@ def host_lib():
             "rth_scene_get_camera_pose": [C.c_void_p, C.c_void_p], "rth_scene_update_camera": [C.c_void_p, C.c_int, C.c_int],
             "rth_scene_get_camera": [C.c_void_p, C.c_void_p], "rth_scene_light_weights": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_scene_update_instances": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
+            "rth_scene_set_instances": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
             "rth_scene_light_sources": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
@@ -116,6 +117,12 @@ class Scene:
         assert xf.shape[0] == ids.size
         if host_lib().rth_scene_update_instances(self._h, ids.ctypes.data, xf.ctypes.data, ids.size) != 0:
             raise ValueError("Scene.updateInstances: instance id out of range")
+    def setInstances(self, inst_array):
+        """Scene::setInstances: replace the instance list (abi.INSTANCE_DT records or n x 56 bytes); the nodes, the triangle-light records and the statistics follow;
+        desc() afterwards describes the new scene"""
+        rows = np.ascontiguousarray(inst_array).view(np.uint8).reshape(-1)
+        if rows.size % 56 or host_lib().rth_scene_set_instances(self._h, rows.ctypes.data, rows.size // 56) != 0:
+            raise ValueError("Scene.setInstances: an empty table, a row that is not 56 bytes, or a prim mesh out of range")
     def updateVertices(self, prim_mesh, first, rows):
         """Scene::updateVertices: rows (abi.VERTEX_DT records or n x 32 bytes) replace vertices [first, first + n) of one prim mesh; the triangle-light records are
         recomputed; desc() afterwards describes the deformed scene"""

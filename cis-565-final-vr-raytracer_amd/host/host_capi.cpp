@@ -70,6 +70,10 @@ void rth_scene_stats(void* s, uint64_t* out9)
   out9[0] = st.triangles; out9[1] = st.instancedTriangles; out9[2] = st.vertices; out9[3] = st.primMeshes; out9[4] = st.nodes;
   out9[5] = st.materials; out9[6] = st.textures; out9[7] = st.puncLights; out9[8] = st.trigLights;
 }
+int rth_scene_set_instances(void* s, const rt_instance* instances, uint32_t count)
+{
+  return static_cast<Scene*>(s)->setInstances(instances, count) ? 0 : -1;
+}
 int rth_scene_update_instances(void* s, const uint32_t* ids, const float* transforms, uint32_t count)
 {
   return static_cast<Scene*>(s)->updateInstances(ids, transforms, count) ? 0 : -1;

@@ -89,6 +89,24 @@ class AccelStructure {
     if(rt_rebuild_accel(m_ctx) != RT_OK) { fprintf(stderr, "AccelStructure::rebuild: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
+  // Add and remove instances without a new scene (include/rt_abi.h "Adding and removing instances"): the whole new table.  Emitters stay where they are in it.
+  bool setInstances(const rt_instance* instances, uint32_t count)
+  {
+    if(rt_set_instances(m_ctx, count, instances) != RT_OK) { fprintf(stderr, "AccelStructure::setInstances: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  // Scene::setInstances (host side: nodes, instance table, light records) + setInstances().  What the scene would refuse (an empty table, a prim mesh out of
+  // range) is checked first and the device, whose checks are the stricter ones, is asked before the scene changes: a refused table changes neither.
+  bool setInstances(Scene& scene, const rt_instance* instances, uint32_t count)
+  {
+    bool sceneTakesIt = instances && count > 0;
+    for(uint32_t k = 0; sceneTakesIt && k < count; k++) sceneTakesIt = instances[k].primMesh < scene.getScene().primMeshes.size();
+    if(!sceneTakesIt) { fprintf(stderr, "AccelStructure::setInstances: an empty table or a prim mesh out of range\n"); return false; }
+    if(!setInstances(instances, count)) return false;
+    if(!scene.setInstances(instances, count)) { fprintf(stderr, "AccelStructure::setInstances: the scene refused the table\n"); return false; }
+    return true;
+  }
+  rt_instances_stats instancesStats() const { rt_instances_stats s{}; (void)rt_get_instances_stats(m_ctx, &s); return s; }
   rt_rebuild_stats rebuildStats() const { rt_rebuild_stats s{}; (void)rt_get_rebuild_stats(m_ctx, &s); return s; }
   void destroy() {}  // owned by the context
  private:

@@ -284,6 +284,28 @@ bool Scene::updateInstances(const uint32_t* ids, const float* transforms, uint32
   return true;
 }
 
+bool Scene::setInstances(const rt_instance* instances, uint32_t count)
+{
+  if(!instances || count == 0) return false;
+  for(uint32_t k = 0; k < count; k++) if(instances[k].primMesh >= m_gltf.primMeshes.size()) return false;
+  m_gltf.nodes.resize(count);
+  m_stats.instancedTriangles = 0;
+  for(uint32_t k = 0; k < count; k++) {
+    M4 m = M4::identity();
+    for(int r = 0; r < 3; r++) for(int c = 0; c < 4; c++) m.at(r, c) = instances[k].objectToWorld[r * 4 + c];
+    m_gltf.nodes[k].worldMatrix = m;
+    m_gltf.nodes[k].primMesh = int(instances[k].primMesh);
+    m_stats.instancedTriangles += m_gltf.primMeshes[instances[k].primMesh].indexCount / 3;
+  }
+  m_stats.nodes = count;
+  m_instances.assign(instances, instances + count);
+  createTrigLightBuffer();   // (as updateInstances; under the emitter rule the records keep their order and count)
+  m_stats.trigLights = uint32_t(m_trigLights.size());
+  if(m_lightBufInfo.puncLightSize > 0 || m_lightBufInfo.trigLightSize > 0)
+    m_lightBufInfo.trigSampProb = m_trigLightWeight / (m_trigLightWeight + m_puncLightWeight);
+  return true;
+}
+
 bool Scene::updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows)
 {
   if(primMesh >= m_gltf.primMeshes.size()) return false;

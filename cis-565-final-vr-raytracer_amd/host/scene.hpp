@@ -89,6 +89,11 @@ class Scene {
   // getDesc() afterwards describes the moved scene (rt_update_lights takes trigLights / puncLights / lightInfo from it).  The reference moves a node by editing
   // nvh::GltfScene::m_nodes and rebuilding its TLAS (src/accelstruct.cpp:132-162).
   bool updateInstances(const uint32_t* ids, const float* transforms, uint32_t count);
+  // Replace the instance list (include/rt_abi.h "Adding and removing instances"): the drawable nodes become one per row of `instances` (world matrix and prim mesh;
+  // the rows' flags are kept as given), the triangle-light records are recomputed as by updateInstances and the statistics follow.  False (nothing changed) for an
+  // empty or NULL table or a prim mesh out of range.  The emitter rule is the device's to enforce (rt_set_instances): under it the light records keep their order
+  // and count.  AccelStructure::setInstances hands the same rows to the device; getDesc() afterwards describes the new scene.
+  bool setInstances(const rt_instance* instances, uint32_t count);
   // Deform a prim mesh on the host (include/rt_abi.h "Deforming meshes"): rows replace vertices [first, first + count) of the mesh in the vertex buffer and their
   // positions in the loader's arrays, and the triangle-light records are recomputed as by updateInstances, so a deformed emitter lights from its new shape
   // (rt_update_vertices takes the same rows, rt_update_lights the records from getDesc()).  False (nothing changed) for a mesh or a range out of bounds.

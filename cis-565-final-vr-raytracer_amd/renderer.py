@@ -22,6 +22,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
+               "rt_set_instances", "rt_get_instances_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
@@ -127,6 +128,9 @@ def hip_lib():
         if hasattr(L, "rt_rebuild_accel"):   # rebuilding on the device (absent from older A/B libraries)
             L.rt_rebuild_accel.argtypes = [C.c_void_p]
             L.rt_get_rebuild_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_instances"):   # adding and removing instances (absent from older A/B libraries)
+            L.rt_set_instances.argtypes = abi.SET_INSTANCES_ARGTYPES
+            L.rt_get_instances_stats.argtypes = abi.GET_INSTANCES_STATS_ARGTYPES
         if hasattr(L, "rt_set_object_motion"):   # object motion vectors (absent from older A/B libraries)
             L.rt_set_object_motion.argtypes = [C.c_void_p, C.c_int]
             L.rt_object_motion_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -466,6 +470,20 @@ class Renderer:
     def rebuild_stats(self):
         s = abi.RebuildStats()
         self._chk(hip_lib().rt_get_rebuild_stats(self._h, C.byref(s)), "rt_get_rebuild_stats")
+        return s
+
+    # ---- adding and removing instances (include/rt_abi.h "Adding and removing instances")
+    def set_instances(self, inst_array):
+        """rt_set_instances: inst_array = abi.INSTANCE_DT records (or n x 56 bytes), the whole new instance table.  Expands it into the device builder's input and
+        builds a new tree on the GPU; drains the frames in flight.  Emissive instances must stay in place (include/rt_abi.h, the emitter rule)"""
+        rows = np.ascontiguousarray(inst_array).view(np.uint8).reshape(-1)
+        if rows.size % 56:
+            raise ValueError("set_instances: 56 bytes per instance")
+        self._chk(hip_lib().rt_set_instances(self._h, rows.size // 56, rows.ctypes.data), "rt_set_instances")
+
+    def instances_stats(self):
+        s = abi.InstancesStats()
+        self._chk(hip_lib().rt_get_instances_stats(self._h, C.byref(s)), "rt_get_instances_stats")
         return s
 
     # ---- deforming meshes (include/rt_abi.h "Deforming meshes", DESIGN.md §21)

@@ -751,6 +751,55 @@ typedef struct {
 int rt_rebuild_accel(rt_ctx* ctx);                       /* LBVH -> BVH8 on the GPU from the context's current scene */
 int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
 /* ------------------------------------------------------------------------------------------------------------------
+ * Adding and removing instances (added within ABI 2.4, no version bump; csrc/instances.hip).  rt_update_instances moves instances, the deform
+ * calls bend meshes, rt_rebuild_accel gives a new topology; what none of them can do is change WHICH objects exist.  rt_set_instances replaces the whole instance
+ * table without a new scene: prim meshes, vertices (as they are on the device now, skins and morphs applied), indices, materials, textures, lights and environment
+ * stay as uploaded.  What a leaf record holds besides its position is a function of (prim mesh, triangle, instance flags) only; it is kept per prim mesh on the
+ * device (the templates: one alpha record and one opacity micro-map per triangle, made the first time a mesh has an instance without RT_INST_FORCE_OPAQUE) and
+ * expanded per (instance, triangle) pair by a kernel; positions, TRI_FLIP and the tree come from rt_rebuild_accel's pipeline.  Frames, rays and the tree are bit
+ * for bit those of rt_upload_scene + rt_build_accel + rt_rebuild_accel of the new description (leaf records differ in alphaIdx only, whose numbering is per mesh).
+ *
+ * rt_set_instances(ctx, numInstances, instances): valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise), on a host-built or device-built tree.
+ *   Afterwards the context is in the state rt_rebuild_accel leaves: the tree is a device-built tree over the new set (no SAH, no spatial splits: it traces slower
+ *   than a host-built one until a later rt_build_accel, which builds the new scene because the context's copy of the table is replaced); rt_update_instances,
+ *   rt_update_vertices, rt_update_skins, rt_update_morphs and rt_rebuild_accel work on it; rt_accel_stats and rt_accel_readback describe it.
+ *   Refusals (RT_ERR_INVALID_ARG, nothing changes, rt_last_error names the first offender): a NULL table; numInstances == 0; a total triangle count of 0 or above
+ *   2^31 - 1 (bit 31 of the record index is used by the call); a prim mesh out of range; a matrix rt_update_instances would refuse (a non-finite entry, a
+ *   determinant that is zero or not finite, no finite inverse); the emitter rule.  rt_upload_scene refuses no instance flag bits, and neither does this call.
+ *   The emitter rule: triangle-light records, the alias table and the light-source binding name instances by index.  In a scene with triangle lights, every
+ *   index i below the old count whose old instance has an emissive prim mesh (the scene's light rule, as rt_set_skins applies it: luminance of the material's
+ *   emissiveFactor > 1e-2), or that a light-source binding names, must hold the same rt_instance in the new table, all bytes of primMesh, flags and objectToWorld equal, and no other new instance may use
+ *   an emissive prim mesh.  A host puts its emitters first and moves them with rt_update_instances.  A scene without triangle lights is not affected.
+ *   Ordering: like rt_rebuild_accel it joins the frames in flight, runs on the context's main stream and returns after its kernels completed.  It leaves the frame
+ *   buffers, the SVGF / TAA histories and the stream-priority decision alone and resets the reference-mode sums (n -> 0).  It also drops the settled primary
+ *   visibility (as rt_build_accel does), resets the primary seed plane, and makes every instance's previous matrix its current one: object and vertex motion see
+ *   no motion across the call, and a surface that appeared restarts through the G-buffer tests.  No other per-pixel plane holds an instance or record index across
+ *   frames.  Skins, morph sets (with their weights) and the light-source binding are kept.
+ *   Buffers: the rebuild's working buffers and two trees, two record tables, two triRef arrays and two instance-row arrays (a call writes the ones the context
+ *   does not use; they swap on success) are allocated by the first call after a host build, with 1/8 slack over the triangle and the instance count, and again by a
+ *   call whose counts exceed that capacity (reallocated = 1 in both cases; the old buffers are freed after the new tree is in place).  A call that fits allocates
+ *   and frees nothing unless the tree's depth crosses a multiple of 4 (the traversal stack), or the table outgrows the deform calls' per-instance job table.
+ *   Bus traffic: a call that makes no template moves numInstances * 112 + (numInstances + 1) * 4 + 24 bytes host -> device: the instance rows, the prefix words
+ *   (first record of every instance; bit 31: the matrix mirrors) and the 24-byte seed of the build's centre bounds.  The first call also uploads one word per prim
+ *   mesh, and a call that makes templates 80 bytes per triangle of the meshes concerned.
+ *   Failure: an allocation that fails (RT_ERR_OOM), a tree deeper than the traversal stack (RT_ERR_INVALID_ARG), a HIP error or a builder invariant (RT_ERR_HIP)
+ *   leave the previous instance table, tree, record table and refit state in place and usable.
+ *   Not done: rt_mgpu_* contexts and the row-tiled hosts (they upload the new scene); emissive instances added, removed or re-indexed; new prim meshes or
+ *   triangles; event-ordered instead of drained updates; SAH / spatial splits on the device (DESIGN.md §19's frame cost applies until a host build).
+ * rt_get_instances_stats: what the last rt_set_instances that succeeded did.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  uint32_t instances;        /* instances after the call */
+  uint32_t triangles;        /* leaf records = (instance, triangle) pairs after the call */
+  uint32_t added, removed;   /* new count - common prefix length with the old table; old count - that length (diagnostic only) */
+  uint32_t bytesUploaded;    /* bytes the call moved host -> device */
+  uint32_t reallocated;      /* 1: the device buffers were too small for the new counts (or absent: first call after a host build) and were allocated */
+  float    expandMs;         /* HIP-event time of the record-expansion kernels */
+  float    ms;               /* HIP-event time of the whole call on the main stream (expansion + device build) */
+} rt_instances_stats;        /* 32 B */
+int rt_set_instances(rt_ctx* ctx, uint32_t numInstances, const rt_instance* instances);
+int rt_get_instances_stats(rt_ctx* ctx, rt_instances_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
  * Object motion vectors (added within ABI 2.4, no version bump; the RT_OM builds of csrc/stages.hip).  rt_update_instances moves a surface, but the
  * reference's temporal lookup reprojects a hit with the camera's lastProjView and measures reprojDepth from the camera's lastPosition only, so on a moved surface
  * it lands on whatever was at that world position one frame earlier: the history is rejected (the prop stays noisy) or, on a large one-material object, taken
