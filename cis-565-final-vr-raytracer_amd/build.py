@@ -16,7 +16,29 @@ HOST_LIB = os.path.join(_HERE, "host", "librestir_host.so")
 # (measured) and cost the v_mov that packs their operands: without it every kernel is 3-4 % faster (scripts/ab_flags.sh)
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
              "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize", "-Wno-unused-result", "-x", "hip"]
-HIP_SRC = ["rt_api.cpp", "mgpu.cpp", "bvh8_builder.cpp", "stages.hip", "stages_sky.hip", "stages_cnt.hip", "stages_sky_cnt.hip", "stages_lat.hip", "stages_sky_lat.hip", "stages_om.hip", "stages_sky_om.hip", "stages_lat_om.hip", "stages_sky_lat_om.hip", "stages_vm.hip", "stages_sky_vm.hip", "stages_lat_vm.hip", "stages_sky_lat_vm.hip", "stages_rp.hip", "stages_sky_rp.hip", "stages_rp_cnt.hip", "stages_sky_rp_cnt.hip", "filters.hip", "post.hip", "microbench.hip", "reference.hip", "reference_sky.hip", "svgf.hip", "gi_spatial.hip", "taa.hip", "refit.hip", "accel_build.hip", "instances.hip", "deform.hip", "light_records.hip", "morph.hip", "vmotion.hip"]
+# translation units compiled once
+HIP_SRC = ["rt_api.cpp", "mgpu.cpp", "bvh8_builder.cpp", "filters.hip", "post.hip", "microbench.hip", "svgf.hip", "gi_spatial.hip", "taa.hip", "refit.hip", "accel_build.hip", "instances.hip", "deform.hip", "light_records.hip", "morph.hip", "vmotion.hip"]
+# THE table of the builds of the traced stages: csrc/stages.hip is compiled once per entry with -D<switch>=1 for each switch (what the switches do: the note at the
+# top of stages.hip).  The name is the build's namespace, which stages.hip pastes from the same switches, and one of RT_STAGE_BUILDS in csrc/stage_select.h, where
+# the rule that picks a build per launch lives (tests/test_stage_select_cpu.py holds the two lists together; DESIGN.md §28: adding a build).
+STAGE_BUILDS = {
+    "base": (), "sky": ("RT_SKY",), "base_cnt": ("RT_COUNT",), "sky_cnt": ("RT_SKY", "RT_COUNT"), "base_lat": ("RT_LAT",), "sky_lat": ("RT_SKY", "RT_LAT"),
+    "base_om": ("RT_OM",), "sky_om": ("RT_SKY", "RT_OM"), "base_lat_om": ("RT_LAT", "RT_OM"), "sky_lat_om": ("RT_SKY", "RT_LAT", "RT_OM"),
+    "base_vm": ("RT_VM",), "sky_vm": ("RT_SKY", "RT_VM"), "base_lat_vm": ("RT_LAT", "RT_VM"), "sky_lat_vm": ("RT_SKY", "RT_LAT", "RT_VM"),
+    "base_rp": ("RT_REPLAY",), "sky_rp": ("RT_SKY", "RT_REPLAY"), "base_rp_cnt": ("RT_COUNT", "RT_REPLAY"), "sky_rp_cnt": ("RT_SKY", "RT_COUNT", "RT_REPLAY"),
+}
+# ... and of the reference path tracer, csrc/reference.hip (namespaces ref / ref_sky)
+REFERENCE_BUILDS = {"reference": (), "reference_sky": ("RT_SKY",)}
+
+
+def hip_units():
+    """(source, object stem, switches) of every translation unit of csrc/librestir_hip.so; a base build's object carries no 'base' (stages.o, stages_lat.o)"""
+    units = [(src, os.path.splitext(src)[0], ()) for src in HIP_SRC]
+    units += [("stages.hip", ("stages_" + name).replace("_base", ""), sw) for name, sw in STAGE_BUILDS.items()]
+    units += [("reference.hip", name, sw) for name, sw in REFERENCE_BUILDS.items()]
+    return units
+
+
 HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-pthread"]
 HOST_SRC = ["scene.cpp", "scene_gen.cpp", "hdr_sampling.cpp", "gltf_loader.cpp", "jpeg_decoder.cpp", "png_writer.cpp", "host_capi.cpp"]
 
@@ -38,8 +60,8 @@ def _deps(d, exts):
 
 
 def build_hip(force=False, verbose=False, variant=None, extra_flags=()):
-    """hipcc --offload-arch=gfx950: one object per translation unit, compiled in parallel (the traced stage kernels exist in six
-    builds plus four with object motion vectors, four with per-vertex motion vectors and four direct stages with primary replay, see csrc/stages.hip; the filter chains and compose once, csrc/filters.hip), then one link into csrc/librestir_hip.so.  Objects go to csrc/_obj (git-ignored).
+    """hipcc --offload-arch=gfx950: one object per translation unit, compiled in parallel (csrc/stages.hip once per entry of STAGE_BUILDS, csrc/reference.hip
+    once per entry of REFERENCE_BUILDS, everything else once: hip_units), then one link into csrc/librestir_hip.so.  Objects go to csrc/_obj (git-ignored).
     `variant` + `extra_flags`: a measurement build (e.g. -DRT_WAVEPROF=1) into csrc/_ab/librestir_hip_<variant>.so, selected at run
     time with RESTIR_HIP_LIB; never the product library."""
     d = os.path.join(_HERE, "csrc")
@@ -51,12 +73,12 @@ def build_hip(force=False, verbose=False, variant=None, extra_flags=()):
         os.makedirs(objdir, exist_ok=True)
         flags = [f for f in HIP_FLAGS if f != "-shared"] + list(extra_flags) + os.environ.get("RESTIR_EXTRA_HIPFLAGS", "").split()   # experiments only
         jobs = []
-        for src in HIP_SRC:
-            obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
+        for src, stem, switches in hip_units():
+            obj = os.path.join(objdir, stem + ".o")
             # kernel translation units at -Os: the smaller loop bodies of the traced kernels measure 0.4 % (frames in flight) to 1.6 % (direct stage alone)
             # faster than at -O3, same bits (profiles/r02_tile_order_ab.txt); the host translation units (BVH builder, C-ABI) stay at -O3
             fl = [("-Os" if (f == "-O3" and src.endswith(".hip")) else f) for f in flags]
-            cmd = [hipcc] + fl + ["-c", os.path.join(d, src), "-o", obj]
+            cmd = [hipcc] + fl + ["-D%s=1" % sw for sw in switches] + ["-c", os.path.join(d, src), "-o", obj]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             jobs.append((cmd, obj, subprocess.Popen(cmd)))

@@ -133,4 +133,12 @@ struct DevVis {
   uint32_t record;          // 1: this launch records, 0: it replays
 };
 
+// What launchStage of a build of the traced stages (stages.h) takes beside the frame: each build reads the one pointer its kernels need, which is then not null
+// (the object-motion builds om, the per-vertex-motion builds vm, the primary-replay builds vis, the plain builds none).  Host side only, never a kernel argument.
+struct StageExtra {
+  const DevObjMotion* om;
+  const DevVtxMotion* vm;
+  const DevVis* vis;
+};
+
 }  // namespace rt

@@ -16,7 +16,7 @@ constexpr int REF_BAND_PIXELS = 1 << 20;
                              int rowBegin, int rowEnd);                                                                                      \
   }
 RT_DECL_REF(ref_base)   // HDR environment only (reference.hip)
-RT_DECL_REF(ref_sky)    // procedural sun & sky compiled in (reference_sky.hip)
+RT_DECL_REF(ref_sky)    // procedural sun & sky compiled in (reference.hip with RT_SKY)
 #undef RT_DECL_REF
 // mean of `component` (0 direct, 1 indirect, 2 direct + indirect) over n samples -> RGBA32F, a = 1: float(sum / n) (component 2: float((direct + indirect) / n)),
 // every operation in IEEE double, one rounding to float at the end; n == 0 gives (0, 0, 0, 1) and does not read `acc`

@@ -12,7 +12,7 @@
 //                   hits at depth > 1 with their MIS weight; every path multi-bounce, throughput starting at 1, the real albedo at vertex 1
 // No firefly clamp, no HDR->LDR encoding, no reservoirs.  Every shading function is Ctx's (shading.h); MISw is stage_common.h's.
 // Launch shape: one thread per pixel, an 8x8 tile per wave64, the whole traversal stack in LDS (the serial stages' stack); one sample per launch.
-// This file is compiled twice: as is, and through reference_sky.hip with RT_SKY = 1 (the stages' split, see stages.hip).
+// This file is compiled twice: as is, and with -DRT_SKY=1 (REFERENCE_BUILDS in build.py; the stages' split, see stages.hip).
 #ifndef RT_SKY
 #define RT_SKY 0
 #endif

@@ -279,10 +279,10 @@ static hipError_t joinInFlight(rt_ctx* c)
   return e;
 }
 
-typedef hipError_t (*StageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const rt_state&, const rt_scene_camera&, int, int, int, int);
-// What runs a launch: the filter chains and compose exist once (csrc/filters.hip); every other stage comes from one of the six builds of stages.hip.
+// What runs a launch: the filter chains and compose exist once (csrc/filters.hip); every other stage comes from one of the builds of stages.hip (STAGE_BUILDS in
+// build.py).  Which one is stage_select.h's rule; this file holds what the rule is fed with and the table from its answer to a function.
 // The traced kernels exist twice: the throughput build (one ray per lane, majority-vote rounds, 4-5 waves per
-// SIMD: full frames are bound by instruction issue) and the latency build (csrc/stages_lat.hip: eight lanes per ray, a workgroup of eight waves per tile:
+// SIMD: full frames are bound by instruction issue) and the latency build (RT_LAT: eight lanes per ray, a workgroup of eight waves per tile:
 // a row band of a multi-GPU frame or a small image is bound by the dependent steps of its slowest rays, and the latency build shortens the step).
 // RT_TRAVERSAL_AUTO decides by the number of 8x8 tiles of the launch; the thresholds are where the two builds measured equal on the benchmark scene
 // (profiles/r03_band_chunk_ab.txt, profiles/r03_lat_wide_ab.txt):
@@ -292,58 +292,22 @@ typedef hipError_t (*StageLauncher)(hipStream_t, const DevScene&, const DevFrame
 //     short chain with 2-4x the lane-cycles, which a co-running kernel would have used.
 // The counting build is a throughput build.  Bit-identical either way.  RESTIR_LAT_TILES / RESTIR_LAT_TILES_IND override both cases (experiments).
 static int envInt(const char* name) { const char* e = getenv(name); return e ? atoi(e) : -1; }
-static int latTilesDirect(bool shared)
+static rt::LatencyTiles latencyTiles(bool shared)
 {
   static const int alone = envInt("RESTIR_LAT_TILES"), sh = envInt("RESTIR_LAT_TILES_SHARED");
-  return shared ? (sh >= 0 ? sh : (alone >= 0 ? alone : 512)) : (alone >= 0 ? alone : 2000);
+  static const int aloneInd = envInt("RESTIR_LAT_TILES_IND"), shInd = envInt("RESTIR_LAT_TILES_IND_SHARED");
+  if(!shared) return {alone >= 0 ? alone : 2000, aloneInd >= 0 ? aloneInd : 2000};
+  return {sh >= 0 ? sh : (alone >= 0 ? alone : 512), shInd >= 0 ? shInd : (aloneInd >= 0 ? aloneInd : 640)};
 }
-static int latTilesIndirect(bool shared)
-{
-  static const int alone = envInt("RESTIR_LAT_TILES_IND"), sh = envInt("RESTIR_LAT_TILES_IND_SHARED");
-  return shared ? (sh >= 0 ? sh : (alone >= 0 ? alone : 640)) : (alone >= 0 ? alone : 2000);
-}
-static hipError_t filterLauncher(hipStream_t stream, const DevScene&, const DevFrame& F, const rt_state& st, const rt_scene_camera& cam, int stage, int level, int r0, int r1)
+typedef hipError_t (*StageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const rt::StageExtra&, const rt_state&, const rt_scene_camera&, int, int, int, int);
+static hipError_t filterLauncher(hipStream_t stream, const DevScene&, const DevFrame& F, const rt::StageExtra&, const rt_state& st, const rt_scene_camera& cam, int stage,
+                                 int level, int r0, int r1)
 { return rt::launchFilterStage(stream, F, st, cam, stage, level, r0, r1); }
-static bool latencyBuild(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
-{
-  bool lat = false;
-  if(!c->counting && (stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT)) {
-    if(c->traversal == RT_TRAVERSAL_LATENCY) lat = true;
-    else if(c->traversal == RT_TRAVERSAL_AUTO) {
-      const bool half = stage == RT_STAGE_INDIRECT;
-      const int gw = half ? st.size.x / 2 : st.size.x, gh = half ? st.size.y / 2 : st.size.y;
-      const int r1 = (rowEnd <= 0 || rowEnd > gh) ? gh : rowEnd, r0 = rowBegin < 0 ? 0 : rowBegin;
-      const long tiles = long((gw + 7) / 8) * long((std::max(0, r1 - r0) + 7) / 8);
-      lat = tiles <= (half ? latTilesIndirect(c->overlap >= 2) : latTilesDirect(c->overlap >= 2));
-    }
-  }
-  return lat;
-}
-static StageLauncher stageLauncher(const rt_ctx* c, const rt_state& st, int stage, int rowBegin, int rowEnd)
-{
-  if(stage == RT_STAGE_DENOISE_DIRECT || stage == RT_STAGE_DENOISE_INDIRECT || stage == RT_STAGE_COMPOSE) return filterLauncher;
-  const bool lat = latencyBuild(c, st, stage, rowBegin, rowEnd);
-  if(c->ds.sky) return lat ? rt::sky_lat::launchStage : (c->counting ? rt::sky_cnt::launchStage : rt::sky::launchStage);
-  return lat ? rt::base_lat::launchStage : (c->counting ? rt::base_cnt::launchStage : rt::base::launchStage);
-}
-
-// the direct and the indirect stage of a frame rendered with object motion vectors on: the same choice among the four RT_OM builds (no counting form)
-typedef hipError_t (*OmStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const DevObjMotion&, const rt_state&, const rt_scene_camera&, int, int, int, int);
-static OmStageLauncher omStageLauncher(const rt_ctx* c, const rt_state& st, int stage)
-{
-  const bool lat = latencyBuild(c, st, stage, 0, 0);
-  if(c->ds.sky) return lat ? rt::sky_lat_om::launchStage : rt::sky_om::launchStage;
-  return lat ? rt::base_lat_om::launchStage : rt::base_om::launchStage;
-}
-
-// ... and with per-vertex motion vectors on: the four RT_VM builds
-typedef hipError_t (*VmStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const DevVtxMotion&, const rt_state&, const rt_scene_camera&, int, int, int, int);
-static VmStageLauncher vmStageLauncher(const rt_ctx* c, const rt_state& st, int stage)
-{
-  const bool lat = latencyBuild(c, st, stage, 0, 0);
-  if(c->ds.sky) return lat ? rt::sky_lat_vm::launchStage : rt::sky_vm::launchStage;
-  return lat ? rt::base_lat_vm::launchStage : rt::base_vm::launchStage;
-}
+static const StageLauncher g_stageLaunchers[rt::STAGE_BUILD_COUNT] = {   // by rt::StageBuild
+#define RT_STAGE_LAUNCHER(ns) rt::ns::launchStage,
+  RT_STAGE_BUILDS(RT_STAGE_LAUNCHER)
+#undef RT_STAGE_LAUNCHER
+  filterLauncher};
 
 // ---- settled primary visibility (primary_replay.h) -------------------------------------------------------------------------------------------------
 // RESTIR_PRIMARY_REPLAY=0 switches it off, RESTIR_VIS_K sets the list length per pixel (1..64), RESTIR_VIS_REST_FRAMES the at-rest launches ahead of a recording (>= 2);
@@ -381,18 +345,31 @@ static rt::PrimaryReplayAction primaryReplayLaunch(rt_ctx* c, const rt_state& st
   V.record = a == rt::PRIMARY_REPLAY_RECORD ? 1u : 0u;
   return a;
 }
-typedef hipError_t (*RpStageLauncher)(hipStream_t, const DevScene&, const DevFrame&, const rt::DevVis&, const rt_state&, const rt_scene_camera&, int, int, int, int);
-static RpStageLauncher rpStageLauncher(const rt_ctx* c)
-{
-  if(c->ds.sky) return c->counting ? rt::sky_rp_cnt::launchStage : rt::sky_rp::launchStage;
-  return c->counting ? rt::base_rp_cnt::launchStage : rt::base_rp::launchStage;
-}
 // after a RECORD / REPLAY launch was issued (or failed to be)
 static void primaryReplayIssued(rt_ctx* c, rt::PrimaryReplayAction a, bool ok)
 {
   if(!ok) { dropPrimaryReplay(c); return; }
   if(a == rt::PRIMARY_REPLAY_RECORD) c->replayRecorded++;
   if(a == rt::PRIMARY_REPLAY_REPLAY) c->replayReplayed++;
+}
+
+// One launch of a stage on `strm`, for rt_render_frame and rt_run_stage alike.  A direct launch that spawns primary rays (level 2 is the rayless half) passes through
+// the replay rule, eligible when it would be a throughput launch of a context without TAA and without a motion-vector mode; stage_select.h names the build; a
+// RECORD / REPLAY launch reports back to the rule.  `motion`: the motion-vector form of the frame's traced stages, whose argument `X` then holds.
+static hipError_t launchStageOn(rt_ctx* c, hipStream_t strm, const DevFrame& F, rt::StageExtra X, rt::StageMotion motion, const rt_state& st, const rt_scene_camera& cam,
+                                int stage, int level, int rowBegin, int rowEnd)
+{
+  const bool lat = rt::latencyBuild(c->counting, c->traversal, stage, st.size.x, st.size.y, rowBegin, rowEnd, latencyTiles(c->overlap >= 2));
+  rt::DevVis V{};
+  rt::PrimaryReplayAction act = rt::PRIMARY_REPLAY_NORMAL;
+  if(stage == RT_STAGE_DIRECT && level != 2) {
+    const bool fullFrame = rowBegin == 0 && (rowEnd <= 0 || rowEnd >= c->H);
+    act = primaryReplayLaunch(c, st, cam, fullFrame, c->taa.mode == RT_TAA_OFF && c->objMotion == RT_OBJECT_MOTION_OFF && !lat, V);
+  }
+  X.vis = &V;
+  const hipError_t e = g_stageLaunchers[rt::stageBuild(c->ds.sky, c->counting, lat, stage, motion, act)](strm, c->ds, F, X, st, cam, stage, level, rowBegin, rowEnd);
+  if(act != rt::PRIMARY_REPLAY_NORMAL) primaryReplayIssued(c, act, e == hipSuccess);
+  return e;
 }
 
 // ---- host side of rt_build_accel, cached by scene content (buildHostAccel below) ---------------------------------------------------------------------
@@ -1345,17 +1322,8 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
   DevFrame F = makeFrame(c, frames);
   if(stage == RT_STAGE_INDIRECT) F.histMiss = c->scratch.qcount + 251;  // per-stage-kind flag (rt_history_miss_stage)
   // (stage kinds share no scratch: a caller may spread them over several streams, tiled.PipelinedTiledFrame does)
-  hipError_t e;
-  rt::DevVis V{};
-  rt::PrimaryReplayAction act = rt::PRIMARY_REPLAY_NORMAL;
-  if(stage == RT_STAGE_DIRECT && level != 2) {   // (level 2 is the rayless half: it spawns no primary ray)
-    const bool fullFrame = rowBegin == 0 && (rowEnd <= 0 || rowEnd >= c->H);
-    act = primaryReplayLaunch(c, *st, c->cam, fullFrame, c->objMotion == RT_OBJECT_MOTION_OFF && !latencyBuild(c, *st, stage, rowBegin, rowEnd), V);
-  }
-  if(act != rt::PRIMARY_REPLAY_NORMAL) {
-    e = rpStageLauncher(c)(c->stream, c->ds, F, V, *st, c->cam, stage, level, rowBegin, rowEnd);
-    primaryReplayIssued(c, act, e == hipSuccess);
-  } else e = stageLauncher(c, *st, stage, rowBegin, rowEnd)(c->stream, c->ds, F, *st, c->cam, stage, level, rowBegin, rowEnd);
+  // (never a motion-vector build, whatever rt_set_object_motion says: the motion state belongs to rt_render_frame's frames)
+  const hipError_t e = launchStageOn(c, c->stream, F, rt::StageExtra{}, rt::STAGE_MOTION_NONE, *st, c->cam, stage, level, rowBegin, rowEnd);
   if(e == hipErrorInvalidValue) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: level out of range for this stage (RT_STAGE_DIRECT levels 1 / 2 exist in the spatial modes only)");
   if(e == hipErrorInvalidConfiguration) return fail(c, RT_ERR_HIP, "rt_run_stage: the traversal-stack overflow area is missing or too small for this launch (internal sizing error)");
   RT_HIP(c, e);
@@ -1494,10 +1462,8 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     return RT_OK;
   };
   auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    const bool traced = stage == RT_STAGE_DIRECT || stage == RT_STAGE_INDIRECT;
-    hipError_t e = (om && traced) ? omStageLauncher(c, *st, stage)(strm, c->ds, F, OM, *st, cam, stage, level, 0, 0)
-                 : (vm && traced) ? vmStageLauncher(c, *st, stage)(strm, c->ds, F, VM, *st, cam, stage, level, 0, 0)
-                                  : stageLauncher(c, *st, stage, 0, 0)(strm, c->ds, F, *st, cam, stage, level, 0, 0);
+    const hipError_t e = launchStageOn(c, strm, F, rt::StageExtra{&OM, &VM, nullptr}, om ? rt::STAGE_MOTION_OBJECT : (vm ? rt::STAGE_MOTION_VERTEX : rt::STAGE_MOTION_NONE),
+                                       *st, cam, stage, level, 0, 0);
     if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
     return record(strm, stage);
   };
@@ -1509,17 +1475,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   auto direct = [&](hipStream_t strm) -> int {
     if(om && omMotion) RT_HIP(c, hipMemcpyAsync(c->omTable, c->omHost.data(), c->omHost.size() * sizeof(OmCamera), hipMemcpyHostToDevice, strm));
     if(vm && vmMotion) RT_HIP(c, hipMemcpyAsync(c->vmTable, c->vmHost.data(), c->vmHost.size() * sizeof(VmRow), hipMemcpyHostToDevice, strm));
-    // settled primary visibility: a frame of the throughput build without TAA and without a motion-vector mode passes through the rule (primary_replay.h)
-    rt::DevVis V{};
-    const rt::PrimaryReplayAction act = primaryReplayLaunch(c, *st, cam, true, c->taa.mode == RT_TAA_OFF && c->objMotion == RT_OBJECT_MOTION_OFF && !om && !vm &&
-                                                            !latencyBuild(c, *st, RT_STAGE_DIRECT, 0, 0), V);
-    int r;
-    if(act != rt::PRIMARY_REPLAY_NORMAL) {
-      const hipError_t e = rpStageLauncher(c)(strm, c->ds, F, V, *st, cam, RT_STAGE_DIRECT, 0, 0, 0);
-      primaryReplayIssued(c, act, e == hipSuccess);
-      if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-      r = record(strm, RT_STAGE_DIRECT);
-    } else r = run(strm, RT_STAGE_DIRECT, 0);
+    const int r = run(strm, RT_STAGE_DIRECT, 0);   // (through the replay rule: launchStageOn)
     if(r == RT_OK) {
       if(om) c->omInstValid = true;
       if(vm) c->omInstValid = c->vmDeltaValid = true;

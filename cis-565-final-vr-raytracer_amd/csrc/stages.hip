@@ -8,10 +8,10 @@
 // Launch shape: one wave64 per 8x8 pixel tile (= the reference's 8x8 workgroups, host_device.h:31-38), 1-D grid with
 // an XCD-aware tile order: consecutive workgroup ids land on different XCDs (observed b % 8), so XCD x gets the x-th
 // contiguous band of tile rows and its private 4 MiB L2 sees one compact screen region + the BVH subtrees under it.
-// This file is compiled six times: as is, and through stages_{sky,cnt,sky_cnt,lat,sky_lat}.hip with RT_SKY / RT_COUNT / RT_LAT set; what those switches do not reach is in filters.hip.
-// Four more builds, stages_{om,sky_om,lat_om,sky_lat_om}.hip, set RT_OM (below) for contexts with object motion vectors on, and four,
-// stages_{vm,sky_vm,lat_vm,sky_lat_vm}.hip, set RT_VM for contexts with per-vertex motion vectors on.  Four thin ones, stages_{rp,sky_rp,rp_cnt,sky_rp_cnt}.hip, set
-// RT_REPLAY (below): the direct stage of a camera at rest.
+// This file is compiled once per entry of STAGE_BUILDS in build.py (-D<switch>=1 per switch of the entry; no stub files): the table is the one statement of which
+// builds exist, stage_select.h holds the same names and the rule that picks one per launch, DESIGN.md §28 says how to add one.  The switches (below): RT_SKY / RT_COUNT /
+// RT_LAT for the plain builds, RT_OM for contexts with object motion vectors on, RT_VM for per-vertex motion vectors, RT_REPLAY for the direct stage of a camera at
+// rest; what the switches do not reach is in filters.hip.
 //   RT_SKY = 1    procedural sun & sky code paths compiled in.  Keeping sun_and_sky() out of the default kernels saves 13 VGPRs
 //                 in k_direct_stage — the procedural sky is the rarely used mode (default in_use = 0, sample_example.hpp:202).
 //   RT_COUNT = 1  traversal / shading counters (rt_set_counting) are flushed at the end of the traced kernels.  Without the
@@ -42,8 +42,8 @@
 #endif
 //   RT_REPLAY = 1 settled primary visibility: k_direct_stage alone, taking a DevVis.  A RECORD launch traces the primary ray as every build does and
 //                 then once more, culling by deterministic accepts only, to store what a camera at rest needs to know of it; REPLAY launches re-test the stored
-//                 records with the frame's seed and run no traversal loop for the primary ray.  Base and sky, each with its counting form (stages_{rp,sky_rp,
-//                 rp_cnt,sky_rp_cnt}.hip); no latency or object-motion form.  Every other stage and the rayless half of the direct stage forward to the plain build.
+//                 records with the frame's seed and run no traversal loop for the primary ray.  Base and sky, each with its counting form; no latency or
+//                 object-motion form.  Every other stage and the rayless half of the direct stage forward to the plain build.
 #ifndef RT_REPLAY
 #define RT_REPLAY 0
 #endif
@@ -56,6 +56,7 @@
 #if RT_OM && RT_VM
 #error "RT_OM and RT_VM are two builds"
 #endif
+// RT_OM_PARAM / RT_OM_ARG: the motion-vector argument of the device functions between the kernels and the shading, RT_OM_KPARAM: of the kernels
 #if RT_OM
 #define RT_OM_PARAM , const DevObjMotion& OM
 #define RT_OM_KPARAM , DevObjMotion OM
@@ -72,56 +73,37 @@
 #if RT_LAT && RT_COUNT
 #error "the counting build exists for the throughput kernels only"
 #endif
-#if RT_REPLAY && RT_SKY && RT_COUNT
-#define RT_VARIANT sky_rp_cnt
-#define RT_FORWARD sky_cnt
-#elif RT_REPLAY && RT_SKY
-#define RT_VARIANT sky_rp
-#define RT_FORWARD sky
-#elif RT_REPLAY && RT_COUNT
-#define RT_VARIANT base_rp_cnt
-#define RT_FORWARD base_cnt
-#elif RT_REPLAY
-#define RT_VARIANT base_rp
-#define RT_FORWARD base
-#elif RT_VM && RT_LAT && RT_SKY
-#define RT_VARIANT sky_lat_vm
-#define RT_FORWARD sky
-#elif RT_VM && RT_LAT
-#define RT_VARIANT base_lat_vm
-#define RT_FORWARD base
-#elif RT_VM && RT_SKY
-#define RT_VARIANT sky_vm
-#define RT_FORWARD sky
-#elif RT_VM
-#define RT_VARIANT base_vm
-#define RT_FORWARD base
-#elif RT_OM && RT_LAT && RT_SKY
-#define RT_VARIANT sky_lat_om
-#define RT_FORWARD sky
-#elif RT_OM && RT_LAT
-#define RT_VARIANT base_lat_om
-#define RT_FORWARD base
-#elif RT_OM && RT_SKY
-#define RT_VARIANT sky_om
-#define RT_FORWARD sky
-#elif RT_OM
-#define RT_VARIANT base_om
-#define RT_FORWARD base
-#elif RT_LAT && RT_SKY
-#define RT_VARIANT sky_lat
-#define RT_FORWARD sky
-#elif RT_LAT
-#define RT_VARIANT base_lat
-#define RT_FORWARD base
-#elif RT_SKY && RT_COUNT
-#define RT_VARIANT sky_cnt
-#elif RT_SKY
-#define RT_VARIANT sky
-#elif RT_COUNT
-#define RT_VARIANT base_cnt
+// The build's namespace, pasted from the switches: environment, then _lat, then _om / _vm / _rp, then _cnt (the names of RT_STAGE_BUILDS, stage_select.h).
+// RT_FORWARD, for the builds that hold a part of the kernels only: the plain build of the same environment and counting, which launches the rest.
+#if RT_SKY
+#define RT_NS_ENV sky
 #else
-#define RT_VARIANT base
+#define RT_NS_ENV base
+#endif
+#if RT_LAT
+#define RT_NS_LAT _lat
+#else
+#define RT_NS_LAT
+#endif
+#if RT_OM
+#define RT_NS_FORM _om
+#elif RT_VM
+#define RT_NS_FORM _vm
+#elif RT_REPLAY
+#define RT_NS_FORM _rp
+#else
+#define RT_NS_FORM
+#endif
+#if RT_COUNT
+#define RT_NS_CNT _cnt
+#else
+#define RT_NS_CNT
+#endif
+#define RT_NS_PASTE_(a, b, c, d) a##b##c##d
+#define RT_NS_PASTE(a, b, c, d) RT_NS_PASTE_(a, b, c, d)
+#define RT_VARIANT RT_NS_PASTE(RT_NS_ENV, RT_NS_LAT, RT_NS_FORM, RT_NS_CNT)
+#if RT_LAT || RT_OM || RT_VM || RT_REPLAY
+#define RT_FORWARD RT_NS_PASTE(RT_NS_ENV, , , RT_NS_CNT)
 #endif
 #include "stage_common.h"
 #include <algorithm>
@@ -1093,37 +1075,18 @@ __global__ __launch_bounds__(64, RT_INDIRECT_LB) void k_indirect_stage(DevScene 
 // ------------------------------------------------------------------------------------------------------------
 // host-side launch (one entry of Renderer::run's dispatch list, renderer.cpp:163-205)
 // ------------------------------------------------------------------------------------------------------------
-#if RT_REPLAY
-// RT_STAGE_DIRECT only, sized as the plain build sizes it; the rayless half (spatial modes) is the plain build's kernel
-hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F, const DevVis& V, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
+// One signature for every build (stages.h); of `X` a build reads the one pointer that its kernels take by value: RT_OM om, RT_VM vm, RT_REPLAY vis.
+hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F, const StageExtra& X, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
                        int rowBegin, int rowEnd)
 {
-  if(stage != RT_STAGE_DIRECT) return hipErrorInvalidValue;
-  DevScene S = Sin;
-  S.stackEntries = F.stackLds > 0 ? std::min(F.stackLds, S.stackTotal) : S.stackTotal;
-  const bool needOvf = S.stackTotal > S.stackEntries;
-  const int gw = st.size.x, gh = st.size.y;
-  if(rowEnd <= 0 || rowEnd > gh) rowEnd = gh;
-  if(rowBegin < 0) rowBegin = 0;
-  if(rowBegin >= rowEnd || gw <= 0) return hipSuccess;
-  const int tilesX = (gw + 7) / 8, tilesY = (rowEnd - rowBegin + 7) / 8;
-  const dim3 grid(tileGrid(tilesX, tilesY)), block(64);
-  const size_t lds = size_t(S.stackEntries) * 64 * sizeof(uint2);
-  const bool spatial = st.ReSTIRState == RT_RESTIR_SPATIAL || st.ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
-  if(level < 0 || level > 2 || (level != 0 && !spatial)) return hipErrorInvalidValue;
-  if(!V.det || !V.count || !V.list || rowBegin != 0 || rowEnd != gh) return hipErrorInvalidValue;   // full frames only: the planes are indexed by pixel
-  if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;
-  if(level != 2) {
-    if(V.record) hipLaunchKernelGGL(k_direct_stage<true>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
-    else hipLaunchKernelGGL(k_direct_stage<false>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
-  }
-  if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
-  return hipGetLastError();
-}
-#else
-hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& F RT_OM_PARAM, const rt_state& st, const rt_scene_camera& cam, int stage, int level,
-                       int rowBegin, int rowEnd)
-{
+#if RT_OM
+  const DevObjMotion& OM = *X.om;
+#elif RT_VM
+  const DevVtxMotion& OM = *X.vm;
+#elif RT_REPLAY
+  const DevVis& V = *X.vis;
+  if(stage != RT_STAGE_DIRECT) return hipErrorInvalidValue;   // the build holds k_direct_stage alone
+#endif
   DevScene S = Sin;
 #if RT_LAT
   S.stackEntries = S.stackTotal + (S.gangMax > 0 ? GANG_EXTRA : 0);   // one column per RAY (8 per wave): the whole stack fits in LDS (+ the room gang mode expands into)
@@ -1152,17 +1115,25 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
       if(level < 0 || level > 2 || (level != 0 && !spatial)) return hipErrorInvalidValue;
 #if RT_LAT
       if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, dim3(64 * nWaves), wideLdsBytes(S.stackEntries, nWaves), stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY);
-      if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
+#elif RT_REPLAY
+      if(!V.det || !V.count || !V.list || rowBegin != 0 || rowEnd != gh) return hipErrorInvalidValue;   // full frames only: the planes are indexed by pixel
+      if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;
+      if(level != 2) {
+        if(V.record) hipLaunchKernelGGL(k_direct_stage<true>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+        else hipLaunchKernelGGL(k_direct_stage<false>, grid, block, lds, stream, S, F, V, st, cam, rowBegin, rowEnd, tilesX, tilesY);
+      }
 #else
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
       if(level != 2) hipLaunchKernelGGL(k_direct_stage, grid, block, lds, stream, S, F RT_OM_ARG, st, cam, rowBegin, rowEnd, tilesX, tilesY);
-#if RT_OM || RT_VM
-      if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, st, cam, stage, 2, rowBegin, rowEnd);
+#endif
+      // the rayless half (spatial modes): the plain build's kernel
+#ifdef RT_FORWARD
+      if(level != 1 && spatial) return rt::RT_FORWARD::launchStage(stream, Sin, F, X, st, cam, stage, 2, rowBegin, rowEnd);
 #else
       if(level != 1 && spatial) hipLaunchKernelGGL(k_direct_spatial, grid, block, 0, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
 #endif
-#endif
       break;
+#if !RT_REPLAY
     case RT_STAGE_INDIRECT: {
       // per-XCD tile lists: capacity = the tiles one XCD can own under the striped mapping
       const int cap = int(tileGrid(tilesX, tilesY) / 8);
@@ -1188,7 +1159,8 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
 #endif
       break;
     }
-#if !RT_LAT && !RT_OM && !RT_VM   // the two stages the reference compiles but does not dispatch: throughput builds only
+#endif
+#if !RT_LAT && !RT_OM && !RT_VM && !RT_REPLAY   // the two stages the reference compiles but does not dispatch: throughput builds only
     case RT_STAGE_DIRECT_GEN:
       if(needOvf && grid.x * 64u > S.stackOvfThreads) return hipErrorInvalidConfiguration;   // overflow area missing / too small: an internal sizing error, not the caller's
       hipLaunchKernelGGL(k_direct_gen, grid, block, lds, stream, S, F, st, cam, rowBegin, rowEnd, tilesX, tilesY);
@@ -1199,7 +1171,6 @@ hipError_t launchStage(hipStream_t stream, const DevScene& Sin, const DevFrame& 
   }
   return hipGetLastError();
 }
-#endif  // RT_REPLAY
 
 }  // namespace RT_VARIANT
 }  // namespace rt

@@ -21,7 +21,7 @@ struct RayHit {
   float u, v;
 };
 
-// RT_LAT (compile-time): the latency build of the traced kernels, eight lanes per ray throughout (below; csrc/stages_lat.hip)
+// RT_LAT (compile-time): the latency build of the traced kernels, eight lanes per ray throughout (below; the builds base_lat / sky_lat of stages.hip)
 #ifndef RT_LAT
 #define RT_LAT 0
 #endif
@@ -754,7 +754,7 @@ RT_DEV void tracePoolTiles(const DevScene& S, float4* pool, uint32_t have /* bit
   waveLdsSync();
 }
 
-// ---- latency-mode traversal: eight lanes per ray (RT_LAT = 1: the traced kernels of SMALL launches, csrc/stages_lat.hip) ------------------------------
+// ---- latency-mode traversal: eight lanes per ray (RT_LAT = 1: the traced kernels of SMALL launches, the _lat builds of stages.hip) ------------------------------
 // A row band of a multi-GPU frame (or a small image) puts about one wave on a SIMD, and its launch takes what its slowest wave takes.  Measured on the
 // horizon bands of the benchmark frame (profiles/r03a_wave_profile_baseline.txt, profiles/r03_lat_narrow_band_ab.txt): a wave64 instruction costs its
 // wave ~4 cycles however empty the SIMD is, so a ray's chain is (node steps + triangle steps) x (memory latency + the step's OWN instruction time), and

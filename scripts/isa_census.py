@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Instruction census of the device code of one stages translation unit (round 6: typed address spaces on the traversal path).
 
-  python scripts/isa_census.py [stages.hip|stages_lat.hip|filters.hip|...] [extra hipcc flags...]
+  python scripts/isa_census.py [stages.hip|filters.hip|...] [extra hipcc flags: stages.hip -DRT_LAT=1 is the build base_lat, ...]
 
 Compiles the unit device-only to gfx950 assembly with the product flags (restir_amd/build.py) and prints, per kernel: flat_ / global_ / ds_ / scratch_ / buffer_
 loads and stores, s_waitcnt that wait on BOTH counters (vmcnt and lgkmcnt) at once, VGPRs, spills, scratch bytes.  Runs on the CPU box (hipcc cross-compiles)."""

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Scratch accesses inside the loops of the two traced kernels (the companion of scripts/isa_census.py: "no scratch access inside a traversal loop").
 
-  python scripts/isa_loops.py [stages.hip|stages_sky.hip|...] [extra hipcc flags...]
+  python scripts/isa_loops.py [stages.hip] [extra hipcc flags: stages.hip -DRT_SKY=1 is the build sky, ...]
 
 Compiles the unit as isa_census.py does and lists, for k_direct_stage and k_indirect_stage, every loop (a backward branch to a .LBB label) of more than 100
 instructions: its length, its 16-byte loads (a traversal loop fetches nodes and triangle records: 5 or more), its DPP moves (the eight-lanes-per-ray tail) and the

@@ -291,8 +291,8 @@ def test_large_launch_indirect_bit_exact():
     assert np.isfinite(img).all() and img.max() > 0.0
 
 
-# ---- which code runs a stage: csrc/rt_api.cpp stageLauncher picks one of the six builds of csrc/stages.hip for the traced stages and csrc/filters.hip for the
-# filter chains and compose, whatever the selection is
+# ---- which code runs a stage: csrc/stage_select.h picks one of the builds of csrc/stages.hip (STAGE_BUILDS in build.py; the six plain ones here) for the traced
+# stages and csrc/filters.hip for the filter chains and compose, whatever the selection is
 SELECTIONS = [(sky, mode) for sky in (False, True) for mode in ("throughput", "counting", "latency")]
 SELECT_SIZES = [(101, 51), (1, 1)]   # ragged tiles + an odd 50 x 25 half resolution (whose last row is a band of its own below); the smallest size test_gpu_optin_shapes.py renders
 SELECT_FRAMES = 2

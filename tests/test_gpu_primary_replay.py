@@ -154,9 +154,10 @@ def test_twelve_frames_equal_the_oracle_and_record_and_replay_where_expected(bui
     assert stats["pixelsListed"] + stats["pixelsOverflow"] > 0     # the street has alpha-tested cards in front of opaque surfaces: R is more than {d*} somewhere
 
 
-@pytest.mark.parametrize("size", [(8, 8), (9, 1)], ids=["8x8", "9x1"])
-def test_one_tile_and_one_row(size):
-    problems, stats = run_sequence("base", *size, offsets=[0] * 5, expect=REST5)
+# (the third case is the one that reaches the build sky_rp_cnt: sun & sky and counting on, recorded and replayed)
+@pytest.mark.parametrize("size,build,counting", [((8, 8), "base", False), ((9, 1), "base", False), ((8, 8), "sky", True)], ids=["8x8", "9x1", "8x8-sky-counting"])
+def test_one_tile_and_one_row(size, build, counting):
+    problems, stats = run_sequence(build, *size, offsets=[0] * 5, expect=REST5, setup=(lambda r: r.set_counting(True)) if counting else None)
     print(size, stats)
     assert problems == [] and stats["state"] == 1
     assert stats["pixelsSettled"] + stats["pixelsListed"] + stats["pixelsOverflow"] == size[0] * size[1]

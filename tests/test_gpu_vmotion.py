@@ -65,9 +65,10 @@ def test_with_the_camera_step(tmp):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("which", ["svgf", "gi_spatial", "sky"])
+@pytest.mark.parametrize("which", ["svgf", "gi_spatial", "sky", "sky-throughput"])
 def test_with_an_opt_in_pass_or_the_sky_build(tmp, which):
     kw = {}
+    W, H, frames = 33, 17, 5
     if which == "svgf":
         den = abi.Denoiser()
         den.mode = abi.DENOISER_SVGF
@@ -78,8 +79,11 @@ def test_with_an_opt_in_pass_or_the_sky_build(tmp, which):
         kw["gis"] = gis
     else:
         kw["sky"] = abi.SunAndSky(in_use=1)
-    bad, flagged, moved_px, _ = run(tmp, "cornell", 33, 17, frames=5, **kw)      # (with SVGF on, diff() compares the histories)
-    assert flagged == FLAGGED[:5] and moved_px > 0
+        if which == "sky-throughput":     # an image this small takes the build sky_lat_vm unless told otherwise: this case is the one that reaches sky_vm
+            kw["traversal"] = abi.TRAVERSAL_THROUGHPUT
+            W, H, frames = 16, 8, 2
+    bad, flagged, moved_px, _ = run(tmp, "cornell", W, H, frames=frames, **kw)      # (with SVGF on, diff() compares the histories)
+    assert flagged == FLAGGED[:frames] and moved_px > 0
     assert not bad, bad
 
 
