@@ -126,6 +126,19 @@ class Taa(C.Structure):  # rt_taa, 32 B; defaults = the library's
         d = dict(mode=TAA_OFF, jitterPhases=8, alpha=0.1, clipGamma=1.0)
         d.update(kw)
         super().__init__(**d)
+# rt_set_upscale (include/rt_abi.h "Temporal upsampling"); rt_upscale_readback ids
+UPSCALE_OFF, UPSCALE_TEMPORAL = range(2)
+UPSCALE_DIRECT, UPSCALE_INDIRECT, UPSCALE_HISTORY_LENGTH, UPSCALE_LDR = range(4)
+
+
+class Upscale(C.Structure):  # rt_upscale, 32 B; defaults = the library's
+    _fields_ = [("mode", C.c_int32), ("outWidth", C.c_int32), ("outHeight", C.c_int32), ("jitterPhases", C.c_int32), ("alpha", C.c_float),
+                ("clipGamma", C.c_float), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, **kw):
+        d = dict(mode=UPSCALE_OFF, outWidth=0, outHeight=0, jitterPhases=16, alpha=0.1, clipGamma=1.0)
+        d.update(kw)
+        super().__init__(**d)
 # rt_stage_id
 (STAGE_DIRECT, STAGE_INDIRECT, STAGE_DENOISE_DIRECT, STAGE_DENOISE_INDIRECT, STAGE_COMPOSE, STAGE_DIRECT_GEN, STAGE_DIRECT_REUSE) = range(7)
 # rt_restir_state

@@ -25,6 +25,7 @@
 #include "svgf.h"
 #include "gi_spatial.h"
 #include "taa.h"
+#include "upscale.h"
 #include "refit.h"
 #include "accel_build.h"
 #include "instances.h"
@@ -130,6 +131,18 @@ struct rt_ctx {
   int taaLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
   bool taaHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame taaFrame[parity] (rt_tonemap)
   int taaFrame[2] = {0, 0};
+  // rt_set_upscale (csrc/upscale.hip).  History at the output size: [frame parity][direct, indirect, n], allocated by the first resolved frame
+  // together with the output-size RGBA8 target and the tonemap's scratch (row sums, means, mip pyramids), freed by rt_resize / rt_destroy / an rt_set_upscale
+  // that changes the output size.  Frame f reads parity (f + 1) & 1 and writes f & 1.  The fields mirror TAA's.
+  rt_upscale ups{RT_UPSCALE_OFF, 0, 0, 16, 0.1f, 1.0f, {0, 0}};
+  void* upsHist[2][3] = {};
+  int upsW = 0, upsH = 0;    // the output size upsHist was allocated for
+  void* upsLdr = nullptr; double* upsRowSums = nullptr; float* upsMean = nullptr; float4* upsMipD = nullptr; float4* upsMipI = nullptr;
+  bool upsLdrWritten = false;
+  bool upsValid = false;     // the history of parity upsLast may be read by the next frame (host-side, consumed when a frame is enqueued)
+  int upsLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
+  bool upsHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame upsFrame[parity] (rt_upscale_tonemap)
+  int upsFrame[2] = {0, 0};
   // rt_update_instances (csrc/refit.hip).  Made by the first update after a build from the device tree (ensureRefitState) and dropped with the tree: the record -> node
   // map, the contiguous node range of every level, per instance its largest |world coordinate| (the pad is a reduction over instances) and its handedness.
   // The device arrays live in accelAllocs.
@@ -354,7 +367,7 @@ static void primaryReplayIssued(rt_ctx* c, rt::PrimaryReplayAction a, bool ok)
 }
 
 // One launch of a stage on `strm`, for rt_render_frame and rt_run_stage alike.  A direct launch that spawns primary rays (level 2 is the rayless half) passes through
-// the replay rule, eligible when it would be a throughput launch of a context without TAA and without a motion-vector mode; stage_select.h names the build; a
+// the replay rule, eligible when it would be a throughput launch of a context without TAA, without temporal upsampling and without a motion-vector mode; stage_select.h names the build; a
 // RECORD / REPLAY launch reports back to the rule.  `motion`: the motion-vector form of the frame's traced stages, whose argument `X` then holds.
 static hipError_t launchStageOn(rt_ctx* c, hipStream_t strm, const DevFrame& F, rt::StageExtra X, rt::StageMotion motion, const rt_state& st, const rt_scene_camera& cam,
                                 int stage, int level, int rowBegin, int rowEnd)
@@ -364,7 +377,7 @@ static hipError_t launchStageOn(rt_ctx* c, hipStream_t strm, const DevFrame& F, 
   rt::PrimaryReplayAction act = rt::PRIMARY_REPLAY_NORMAL;
   if(stage == RT_STAGE_DIRECT && level != 2) {
     const bool fullFrame = rowBegin == 0 && (rowEnd <= 0 || rowEnd >= c->H);
-    act = primaryReplayLaunch(c, st, cam, fullFrame, c->taa.mode == RT_TAA_OFF && c->objMotion == RT_OBJECT_MOTION_OFF && !lat, V);
+    act = primaryReplayLaunch(c, st, cam, fullFrame, c->taa.mode == RT_TAA_OFF && c->ups.mode == RT_UPSCALE_OFF && c->objMotion == RT_OBJECT_MOTION_OFF && !lat, V);
   }
   X.vis = &V;
   const hipError_t e = g_stageLaunchers[rt::stageBuild(c->ds.sky, c->counting, lat, stage, motion, act)](strm, c->ds, F, X, st, cam, stage, level, rowBegin, rowEnd);
@@ -500,6 +513,15 @@ static void freeTaaHistory(rt_ctx* c)
 {
   for(auto& par : c->taaHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
   c->taaValid = false; c->taaLast = -1; c->taaHeld[0] = c->taaHeld[1] = false;
+}
+// the upsampling history and what rt_upscale_tonemap needs at the output size (the caller has drained the context)
+static void freeUpscaleHistory(rt_ctx* c)
+{
+  for(auto& par : c->upsHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
+  for(void* p : {c->upsLdr, static_cast<void*>(c->upsRowSums), static_cast<void*>(c->upsMean), static_cast<void*>(c->upsMipD), static_cast<void*>(c->upsMipI)}) if(p) (void)hipFree(p);
+  c->upsLdr = nullptr; c->upsRowSums = nullptr; c->upsMean = nullptr; c->upsMipD = c->upsMipI = nullptr;
+  c->upsW = c->upsH = 0; c->upsLdrWritten = false;
+  c->upsValid = false; c->upsLast = -1; c->upsHeld[0] = c->upsHeld[1] = false;
 }
 
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
@@ -653,6 +675,7 @@ int rt_destroy(rt_ctx* c)
   freeSvgfHistory(c);
   freeGiSpatial(c);
   freeTaaHistory(c);
+  freeUpscaleHistory(c);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
   if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
@@ -751,6 +774,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->refN = 0;   // a new scene: the reference sums start again
   c->svgfValid = false;
   c->taaValid = false;
+  c->upsValid = false;
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // object motion: nothing of the new scene has moved
   if(c->vmPlane) { (void)hipFree(c->vmPlane); c->vmPlane = nullptr; }   // ... or has been deformed; the plane is made again for the new vertex array below
   c->vmDeformed.clear(); c->vmPending = false;
@@ -962,6 +986,7 @@ int rt_build_accel(rt_ctx* c)
   c->refN = 0;
   c->svgfValid = false;
   c->taaValid = false;
+  c->upsValid = false;
   // Host products (BVH8, alpha records, opacity micro-maps): built once per distinct scene in this process and shared by every context that uploads
   // the same scene — the N ranks of an rt_mgpu context, or an application's contexts on several devices (1.4-1.6 s per build at 2.8 M triangles).
   std::shared_ptr<const HostAccel> ha;
@@ -1032,6 +1057,7 @@ int rt_resize(rt_ctx* c, int w, int h)
   freeSvgfHistory(c);
   freeGiSpatial(c);
   freeTaaHistory(c);
+  freeUpscaleHistory(c);
   freeObjectMotion(c);
   freeVis(c);
   const size_t n = size_t(w) * h, nh = size_t(w / 2) * (h / 2);
@@ -1262,6 +1288,48 @@ static TaaArgs taaArgs(const rt_ctx* c, const DevFrame& F, int frames, bool hist
   return A;
 }
 
+// The upsampling history of both parities at the output size, the RGBA8 target and the tonemap's scratch (rt_render_frame's first frame with the mode on; the
+// caller has drained the context).  Zeroed: nothing reads it before a frame wrote it.
+static int allocUpscaleHistory(rt_ctx* c)
+{
+  const int wo = c->ups.outWidth, ho = c->ups.outHeight;
+  const size_t n = size_t(wo) * ho;
+  auto get = [&](void** p, size_t bytes) -> bool {
+    bytes = std::max<size_t>(bytes, 256);
+    if(hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
+    return hipMemset(*p, 0, bytes) == hipSuccess;
+  };
+  bool ok = true;
+  const size_t bytes[3] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float)};
+  for(auto& par : c->upsHist) for(int k = 0; k < 3 && ok; k++) ok = get(&par[k], bytes[k]);
+  ok = ok && get(&c->upsLdr, n * 4) && get(reinterpret_cast<void**>(&c->upsRowSums), size_t(ho) * 6 * sizeof(double)) && get(reinterpret_cast<void**>(&c->upsMean), 8 * sizeof(float)) &&
+       get(reinterpret_cast<void**>(&c->upsMipD), (n + 64) * sizeof(float4)) && get(reinterpret_cast<void**>(&c->upsMipI), (n + 64) * sizeof(float4));   // (sized as rt_resize sizes the render-size ones)
+  if(!ok) { freeUpscaleHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the upsampling history failed"); }
+  RT_HIP(c, hipDeviceSynchronize());
+  c->upsW = wo; c->upsH = ho; c->upsLdrWritten = false;
+  c->upsValid = false; c->upsLast = -1; c->upsHeld[0] = c->upsHeld[1] = false;
+  return RT_OK;
+}
+
+// the arguments of the upsampling resolve of frame `frames`; delta is the frame's jitter offset in render pixels
+static UpscaleArgs upscaleArgs(const rt_ctx* c, const DevFrame& F, int frames, bool histValid, const float delta[2])
+{
+  UpscaleArgs A{};
+  const int cur = frames & 1, prev = (frames + 1) & 1;
+  A.thisG = F.thisG; A.lastG = F.lastG;
+  A.curD = F.thisDirectResult; A.curI = F.thisIndirectResult;
+  A.prevD = static_cast<const float4*>(c->upsHist[prev][0]); A.prevI = static_cast<const float4*>(c->upsHist[prev][1]);
+  A.prevN = static_cast<const float*>(c->upsHist[prev][2]);
+  A.outD = static_cast<float4*>(c->upsHist[cur][0]); A.outI = static_cast<float4*>(c->upsHist[cur][1]); A.outN = static_cast<float*>(c->upsHist[cur][2]);
+  A.W = c->W; A.H = c->H; A.Wo = c->upsW; A.Ho = c->upsH;
+  A.histValid = histValid ? 1 : 0;
+  A.alpha = c->ups.alpha; A.clipGamma = c->ups.clipGamma;
+  A.dx = delta[0]; A.dy = delta[1];
+  return A;
+}
+// the ratio limits of rt_set_upscale for a render size
+static bool upscaleRatioOk(int w, int h, int wo, int ho) { return wo >= w && ho >= h && int64_t(wo) <= 4 * int64_t(w) && int64_t(ho) <= 4 * int64_t(h); }
+
 static DevFrame makeFrame(rt_ctx* c, int frames)
 {
   selectFrame(c, frames);
@@ -1310,6 +1378,8 @@ int rt_run_stage(rt_ctx* c, const rt_state* st, int frames, int stage, int level
     return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has GI spatial reuse on (rt_set_gi_spatial), whose pass after the indirect stage only rt_render_frame runs");
   if(c->taa.mode != RT_TAA_OFF)
     return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has TAA on (rt_set_taa), whose jittered camera and resolve pass only rt_render_frame runs");
+  if(c->ups.mode != RT_UPSCALE_OFF)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: this context has temporal upsampling on (rt_set_upscale), whose jittered camera and resolve pass only rt_render_frame runs");
   if(rowBegin < 0 || (rowBegin & 7)) return fail(c, RT_ERR_INVALID_ARG, "rt_run_stage: rowBegin must be a non-negative multiple of 8");
   {  // levels: the filter chains have 4 / 5, the direct stage its two halves in the spatial modes, every other stage only level 0
     const bool spatial = st->ReSTIRState == RT_RESTIR_SPATIAL || st->ReSTIRState == RT_RESTIR_SPATIOTEMPORAL;
@@ -1334,6 +1404,8 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
 {
   int rc = checkReady(c, st);
   if(rc) return rc;
+  if(c->ups.mode != RT_UPSCALE_OFF && !upscaleRatioOk(c->W, c->H, c->ups.outWidth, c->ups.outHeight))
+    return fail(c, RT_ERR_INVALID_ARG, "rt_render_frame: temporal upsampling is on (rt_set_upscale) and the render size rt_resize set no longer satisfies W <= outWidth <= 4 W, H <= outHeight <= 4 H");
   RT_HIP(c, hipSetDevice(c->device));
   if(c->evUsed == rt_ctx::MAX_SETS) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   if(c->evUsed == c->evSets.size()) {
@@ -1365,6 +1437,15 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   if(taa && !c->taaHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocTaaHistory(c))) return rc; }
   rt_scene_camera cam = c->cam;   // the camera of this frame's launches (c->cam stays what rt_set_camera stored)
   if(taa) (void)rt_taa_jitter_camera(&c->cam, frames, c->taa.jitterPhases, c->W, c->H, &cam);
+  // Temporal upsampling (rt_set_upscale; never together with TAA): the same, with its own jitter phases and a resolve into a history at the output size
+  const bool ups = c->ups.mode == RT_UPSCALE_TEMPORAL && st->debugging_mode == 0;
+  if(ups && (!c->upsHist[0][0] || c->upsW != c->ups.outWidth || c->upsH != c->ups.outHeight)) {
+    RT_HIP(c, syncAll(c));
+    freeUpscaleHistory(c);
+    if((rc = allocUpscaleHistory(c))) return rc;
+  }
+  float upsDelta[2] = {0.0f, 0.0f};
+  if(ups) (void)rt_upscale_jitter_camera(&c->cam, frames, c->ups.jitterPhases, c->W, c->H, &cam, upsDelta);
   // Object motion vectors (rt_set_object_motion): the direct and the indirect stage come from the RT_OM builds, which write / read the instance image; when an
   // instance is in motion they also read the per-instance camera table, filled here and uploaded ahead of the direct stage on its stream (below)
   const bool om = c->objMotion == RT_OBJECT_MOTION_ON && !c->counting && c->omInst;
@@ -1526,10 +1607,22 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   if(taa) taaA = taaArgs(c, F, frames, c->taaValid && c->taaLast == ((frames + 1) & 1));
   c->taaValid = false;
   c->taaHeld[frames & 1] = false;
-  // compose, then the TAA resolve when it runs; both timed under RT_STAGE_COMPOSE
+  // ... and the same for the upsampling history
+  UpscaleArgs upsA{};
+  if(ups) upsA = upscaleArgs(c, F, frames, c->upsValid && c->upsLast == ((frames + 1) & 1), upsDelta);
+  c->upsValid = false;
+  c->upsHeld[frames & 1] = false;
+  // compose, then the TAA or the upsampling resolve when one runs; all timed under RT_STAGE_COMPOSE
   auto compose = [&](hipStream_t strm) -> int {
     int r;
     if((r = run(strm, RT_STAGE_COMPOSE, 0))) return r;
+    if(ups) {
+      const hipError_t e = launchUpscaleResolve(strm, upsA, cam);
+      if(e != hipSuccess) { c->err = std::string("launchUpscaleResolve: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+      if((r = record(strm, RT_STAGE_COMPOSE))) return r;
+      c->upsValid = true; c->upsLast = frames & 1; c->upsHeld[frames & 1] = true; c->upsFrame[frames & 1] = frames;
+      return RT_OK;
+    }
     if(!taa) return RT_OK;
     const hipError_t e = launchTaaResolve(strm, taaA, cam);
     if(e != hipSuccess) { c->err = std::string("launchTaaResolve: ") + hipGetErrorString(e); return RT_ERR_HIP; }
@@ -1571,6 +1664,9 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     //   is overwritten by direct(f+3) after evDone(f), the indirect image of f by compose(f+2) on sideStream;
     //   its history is double-buffered by parity: the pass of f reads parity f-1 (written by the pass of f-1, earlier on sideStream) and the parity it writes
     //   is rewritten only by the pass of f+2, again on sideStream; rt_tonemap and rt_taa_readback join the frames in flight first.
+    // Temporal upsampling (rt_set_upscale) takes TAA's place on sideStream, after compose(f) and before evDone(f), and reads exactly what TAA reads — the result
+    //   images of f, G(f), G(f-1) — so the three writers above are ordered behind it by the same waits; its history at the output size is double-buffered by
+    //   parity and written and read on sideStream only; rt_upscale_tonemap and rt_upscale_readback join the frames in flight first.
     const uint64_t s = c->seq;
     const int r = int(s & 3);
     const uint64_t depth = (c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) ? 3u : 2u;
@@ -2054,6 +2150,8 @@ int rt_set_taa(rt_ctx* c, const rt_taa* t)
   if(!(t->alpha > 0.0f && t->alpha <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: alpha must lie in (0, 1]");
   if(!(t->clipGamma > 0.0f && std::isfinite(t->clipGamma))) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: clipGamma must be positive and finite");
   for(int32_t r : t->reserved) if(r != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: reserved fields must be 0");
+  if(t->mode == RT_TAA_ON && c->ups.mode != RT_UPSCALE_OFF)
+    return fail(c, RT_ERR_INVALID_ARG, "rt_set_taa: temporal upsampling is on (rt_set_upscale), which brings its own jitter and resolve; switch it off first");
   if(std::memcmp(&c->taa, t, sizeof(rt_taa)) == 0) return RT_OK;
   if(t->mode != c->taa.mode) {   // compose's share of the frame, which the stream priorities were decided on, has changed
     RT_HIP(c, hipSetDevice(c->device));
@@ -2100,13 +2198,15 @@ static double radicalInverse(int k, int base)
   return double(num) / double(den);
 }
 
-int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out)
+// the one implementation of rt_taa_jitter_camera / rt_upscale_jitter_camera: the jittered camera and the offset (dx, dy) in pixels
+static rt_scene_camera jitterCamera(const rt_scene_camera& in, int frames, int jitterPhases, int width, int height, float delta[2])
 {
-  if(!in || !out || jitterPhases < 0 || jitterPhases > 16 || width < 1 || height < 1) return RT_ERR_INVALID_ARG;
-  rt_scene_camera cam = *in;
+  rt_scene_camera cam = in;
+  delta[0] = delta[1] = 0.0f;
   if(jitterPhases > 0) {
     const int k = ((frames % jitterPhases) + jitterPhases) % jitterPhases + 1;
     const float dx = float(radicalInverse(k, 2) - 0.5), dy = float(radicalInverse(k, 3) - 0.5);
+    delta[0] = dx; delta[1] = dy;
     const float ox = (2.0f * dx) / float(width), oy = (2.0f * dy) / float(height);
     float* m = cam.projInverse.m;
     for(int r = 0; r < 4; r++) {
@@ -2114,7 +2214,96 @@ int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases
       m[12 + r] = (m[12 + r] + a) + b;
     }
   }
-  *out = cam;
+  return cam;
+}
+
+int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out)
+{
+  if(!in || !out || jitterPhases < 0 || jitterPhases > 16 || width < 1 || height < 1) return RT_ERR_INVALID_ARG;
+  float delta[2];
+  *out = jitterCamera(*in, frames, jitterPhases, width, height, delta);
+  return RT_OK;
+}
+
+// ---- rt_set_upscale: temporal upsampling (csrc/upscale.hip); the settings are host state read when a frame is enqueued
+int rt_upscale_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out, float delta[2])
+{
+  if(!in || !out || jitterPhases < 0 || jitterPhases > 64 || width < 1 || height < 1) return RT_ERR_INVALID_ARG;
+  float d[2];
+  *out = jitterCamera(*in, frames, jitterPhases, width, height, d);
+  if(delta) { delta[0] = d[0]; delta[1] = d[1]; }
+  return RT_OK;
+}
+
+int rt_set_upscale(rt_ctx* c, const rt_upscale* u)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!u) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: NULL settings");
+  if(u->mode != RT_UPSCALE_OFF && u->mode != RT_UPSCALE_TEMPORAL) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: mode must be RT_UPSCALE_OFF or RT_UPSCALE_TEMPORAL");
+  if(u->outWidth < 0 || u->outHeight < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: outWidth and outHeight must not be negative");
+  if(u->jitterPhases < 0 || u->jitterPhases > 64) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: jitterPhases must lie in 0..64");
+  if(!(u->alpha > 0.0f && u->alpha <= 1.0f)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: alpha must lie in (0, 1]");
+  if(!(u->clipGamma > 0.0f && std::isfinite(u->clipGamma))) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: clipGamma must be positive and finite");
+  for(int32_t r : u->reserved) if(r != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: reserved fields must be 0");
+  if(u->mode == RT_UPSCALE_TEMPORAL) {
+    if(u->outWidth < 1 || u->outHeight < 1) return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: outWidth and outHeight must be at least 1");
+    if(c->W > 0 && !upscaleRatioOk(c->W, c->H, u->outWidth, u->outHeight))
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: the output size must satisfy W <= outWidth <= 4 W and H <= outHeight <= 4 H for the render size rt_resize set");
+    if(c->taa.mode != RT_TAA_OFF)
+      return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: TAA is on (rt_set_taa); temporal upsampling brings its own jitter and resolve, switch TAA off first");
+  }
+  if(std::memcmp(&c->ups, u, sizeof(rt_upscale)) == 0) return RT_OK;
+  const bool sizeChange = c->upsHist[0][0] && (u->outWidth != c->upsW || u->outHeight != c->upsH);
+  if(u->mode != c->ups.mode || sizeChange) {
+    RT_HIP(c, hipSetDevice(c->device));
+    RT_HIP(c, syncAll(c));
+    if(u->mode != c->ups.mode) reopenPriorityDecision(c);   // compose's share of the frame, which the stream priorities were decided on, has changed
+    if(sizeChange) freeUpscaleHistory(c);
+  }
+  c->ups = *u;
+  c->upsValid = false;
+  return RT_OK;
+}
+
+int rt_get_upscale(rt_ctx* c, rt_upscale* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->ups;
+  return RT_OK;
+}
+
+int rt_upscale_reset(rt_ctx* c)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  c->upsValid = false;
+  return RT_OK;
+}
+
+int rt_upscale_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c || !dst) return RT_ERR_INVALID_ARG;
+  if(which < 0 || which > 3) return fail(c, RT_ERR_INVALID_ARG, "rt_upscale_readback: which must be 0 (direct), 1 (indirect), 2 (history length) or 3 (LDR)");
+  if(!c->upsHist[0][0] || c->upsLast < 0) return fail(c, RT_ERR_NO_TARGET, "rt_upscale_readback: no frame has been resolved since the upsampling history was last freed");
+  if(which == 3 && !c->upsLdrWritten) return fail(c, RT_ERR_NO_TARGET, "rt_upscale_readback: rt_upscale_tonemap has not run since the upsampling history was allocated");
+  const size_t px = size_t(c->upsW) * c->upsH;
+  if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float))) return fail(c, RT_ERR_INVALID_ARG, "rt_upscale_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, which == 3 ? c->upsLdr : c->upsHist[c->upsLast][which], bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_upscale_tonemap(rt_ctx* c, const rt_tonemapper* tm, int frames)
+{
+  if(!c || !tm) return RT_ERR_INVALID_ARG;
+  const int cur = frames & 1;
+  if(!c->upsHist[cur][0] || !c->upsHeld[cur] || c->upsFrame[cur] != frames)
+    return fail(c, RT_ERR_NO_TARGET, "rt_upscale_tonemap: this frame was not resolved (rt_set_upscale), or its history has been overwritten or freed");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, joinInFlight(c));  // the resolved images of `frames` are complete once the pass (side stream) is done
+  RT_HIP(c, launchTonemap(c->stream, static_cast<const float4*>(c->upsHist[cur][0]), static_cast<const float4*>(c->upsHist[cur][1]), c->upsRowSums, c->upsMean, *tm, 0,
+                          c->upsW, c->upsH, static_cast<uint32_t*>(c->upsLdr), c->upsMipD, c->upsMipI));
+  c->upsLdrWritten = true;
   return RT_OK;
 }
 

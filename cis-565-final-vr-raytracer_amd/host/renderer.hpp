@@ -260,6 +260,45 @@ class Renderer {
     }
     return true;
   }
+  // Temporal upsampling (include/rt_abi.h): off by default.  With RT_UPSCALE_TEMPORAL the context keeps rendering at the size create() / update() set, with a
+  // jittered camera (keep passing unjittered matrices to setCamera), and resolves each frame into a history at outWidth x outHeight after compose.  The
+  // output-size frame is read with readUpscaleResult / upscaleTonemap; RenderOutput::run keeps showing the render-size frame.
+  bool setUpscale(const rt_upscale& u)
+  {
+    if(rt_set_upscale(m_ctx, &u) != RT_OK) { fprintf(stderr, "Renderer::setUpscale: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_upscale getUpscale()
+  {
+    rt_upscale u{};
+    rt_get_upscale(m_ctx, &u);
+    return u;
+  }
+  bool upscaleReset() { return rt_upscale_reset(m_ctx) == RT_OK; }
+  // the last resolved frame: direct and indirect RGBA32F (outWidth x outHeight).  False before the first resolved frame.
+  bool readUpscaleResult(std::vector<float>& direct, std::vector<float>& indirect)
+  {
+    const rt_upscale u = getUpscale();
+    direct.resize(size_t(u.outWidth) * u.outHeight * 4);
+    indirect.resize(direct.size());
+    if(rt_upscale_readback(m_ctx, 0, direct.data(), direct.size() * sizeof(float)) != RT_OK ||
+       rt_upscale_readback(m_ctx, 1, indirect.data(), indirect.size() * sizeof(float)) != RT_OK) {
+      fprintf(stderr, "Renderer::readUpscaleResult: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
+  // the post pass over the resolved frame `frames` at the output size; rgba: outWidth x outHeight RGBA8, row-major, top row first
+  bool upscaleTonemap(const rt_tonemapper& tm, int frames, std::vector<uint8_t>& rgba)
+  {
+    const rt_upscale u = getUpscale();
+    rgba.resize(size_t(u.outWidth) * u.outHeight * 4);
+    if(rt_upscale_tonemap(m_ctx, &tm, frames) != RT_OK || rt_upscale_readback(m_ctx, 3, rgba.data(), rgba.size()) != RT_OK) {
+      fprintf(stderr, "Renderer::upscaleTonemap: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
   rt_ctx* context() { return m_ctx; }
  private:
   rt_ctx* m_ctx = nullptr;

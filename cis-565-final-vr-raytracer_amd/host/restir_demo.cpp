@@ -2,10 +2,12 @@
 //   loadEnvironmentHdr -> loadScene (Scene::load + AccelStructure::create) -> createRender -> per frame:
 //   updateFrame / Scene::updateCamera -> Renderer::run -> (post.frag's sum of the two HDR images, written to disk)
 // Usage mirrors main.cpp:52-54:  restir_demo [-f scene.gltf | -p cornell|helmet|sponza|bistro|interior] [-e env.hdr]
-//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf] [-g off|on|vis] [-t off|on]
+//                                            [-w 1920] [-h 1080] [-n frames] [-o out] [-s scale] [-a autoExposure] [-r samples] [-d atrous|svgf] [-g off|on|vis] [-t off|on] [-u WxH]
 // -d svgf: the variance-guided spatiotemporal denoiser (rt_set_denoiser, default settings) instead of the reference's A-Trous chain.
 // -g on|vis: ReSTIR GI spatial reuse (rt_set_gi_spatial, default settings; vis = with a visibility ray per accepted neighbour).
 // -t on: temporal anti-aliasing (rt_set_taa, default settings): the PFM and PNG show the resolved frame.  (-a is taken by autoExposure.)
+// -u WxH: temporal upsampling (rt_set_upscale, default settings) to the output size W x H (between 1x and 4x of -w / -h per axis): the frames are rendered
+//       at -w x -h, the PFM, PPM and PNG come from the resolved frame at the output size.  Not together with -t on.
 // -r N: after the real-time frames, N samples per pixel of the reference mode (rt_reference_render: the converged image the frame estimates)
 //       at the last frame's camera, tonemapped like the frame into <out>_reference.png.
 #include <algorithm>
@@ -87,6 +89,16 @@ int main(int argc, char** argv)
     if(!render.setTaa(t)) return 13;
   }
 
+  const std::string upscaleSize = arg(argc, argv, "-u", "");
+  int OW = W, OH = H;   // the size of the images written
+  if(!upscaleSize.empty()) {
+    if(sscanf(upscaleSize.c_str(), "%dx%d", &OW, &OH) != 2) { fprintf(stderr, "-u must be <width>x<height>\n"); return 14; }
+    rt_upscale u = render.getUpscale();
+    u.mode = RT_UPSCALE_TEMPORAL; u.outWidth = OW; u.outHeight = OH;
+    if(!render.setUpscale(u)) return 14;
+  }
+  const bool upscaled = !upscaleSize.empty();
+
   auto t0 = std::chrono::steady_clock::now();
   for(int f = 0; f < frames; f++) {
     scene.updateCamera(W, H);
@@ -99,11 +111,11 @@ int main(int argc, char** argv)
   printf("%d frames %dx%d: %.3f ms/frame\n", frames, W, H, ms / frames);
 
   std::vector<float> d, i;
-  if(taaMode == "on" ? !render.readTaaResult(d, i) : !render.readResult(frames - 1, d, i)) return 6;
+  if(upscaled ? !render.readUpscaleResult(d, i) : (taaMode == "on" ? !render.readTaaResult(d, i) : !render.readResult(frames - 1, d, i))) return 6;
   {  // PFM (bottom-up scanlines, little endian) of direct + indirect = the HDR frame
     std::ofstream pfm(out + ".pfm", std::ios::binary);
-    pfm << "PF\n" << W << " " << H << "\n-1.0\n";
-    for(int y = H - 1; y >= 0; y--) for(int x = 0; x < W; x++) { float c[3]; for(int k = 0; k < 3; k++) c[k] = d[(size_t(y) * W + x) * 4 + k] + i[(size_t(y) * W + x) * 4 + k]; pfm.write(reinterpret_cast<const char*>(c), 12); }
+    pfm << "PF\n" << OW << " " << OH << "\n-1.0\n";
+    for(int y = OH - 1; y >= 0; y--) for(int x = 0; x < OW; x++) { float c[3]; for(int k = 0; k < 3; k++) c[k] = d[(size_t(y) * OW + x) * 4 + k] + i[(size_t(y) * OW + x) * 4 + k]; pfm.write(reinterpret_cast<const char*>(c), 12); }
   }
   {  // the displayed frame: RenderOutput::run (post.frag: Uncharted 2 tone curve + dither) -> PPM + PNG
     RenderOutput offscreen;
@@ -111,11 +123,15 @@ int main(int argc, char** argv)
     offscreen.create(W, H);
     offscreen.m_tm.autoExposure = atoi(arg(argc, argv, "-a", "0"));
     std::vector<uint8_t> rgba;
-    if(!offscreen.run(st, 1.0f, rt_vec2{1.0f, 1.0f}, frames - 1) || !offscreen.readImage(rgba)) return 7;
+    if(upscaled) {   // the same post pass over the resolved frame at the output size
+      rt_tonemapper tm = offscreen.m_tm;
+      tm.zoom = 1.0f; tm.renderingRatio = rt_vec2{1.0f, 1.0f};
+      if(!render.upscaleTonemap(tm, frames - 1, rgba)) return 7;
+    } else if(!offscreen.run(st, 1.0f, rt_vec2{1.0f, 1.0f}, frames - 1) || !offscreen.readImage(rgba)) return 7;
     std::ofstream ppm(out + ".ppm", std::ios::binary);
-    ppm << "P6\n" << W << " " << H << "\n255\n";
-    for(size_t p = 0; p < size_t(W) * H; p++) ppm.write(reinterpret_cast<const char*>(&rgba[p * 4]), 3);
-    if(!writePng(out + ".png", rgba.data(), W, H)) fprintf(stderr, "cannot write %s.png\n", out.c_str());
+    ppm << "P6\n" << OW << " " << OH << "\n255\n";
+    for(size_t p = 0; p < size_t(OW) * OH; p++) ppm.write(reinterpret_cast<const char*>(&rgba[p * 4]), 3);
+    if(!writePng(out + ".png", rgba.data(), OW, OH)) fprintf(stderr, "cannot write %s.png\n", out.c_str());
   }
   const int refSamples = atoi(arg(argc, argv, "-r", "0"));
   if(refSamples > 0) {

@@ -21,6 +21,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_denoiser", "rt_get_denoiser", "rt_denoiser_reset", "rt_denoiser_readback",
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
+               "rt_set_upscale", "rt_get_upscale", "rt_upscale_reset", "rt_upscale_readback", "rt_upscale_tonemap", "rt_upscale_jitter_camera",
                "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
                "rt_set_instances", "rt_get_instances_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
@@ -120,6 +121,13 @@ def hip_lib():
             L.rt_taa_reset.argtypes = [C.c_void_p]
             L.rt_taa_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
             L.rt_taa_jitter_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        if hasattr(L, "rt_set_upscale"):   # temporal upsampling (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
+            L.rt_set_upscale.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_get_upscale.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_upscale_reset.argtypes = [C.c_void_p]
+            L.rt_upscale_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.rt_upscale_tonemap.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.rt_upscale_jitter_camera.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "rt_update_instances"):   # moving instances (absent from older A/B libraries loaded through RESTIR_HIP_LIB)
             L.rt_update_instances.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rt_update_lights.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -440,6 +448,47 @@ class Renderer:
         if rc != 0:
             raise RtError(f"rt_taa_jitter_camera failed ({rc})")
         return out
+
+    # ---- temporal upsampling (include/rt_abi.h "Temporal upsampling")
+    def set_upscale(self, u=None, **kw):
+        """rt_set_upscale with an abi.Upscale, or the library defaults overridden by keywords (set_upscale(mode=abi.UPSCALE_TEMPORAL, outWidth=.., outHeight=..))"""
+        u = u if u is not None else abi.Upscale(**kw)
+        self._chk(hip_lib().rt_set_upscale(self._h, C.byref(u)), "rt_set_upscale")
+
+    def get_upscale(self):
+        u = abi.Upscale()
+        self._chk(hip_lib().rt_get_upscale(self._h, C.byref(u)), "rt_get_upscale")
+        return u
+
+    def upscale_reset(self):
+        self._chk(hip_lib().rt_upscale_reset(self._h), "rt_upscale_reset")
+
+    def upscale_readback(self, which):
+        """the last resolved frame at the output size: abi.UPSCALE_DIRECT / UPSCALE_INDIRECT -> (Ho, Wo, 4) float32; UPSCALE_HISTORY_LENGTH -> (Ho, Wo) float32 n;
+        UPSCALE_LDR -> (Ho, Wo, 4) uint8, what upscale_tonemap last wrote"""
+        u = self.get_upscale()
+        Wo, Ho = u.outWidth, u.outHeight
+        if which == abi.UPSCALE_LDR:
+            out = np.empty((Ho, Wo, 4), dtype=np.uint8)
+        else:
+            out = np.empty((Ho, Wo, 4) if which in (abi.UPSCALE_DIRECT, abi.UPSCALE_INDIRECT) else (Ho, Wo), dtype=np.float32)
+        self._chk(hip_lib().rt_upscale_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_upscale_readback")
+        return out
+
+    def upscale_tonemap(self, tm, frames):
+        """rt_upscale_tonemap: the post pass over the resolved images of frame `frames` at the output size (read it with upscale_readback(abi.UPSCALE_LDR))"""
+        self._chk(hip_lib().rt_upscale_tonemap(self._h, C.byref(tm), int(frames)), "rt_upscale_tonemap")
+
+    @staticmethod
+    def upscale_jitter_camera(cam, frames, jitter_phases, width, height):
+        """rt_upscale_jitter_camera (no context, no GPU): (the camera the context renders frame `frames` with at the render size width x height when temporal
+        upsampling is on, the jitter offset (dx, dy) in render pixels as float32)"""
+        out = abi.SceneCamera()
+        delta = (C.c_float * 2)()
+        rc = hip_lib().rt_upscale_jitter_camera(C.byref(cam), int(frames), int(jitter_phases), int(width), int(height), C.byref(out), delta)
+        if rc != 0:
+            raise RtError(f"rt_upscale_jitter_camera failed ({rc})")
+        return out, np.array([delta[0], delta[1]], dtype=np.float32)
 
     # ---- moving instances (include/rt_abi.h "Moving instances", DESIGN.md §18)
     def update_instances(self, ids, transforms):

@@ -672,6 +672,64 @@ int rt_taa_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 /* pure function, no context, callable without a GPU: the camera the context renders frame `frames` with (jitterPhases 0..16, width, height >= 1) */
 int rt_taa_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out);
 /* ------------------------------------------------------------------------------------------------------------------
+ * Temporal upsampling (added within ABI 2.4, no version bump): render at the size rt_resize set (the render size W x H) with the jittered
+ * camera, resolve after compose into a history at the output size Wo x Ho (W <= Wo <= 4 W, H <= Ho <= 4 H; the two ratios may differ and need not be
+ * integers), read the displayable frame at the output size.  Tracing fewer pixels is what it buys: the traced stages cost in proportion to W * H.
+ * Jitter: a frame with debugging_mode == 0 is rendered with rt_upscale_jitter_camera(&cam, frames, jitterPhases, W, H, ., delta) in place of the camera
+ *   rt_set_camera stored: the arithmetic of rt_taa_jitter_camera (one implementation), 0..64 phases; for jitterPhases <= 16 the camera bits are
+ *   rt_taa_jitter_camera's.  delta = (h2(k) - 0.5, h3(k) - 0.5), k = (frames mod jitterPhases) + 1, is the offset in render pixels (|delta| < 0.5 per
+ *   component; (0, 0) for jitterPhases = 0): under the jitter render pixel p is sampled at render-pixel position p + 0.5 + delta.
+ * Resolve (csrc/upscale.hip), per output pixel o of frame f, fp32, IEEE divisions and square roots, no contraction, for the two components
+ * D = RT_BUF_DIRECT_RESULT and I = RT_BUF_INDIRECT_RESULT after compose (c = that image at render pixel p):
+ *   rho = (float(W) / float(Wo), float(H) / float(Ho)); u = (float(o) + 0.5) * rho; p = int(min(max(floor(u - delta), 0), float((W, H) - 1)));
+ *   e = u - ((float(p) + 0.5) + delta): from this frame's nearest sample to the output pixel's centre, in render pixels.
+ *   No valid material in G(f) at p: D and I of p pass through unchanged (all four channels), n = 1.
+ *   Reprojection as in TAA, at the render size: x = cameraPosDenoise(jittered camera, p, G-buffer distance, (W, H)); sR = (ndc(lastProjView · (x, 1)).xy ·
+ *   0.5 + 0.5) · (W, H); q = floor(sR).  sO = (sR + e) / rho is the history position of o.  The history is consistent when the previous history is
+ *   valid, q lies in the render image, G(f-1) at q has the same material hash, dot(n, n_prev) > 0.9 and |lastPosition - x| < depth_prev · 1.05 (the direct
+ *   stage's temporal test), and floor(sO) lies in the output image.  Inconsistent: out = (c.rgb, 1), n = 1 (nearest-sample upsampling).
+ *   Consistent: n = min(n_prev(floor(sO)) + 1, 1024); h = the 4 x 4 Catmull-Rom sample of the previous resolved image (Wo x Ho, taps clamped, TAA's
+ *   weights and order) around sO - 0.5; h is clipped in YCoCg onto mu ± clipGamma · sigma of c over the in-image 3 x 3 RENDER-size neighbourhood of p with
+ *   TAA's clip along the segment; kappa = max(0, 1 - |e.x| / rho.x) * max(0, 1 - |e.y| / rho.y) (a sample on the output centre counts fully, one a whole
+ *   output pixel away not at all: that pixel keeps its clipped history this frame); a = max(alpha * kappa, 1 / float(n)); out = (h (1 - a) + c a, 1).
+ *   The outputs and n form the history of parity f.
+ * History: two RGBA32F images + one f32 n per parity (Wo * Ho * 36 B each), allocated by the first resolved frame together with what rt_upscale_tonemap
+ *   needs at the output size (an RGBA8 target, row sums, means, mip pyramids); freed by rt_resize, rt_destroy and an rt_set_upscale that changes the output
+ *   size.  It is invalid after rt_resize, rt_upload_scene, rt_build_accel, an rt_set_upscale that changes anything, rt_upscale_reset, a frame with
+ *   debugging_mode != 0 (neither jittered nor resolved) and a frame whose parity does not follow the previous resolved frame's.  Mode off allocates nothing
+ *   and launches nothing.
+ * Schedule: the pass runs right after compose on compose's stream in every schedule (with frames in flight before the frame's completion event is
+ *   recorded) and is timed under RT_STAGE_COMPOSE.  It writes only its history: the frame buffers are what the frame computes at W x H with the jittered
+ *   camera, and rt_tonemap / RT_BUF_LDR keep showing the render-size result images.  Settled primary visibility is off while the mode is on.
+ * Refusals (RT_ERR_INVALID_ARG, rt_last_error names the reason, the settings in use stay): bad field values; turning the mode on while TAA is on, and
+ *   rt_set_taa(RT_TAA_ON) while it is on (one jitter, one resolve); rt_run_stage while it is on; an rt_render_frame whose render size no longer satisfies
+ *   the ratio limits after an rt_resize (rt_set_upscale checks them when a target exists).  The row-tiled hosts and rt_mgpu_* have no upsampling; the
+ *   reference mode ignores it.  A change of mode re-opens the stream-priority decision.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_UPSCALE_OFF = 0 /* default */, RT_UPSCALE_TEMPORAL = 1 };
+typedef struct {
+  int32_t mode;                  /* RT_UPSCALE_*; default OFF */
+  int32_t outWidth, outHeight;   /* W <= outWidth <= 4 W, H <= outHeight <= 4 H (checked with mode TEMPORAL; ignored, but >= 0, with mode OFF); default 0 */
+  int32_t jitterPhases;          /* 0..64; default 16.  0 = no jitter (for A/B) */
+  float   alpha;                 /* (0, 1]: weight of a sample that lies on the output pixel's centre; default 0.1 */
+  float   clipGamma;             /* > 0, finite: width of the colour box in standard deviations; default 1.0 */
+  int32_t reserved[2];           /* must be 0 */
+} rt_upscale;                    /* 32 B */
+/* validates every field (bad values: RT_ERR_INVALID_ARG, the settings in use stay) */
+int rt_set_upscale(rt_ctx* ctx, const rt_upscale* u);
+int rt_get_upscale(rt_ctx* ctx, rt_upscale* out);
+/* the next resolved frame starts without history */
+int rt_upscale_reset(rt_ctx* ctx);
+/* the last resolved frame at the output size: which = 0 direct, 1 indirect (RGBA32F, Wo * Ho * 16 B), 2 history length n (f32, Wo * Ho * 4 B), 3 the
+ * RGBA8 image rt_upscale_tonemap last wrote (Wo * Ho * 4 B).  Synchronous.  RT_ERR_NO_TARGET before the first resolved frame since the history was freed. */
+int rt_upscale_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+/* rt_tonemap's post pass (debugging_mode 0) over the resolved images of frame `frames` at Wo x Ho, into the output-size RGBA8 target.  RT_ERR_NO_TARGET
+ * when frame `frames` is not the resolved frame its parity's history holds. */
+int rt_upscale_tonemap(rt_ctx* ctx, const rt_tonemapper* tm, int frames);
+/* pure function, no context, callable without a GPU: the camera the context renders frame `frames` with (jitterPhases 0..64, width, height >= 1: the RENDER
+ * size) and, when delta is not NULL, the offset in render pixels */
+int rt_upscale_jitter_camera(const rt_scene_camera* in, int frames, int jitterPhases, int width, int height, rt_scene_camera* out, float delta[2]);
+/* ------------------------------------------------------------------------------------------------------------------
  * Moving instances (added within ABI 2.4, no version bump; csrc/refit.hip).  The reference changes an instance's objectToWorld and rebuilds its TLAS per frame
  * (src/accelstruct.cpp:132-162).  Here every (instance, triangle) pair is a world-space leaf record of one flat BVH8, so a move rewrites the leaf records of the
  * moved instances and refits the node boxes above them on the GPU; the tree keeps its topology (no rebuild, no re-derived alpha records or micro-maps, no upload
@@ -1043,7 +1101,7 @@ int rt_get_morph_stats(rt_ctx* ctx, rt_morph_stats* out);
  * the closest deterministic accept and up to K (RESTIR_VIS_K, default RT_VIS_K_DEFAULT, at most 64) stochastic candidates in front of it; later launches REPLAY:
  * they re-test those records with the frame's seed.  Frames are bit for bit what tracing gives.  A pixel with more than K such candidates keeps tracing.  A camera
  * change, rt_resize, rt_upload_scene, rt_build_accel, rt_rebuild_accel, every rt_update_* / rt_set_skins / rt_set_morph_targets call, rt_set_stream, a row-band or
- * latency-build launch, TAA or an object-motion mode on drop the state; the rt_mgpu_* hosts never record; RESTIR_PRIMARY_REPLAY=0 switches it off.  The three
+ * latency-build launch, TAA, temporal upsampling or an object-motion mode on drop the state; the rt_mgpu_* hosts never record; RESTIR_PRIMARY_REPLAY=0 switches it off.  The three
  * planes, (2 + K) x 4 B per pixel, are allocated by the first recording and freed by rt_resize / rt_destroy.
  * rt_get_primary_replay_stats: state (0 none, 1 valid), K, and in state 1 the pixel classes of the recording in force (this drains the context); launches since
  * rt_create.  A replayed query counts as a query in rt_counters.closestHitRays. */
@@ -1065,7 +1123,7 @@ int rt_primary_replay_readback(rt_ctx* ctx, void* dst, size_t bytes);
 int rt_sync(rt_ctx* ctx);
 /* Last error message of this ctx (or of rt_create when ctx == NULL). Never NULL. */
 const char* rt_last_error(rt_ctx* ctx);
-/* ABI version: (major<<16)|minor.  2.4: + object motion vectors (rt_set_object_motion, rt_object_motion_camera, rt_object_motion_readback; additions), + moving instances (rt_update_instances, rt_update_lights, rt_get_refit_stats, rt_accel_readback; additions that change no existing call, so the version stays 2.4 like the three opt-in passes before them), + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
+/* ABI version: (major<<16)|minor.  2.4: + object motion vectors (rt_set_object_motion, rt_object_motion_camera, rt_object_motion_readback; additions), + moving instances (rt_update_instances, rt_update_lights, rt_get_refit_stats, rt_accel_readback; additions that change no existing call, so the version stays 2.4 like the three opt-in passes before them), + temporal anti-aliasing (rt_set_taa, rt_get_taa, rt_taa_reset, rt_taa_readback, rt_taa_jitter_camera), + temporal upsampling (rt_set_upscale, rt_get_upscale, rt_upscale_reset, rt_upscale_readback, rt_upscale_tonemap, rt_upscale_jitter_camera), + the GI spatial reuse (rt_set_gi_spatial, rt_get_gi_spatial, rt_gi_spatial_readback) and the denoiser selection
  * (rt_set_denoiser, rt_get_denoiser, rt_denoiser_reset, rt_denoiser_readback; opt-in additions that change no existing call, so the version stays 2.4), + rt_reference_render, rt_reference_reset, rt_reference_samples, rt_reference_readback, rt_reference_tonemap.  2.3 (round 6): + rt_get_streams, rt_get_stream_layout, rt_mgpu_get_stream_layout; the priority rule probes three frames and re-opens on resize / scene / denoise.  2.2 (round 5): + rt_set_stream_priorities, rt_get_stream_priorities.  2.1 (round 4): + rt_mgpu_get_link_stats.  2.0 (round 3): rt_set_pipeline -> rt_set_traversal; RT_STAGE_DIRECT levels 1 / 2 are rejected outside the
  * spatial modes; 1.1 would have been round 2's additions (rt_mgpu_*, rt_measure_valu_peak, the `level` halves of RT_STAGE_DIRECT). */
 #define RT_ABI_VERSION_MAJOR 2u
@@ -1090,6 +1148,7 @@ static_assert(sizeof(rt_sun_and_sky) == 96, "SunAndSky host_device.h:353-377");
 static_assert(sizeof(rt_denoiser) == 32, "rt_denoiser");
 static_assert(sizeof(rt_gi_spatial) == 32, "rt_gi_spatial");
 static_assert(sizeof(rt_taa) == 32, "rt_taa");
+static_assert(sizeof(rt_upscale) == 32, "rt_upscale");
 static_assert(sizeof(rt_refit_stats) == 32, "rt_refit_stats");
 static_assert(sizeof(rt_deform_stats) == 32, "rt_deform_stats");
 static_assert(sizeof(rt_skin_influence) == 24, "rt_skin_influence");

@@ -17,6 +17,10 @@ the pixels whose primary ray hits a surface (G-buffer depth < infinity):
 at S·W × S·H in a context of its own and averages S×S blocks: the box-filtered pixel a jittered TAA frame estimates (the plain reference is point-sampled at
 pixel centres).  Every line also reports the metrics over the edge pixels: pixels whose 3×3 G-buffer neighbourhood (an unjittered frame) holds another
 material hash or a relative depth step above 10 %.
+--upscale selects temporal upsampling (rt_set_upscale), one JSON line per entry: `off` (the default: native rendering at the configuration's size), `R` or
+`R:key=value:...` (render at round(W / R) x round(H / R), resolve to W x H; rt_upscale fields jitterPhases, alpha, clipGamma) or `bilinear:R` (the same
+low-resolution frames without jitter, each upsampled bilinearly to W x H: what a host without the pass would show).  The reference, the surface and the edge
+pixels are taken at the OUTPUT size W x H (use --ref-supersample: a resolved pixel estimates the box-filtered one).
 The reference ignores the real-time state (its sums are taken once per configuration); every frame of the average uses the same camera (its history matrices
 advanced per frame, as SampleExample::updateFrame does), time = 1000 + f.
 Config 2 runs the whole frame here (bench.py times the direct stage alone for it).
@@ -25,6 +29,7 @@ Config 2 runs the whole frame here (bench.py times the direct stage alone for it
   python scripts/reference_bias.py --denoiser atrous svgf --variants default [--out profiles/denoiser_svgf.jsonl]      # the denoiser A/B
   python scripts/reference_bias.py --gi-spatial off on vis --denoiser atrous svgf --variants default [--out profiles/gi_spatial.jsonl]
   python scripts/reference_bias.py --taa off on on:jitterPhases=0 --denoiser atrous svgf --variants default --ref-supersample 4 [--out profiles/taa.jsonl]   # §16
+  python scripts/reference_bias.py --upscale off 1.5 bilinear:1.5 --variants default --ref-supersample 2 [--out profiles/upscale.jsonl]   # §29
   python scripts/reference_bias.py --timing [--configs 4 2] [--spp 16]      # reference time per sample at the configuration's size (host-timed, synchronised)
   python scripts/reference_bias.py --rays-per-path [--configs 4 2]         # CPU only: ray queries per path of the CPU restatement (tests/refpt_checker.cpp)
 """
@@ -123,6 +128,40 @@ def taa_settings(spec):
     return spec, abi.Taa(mode=abi.TAA_ON if parts[0] == "on" else abi.TAA_OFF, **kw)
 
 
+def upscale_settings(spec, W, H):
+    """`off` | `R[:key=value...]` | `bilinear:R` -> (label, kind, (w, h) render size, abi.Upscale) for the output size W x H"""
+    parts = spec.split(":")
+    if parts[0] == "off":
+        return spec, "off", (W, H), abi.Upscale()
+    try:
+        if parts[0] == "bilinear":
+            R, kind, rest = float(parts[1]), "bilinear", []
+        else:
+            R, kind, rest = float(parts[0]), "temporal", parts[1:]
+    except (ValueError, IndexError):
+        raise SystemExit(f"--upscale {spec}: off, R[:key=value...] or bilinear:R with 1 <= R <= 4")
+    kw = {}
+    for p in rest:
+        k, v = p.split("=")
+        kw[k] = int(v) if k == "jitterPhases" else float(v)
+    w, h = max(1, int(round(W / R))), max(1, int(round(H / R)))
+    if not (w <= W <= 4 * w and h <= H <= 4 * h):
+        raise SystemExit(f"--upscale {spec}: the ratio must lie in 1..4")
+    return spec, kind, (w, h), (abi.Upscale(mode=abi.UPSCALE_TEMPORAL, outWidth=W, outHeight=H, **kw) if kind == "temporal" else abi.Upscale())
+
+
+def bilinear_upsample(img, W, H):
+    """(h, w, C) -> (H, W, C), pixel centres aligned, edge texels repeated"""
+    h, w = img.shape[:2]
+    x = np.clip((np.arange(W) + 0.5) * w / W - 0.5, 0, w - 1); y = np.clip((np.arange(H) + 0.5) * h / H - 0.5, 0, h - 1)
+    x0, y0 = np.floor(x).astype(int), np.floor(y).astype(int)
+    x1, y1 = np.minimum(x0 + 1, w - 1), np.minimum(y0 + 1, h - 1)
+    fx, fy = (x - x0)[None, :, None], (y - y0)[:, None, None]
+    top = img[y0][:, x0] * (1 - fx) + img[y0][:, x1] * fx
+    bot = img[y1][:, x0] * (1 - fx) + img[y1][:, x1] * fx
+    return top * (1 - fy) + bot * fy
+
+
 def edge_pixels(g):
     """pixels whose 3x3 neighbourhood in the G-buffer g (H, W, 4 u32) has another material hash or a relative depth step above 10 %"""
     H, W = g.shape[:2]
@@ -153,9 +192,10 @@ def supersampled_reference(desc, config, W, H, S, spp, batches):
     return [box(c) for c in ref], np.sqrt(box(sigma ** 2) / (S * S)), secs
 
 
-def realtime_average(r, sc, st, frames, warmup, taa_on=False):
+def realtime_average(r, sc, st, frames, warmup, taa_on=False, upscale=None):
     """the mean of each component over the frames after warm-up, the per-pixel standard deviation of each component's luminance over those frames,
-    and the pixels that hit a surface"""
+    and the pixels that hit a surface.  upscale = (kind, W, H): the frames are rendered at st.size and the images taken at W x H, from the resolved frame
+    (`temporal`, rt_upscale_readback) or bilinearly upsampled (`bilinear`)"""
     acc = [None, None, None]
     lsum = [0.0, 0.0, 0.0]
     lsq = [0.0, 0.0, 0.0]
@@ -167,11 +207,15 @@ def realtime_average(r, sc, st, frames, warmup, taa_on=False):
         r.run(st, f)
         if f >= warmup:
             cur = f & 1
-            if taa_on:
+            if upscale is not None and upscale[0] == "temporal":
+                imgs = [r.upscale_readback(w)[..., :3].astype(np.float64) for w in (abi.UPSCALE_DIRECT, abi.UPSCALE_INDIRECT)]
+            elif taa_on:
                 imgs = [r.taa_readback(w)[..., :3].astype(np.float64) for w in (abi.TAA_DIRECT, abi.TAA_INDIRECT)]
             else:
                 imgs = [r.readback(buf).view(np.float32).reshape(st.size.y, st.size.x, 4)[..., :3].astype(np.float64)
                         for buf in (abi.BUF_DIRECT_RESULT0 + cur, abi.BUF_INDIRECT_RESULT0 + cur)]
+            if upscale is not None and upscale[0] == "bilinear":
+                imgs = [bilinear_upsample(img, upscale[1], upscale[2]) for img in imgs]
             imgs.append(imgs[0] + imgs[1])
             for k, img in enumerate(imgs):
                 acc[k] = img if acc[k] is None else acc[k] + img
@@ -214,28 +258,40 @@ def bias(args):
         # the edge pixels, from one unjittered frame
         r.set_camera(sc.getCamera())
         r.run(st0, 0)
-        edge = edge_pixels(r.readback(abi.BUF_GBUFFER0).view(np.uint32).reshape(H, W, 4))
-        runs = [(v, d, g, t) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)
-                for g in map(gi_spatial_settings, args.gi_spatial) for t in map(taa_settings, args.taa)]
-        for (vname, over), (dname, den), (gname, gis), (tname, taa) in runs:
+        g_native = r.readback(abi.BUF_GBUFFER0).view(np.uint32).reshape(H, W, 4)
+        edge = edge_pixels(g_native)
+        surface_native = g_native[..., 0].view(np.float32) < 1e28 * 0.8
+        runs = [(v, d, g, t, u) for v in VARIANTS.items() if v[0] in args.variants for d in map(denoiser_settings, args.denoiser)
+                for g in map(gi_spatial_settings, args.gi_spatial) for t in map(taa_settings, args.taa) for u in (upscale_settings(x, W, H) for x in args.upscale)]
+        edges = args.taa != ["off"] or args.upscale != ["off"]
+        for (vname, over), (dname, den), (gname, gis), (tname, taa), (uname, ukind, (w, h), ups) in runs:
             st = abi.RtxState.from_buffer_copy(st0)
             for k, v in over.items():
                 setattr(st, k, v)
-            r.update(W, H)                                      # fresh history for every variant
+            st.size.x, st.size.y = w, h
+            if args.upscale != ["off"]:
+                r.set_upscale(abi.Upscale())                    # (the ratio limits are checked against the size in force)
+            r.update(w, h)                                      # fresh history for every variant
             r.set_denoiser(den)
             r.set_gi_spatial(gis)
             r.set_taa(taa)
+            if ukind == "temporal":
+                r.set_upscale(ups)
+            sc.updateCamera(w, h)
             r.set_camera(sc.getCamera())
-            frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup, taa.mode == abi.TAA_ON)
+            frame, std, surface = realtime_average(r, sc, st, args.frames, args.warmup, taa.mode == abi.TAA_ON, None if ukind == "off" else (ukind, W, H))
+            if ukind != "off":
+                surface = surface_native
             out = {"config": config, "variant": vname, "denoiser": dname, **({"gi_spatial": gname} if args.gi_spatial != ["off"] else {}),
-                   **({"taa": tname, "ref_supersample": args.ref_supersample, "edge_share": round(float(edge.mean()), 4)} if args.taa != ["off"] else {}),
+                   **({"taa": tname} if args.taa != ["off"] else {}), **({"upscale": uname, "render_size": [w, h]} if args.upscale != ["off"] else {}),
+                   **({"ref_supersample": args.ref_supersample, "edge_share": round(float(edge.mean()), 4)} if edges else {}),
                    "size": [W, H], "frames": args.frames, "warmup": args.warmup, "ref_spp": args.spp,
                    "ref_batches": args.batches, "ref_seconds": round(secs, 2), "surface_share": round(float(surface.mean()), 4)}
             everything = np.ones_like(surface)
             for name, c in (("direct", 0), ("indirect", 1), ("sum", 2)):
                 out[name] = {"all": metrics(frame[c], ref[c], sigma if c == 2 else None, everything, std[c]),
                              "surface": metrics(frame[c], ref[c], sigma if c == 2 else None, surface, std[c])}
-                if args.taa != ["off"]:
+                if edges:
                     out[name]["edge"] = metrics(frame[c], ref[c], sigma if c == 2 else None, edge, std[c])
             line = json.dumps(out)
             print(line, flush=True)
@@ -297,6 +353,7 @@ def main():
     ap.add_argument("--denoiser", nargs="+", default=["atrous"], help="atrous | svgf | svgf:key=value:... (one run of the real-time frames per entry)")
     ap.add_argument("--gi-spatial", nargs="+", default=["off"], help="off | on | vis | on:key=value:... (ReSTIR GI spatial reuse; one run per entry)")
     ap.add_argument("--taa", nargs="+", default=["off"], help="off | on | on:key=value:... (temporal anti-aliasing; one run per entry)")
+    ap.add_argument("--upscale", nargs="+", default=["off"], help="off | R[:key=value:...] | bilinear:R (temporal upsampling from 1/R of the size; one run per entry)")
     ap.add_argument("--ref-supersample", type=int, default=1, help="S: the reference at S*W x S*H, averaged over S x S blocks")
     ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=list(VARIANTS))
     ap.add_argument("--timing", action="store_true")
