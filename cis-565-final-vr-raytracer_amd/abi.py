@@ -215,6 +215,19 @@ PUNC_LIGHT_DT = np.dtype([("type", "<i4"), ("direction", "<f4", 3), ("intensity"
 assert LIGHT_SOURCE_DT.itemsize == 8 and TRIG_LIGHT_DT.itemsize == 96 and PUNC_LIGHT_DT.itemsize == 80 and C.sizeof(LightStats) == 32
 
 
+class EmitterStats(C.Structure):  # rt_emitter_stats, 32 B
+    _fields_ = [("enabled", C.c_uint32), ("records", C.c_uint32), ("emittingInstances", C.c_uint32), ("bytesUploaded", C.c_uint32), ("reallocated", C.c_uint32),
+                ("expandMs", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+# rt_set_emitter_meshes (include/rt_abi.h "Emitters"): rt_emitter_mesh (16 B) and rt_emitter_row (32 B) as numpy rows
+EMITTER_MESH_DT = np.dtype([("primMesh", "<u4"), ("firstRow", "<u4"), ("rowCount", "<u4"), ("reserved", "<u4")])
+EMITTER_ROW_DT = np.dtype([("triangle", "<u4"), ("uv", "<f4", 6), ("pad", "<u4")])
+# int rt_set_emitter_meshes(rt_ctx*, uint32_t numMeshes, const rt_emitter_mesh*, uint32_t numRows, const rt_emitter_row*, float puncLightWeight)
+SET_EMITTER_MESHES_ARGTYPES = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float]
+assert EMITTER_MESH_DT.itemsize == 16 and EMITTER_ROW_DT.itemsize == 32 and C.sizeof(EmitterStats) == 32
+
+
 class RefitStats(C.Structure):  # rt_refit_stats, 32 B
     _fields_ = [("instances", C.c_uint32), ("leafRecords", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("fullRefit", C.c_uint32),
                 ("ms", C.c_float), ("triPad", C.c_float), ("treePad", C.c_float)]

@@ -32,6 +32,8 @@
 #include "deform.h"
 #include "morph.h"
 #include "light_records.h"
+#include "light_derive.h"
+#include "../host/alias_table.hpp"
 #include "dev_math.h"
 
 using namespace rt;
@@ -231,6 +233,25 @@ struct rt_ctx {
   } lights;
   std::vector<void*> lightAllocs;
   hipEvent_t evLights[2] = {nullptr, nullptr};   // start / end of the light kernel of the last update (created by the first binding)
+  // rt_set_emitter_meshes (csrc/light_derive.hip).  The templates (rows of all meshes, first row per prim mesh) live in emitAllocs: replaced by
+  // rt_set_emitter_meshes, dropped by rt_upload_scene.  set[]: the light buffers rt_set_instances derives into, each in a pool of its own; cur: the set the
+  // context's records and binding live in (-1: the uploaded array and the binding of the switch-on, in sceneAllocs / lightAllocs).
+  struct Emit {
+    bool on = false;
+    std::vector<int64_t> meshFirstRow;           // per prim mesh: first template row, or -1 (no template)
+    std::vector<uint32_t> meshRows;              // per prim mesh: rows of its template
+    float puncWeight = 0.f;
+    rt_emitter_row* dRows = nullptr; uint32_t* dMeshFirstRow = nullptr;
+    struct Set {
+      rt_trig_light* rec = nullptr; rt_light_source* src = nullptr; rt_impt_samp* alias = nullptr; uint32_t* prefix = nullptr; uint32_t* ids = nullptr;
+      uint32_t recCap = 0, emitCap = 0;
+      std::vector<void*> pool;
+    } set[2];
+    int cur = -1;
+    rt_emitter_stats stats{};
+  } emit;
+  std::vector<void*> emitAllocs;
+  hipEvent_t evEmit[2] = {nullptr, nullptr};     // around k_light_expand
   // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
   // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
   int objMotion = RT_OBJECT_MOTION_OFF;
@@ -567,6 +588,13 @@ template <class T> static int allocZeroed(rt_ctx* c, std::vector<void*>& pool, s
   return rc;
 }
 static void freePool(std::vector<void*>& pool) { for(void* p : pool) (void)hipFree(p); pool.clear(); }
+// the emitter mode leaves the context: templates and derived light buffers go (the caller has drained the context and replaces what c->ds.trigLights names)
+static void dropEmitters(rt_ctx* c)
+{
+  freePool(c->emitAllocs);
+  for(auto& S : c->emit.set) freePool(S.pool);
+  c->emit = rt_ctx::Emit{};
+}
 // RESTIR_BVH_TIMING=1: where the seconds of rt_upload_scene / rt_build_accel go (stderr)
 struct LoadTimer {
   const bool on = getenv("RESTIR_BVH_TIMING") && atoi(getenv("RESTIR_BVH_TIMING")) != 0;
@@ -657,6 +685,7 @@ int rt_destroy(rt_ctx* c)
   (void)syncAll(c);
   freePool(c->sceneAllocs); freePool(c->accelAllocs); freePool(c->scratchAllocs); freePool(c->ovfAllocs); freePool(c->rebuildAllocs);
   freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs); freePool(c->instAllocs);
+  dropEmitters(c);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
   for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable, c->vmPlane, c->vmDelta, c->vmDeltaSpare,
                   c->vmDeltaSpare2, c->vmTable}) if(p) (void)hipFree(p);
@@ -687,6 +716,7 @@ int rt_destroy(rt_ctx* c)
   for(hipEvent_t e : c->evLights) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evInst) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evEmit) if(e) (void)hipEventDestroy(e);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -765,6 +795,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->morph = rt_ctx::Morph{}; c->skinMats.clear();
   freePool(c->lightAllocs);   // ... and no light-source binding
   c->lights = rt_ctx::Lights{};
+  dropEmitters(c);            // ... and no emitter mode
   freePool(c->instAllocs);    // ... and no instance templates
   c->inst = rt_ctx::InstTemplates{};
   c->deform = rt_ctx::Deform{};
@@ -2850,6 +2881,103 @@ static int makeMeshTemplates(rt_ctx* c, uint32_t mesh, uint32_t* bytesUploaded)
   return RT_OK;
 }
 
+/* ---- emitters: triangle-light records derived from the instance table (include/rt_abi.h "Emitters", csrc/light_derive.hip) ---- */
+// What the host contributes to the derived list of a table: the emitting instances and their first records, the alias entries, the count and trigSampProb.
+struct EmitPlan {
+  std::vector<uint32_t> ids, prefix;     // emitting instances ascending; prefix has one word more (the record count)
+  std::vector<rt_impt_samp> alias;       // per record
+  uint32_t records = 0;
+  float trigSampProb = 0.f;
+};
+
+// bytes a plan moves host -> device: the alias entries, the prefix words and the ids (the formula of include/rt_abi.h)
+static uint32_t emitPlanBytes(const EmitPlan& P) { return uint32_t(P.alias.size() * sizeof(rt_impt_samp) + (P.prefix.size() + P.ids.size()) * 4); }
+
+// The plan of `instances` under the templates (meshFirstRow[m] < 0: prim mesh m has none).  RT_ERR_INVALID_ARG for an instance of an emissive prim mesh
+// without a template.  The alias table is the host Scene's (createTrigLightBuffer): weights luminance(emissiveFactor), total summed in record order.
+static int planEmitters(rt_ctx* c, const char* who, uint32_t numInstances, const rt_instance* instances, const std::vector<int64_t>& meshFirstRow,
+                        const std::vector<uint32_t>& meshRows, float puncWeight, EmitPlan& P)
+{
+  uint64_t recs = 0;
+  std::vector<float> distrib;
+  for(uint32_t i = 0; i < numInstances; i++) {
+    const uint32_t mesh = instances[i].primMesh;
+    if(meshFirstRow[mesh] < 0) {
+      if(emissiveMesh(c, mesh)) {
+        c->err = std::string(who) + ": instance " + std::to_string(i) + ": its emissive prim mesh " + std::to_string(mesh) + " has no emitter template";
+        return RT_ERR_INVALID_ARG;
+      }
+      continue;
+    }
+    P.ids.push_back(i);
+    P.prefix.push_back(uint32_t(recs));
+    recs += meshRows[mesh];
+    if(recs > 0x7fffffffull) { c->err = std::string(who) + ": more than 2^31 - 1 triangle-light records"; return RT_ERR_INVALID_ARG; }
+    const rt_vec3& e = c->materials[size_t(c->primMeshes[mesh].materialIndex)].emissiveFactor;   // (a template needs a material: rt_set_emitter_meshes)
+    distrib.insert(distrib.end(), meshRows[mesh], e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f);
+  }
+  P.prefix.push_back(uint32_t(recs));
+  P.records = uint32_t(recs);
+  float total = 0.f;
+  for(const float w : distrib) total += w;
+  if(P.records) {
+    const std::vector<rth::AliasBucket> table = rth::buildAliasTable(distrib);
+    P.alias.resize(P.records);
+    for(size_t k = 0; k < distrib.size(); k++) P.alias[k] = rt_impt_samp{table[k].failId, table[k].prob, distrib[k] / total, distrib[size_t(table[k].failId)] / total};
+  }
+  // Scene::setInstances' rule: with no light of either kind the value stays
+  P.trigSampProb = (P.records > 0 || c->ds.lightInfo.puncLightSize > 0) ? total / (total + puncWeight) : c->ds.lightInfo.trigSampProb;
+  return RT_OK;
+}
+
+// one set of derived light buffers with 1/8 slack over the counts
+static hipError_t allocEmitSet(rt_ctx::Emit::Set& S, uint32_t records, uint32_t emitting)
+{
+  const size_t recCap = std::max<size_t>(size_t(records) + records / 8, 1), emitCap = std::max<size_t>(size_t(emitting) + emitting / 8, 1);
+  hipError_t e = hipSuccess;
+  auto get = [&](size_t bytes, auto** out) {
+    if(e != hipSuccess) return;
+    void* p = nullptr;
+    e = hipMalloc(&p, bytes);
+    if(e == hipSuccess) { S.pool.push_back(p); *out = static_cast<std::remove_reference_t<decltype(**out)>*>(p); }
+  };
+  get(recCap * sizeof(rt_trig_light), &S.rec); get(recCap * sizeof(rt_light_source), &S.src); get(recCap * sizeof(rt_impt_samp), &S.alias);
+  get((emitCap + 1) * 4, &S.prefix); get(emitCap * 4, &S.ids);
+  if(e == hipSuccess) { S.recCap = uint32_t(std::min<size_t>(recCap, 0xffffffffu)); S.emitCap = uint32_t(std::min<size_t>(emitCap, 0xffffffffu)); }
+  else freePool(S.pool);
+  return e;
+}
+
+// the plan's words into the staging arrays of S, then k_light_expand between evEmit[0] and evEmit[1], on the main stream; records / sources: where it writes
+static hipError_t enqueueLightExpand(rt_ctx* c, const EmitPlan& P, const rt_ctx::Emit::Set& S, const DevInstance* dInst, const rt_emitter_row* dRows,
+                                     const uint32_t* dMeshFirstRow, rt_trig_light* records, rt_light_source* sources)
+{
+  hipStream_t s = c->stream;
+  hipError_t he;
+  if(P.records && (he = hipMemcpyAsync(S.alias, P.alias.data(), P.alias.size() * sizeof(rt_impt_samp), hipMemcpyHostToDevice, s)) != hipSuccess) return he;
+  if((he = hipMemcpyAsync(S.prefix, P.prefix.data(), P.prefix.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return he;
+  if(!P.ids.empty() && (he = hipMemcpyAsync(S.ids, P.ids.data(), P.ids.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return he;
+  if((he = hipEventRecord(c->evEmit[0], s)) != hipSuccess) return he;
+  LightExpandArgs x{};
+  x.prefix = S.prefix; x.ids = S.ids; x.meshFirstRow = dMeshFirstRow; x.rows = dRows; x.alias = S.alias; x.instances = dInst;
+  x.primMeshes = c->ds.primMeshes; x.vertices = c->ds.vertices; x.indices = c->ds.indices; x.records = records; x.sources = sources;
+  x.numEmit = uint32_t(P.ids.size()); x.numRecs = P.records;
+  if((he = launchLightExpand(s, x)) != hipSuccess) return he;
+  return hipEventRecord(c->evEmit[1], s);
+}
+
+// the derived (instance, triangle) list becomes the light-source binding (the counter of the refit tail stays)
+static void installDerivedBinding(rt_ctx* c, const EmitPlan& P, size_t numInstances, rt_light_source* dSources)
+{
+  rt_ctx::Lights& L = c->lights;
+  uint32_t* const counter = L.dCounter;
+  L = rt_ctx::Lights{};
+  L.bound = P.records; L.dSources = dSources; L.dCounter = counter;
+  L.instances.assign(numInstances, 0);
+  for(const uint32_t i : P.ids) L.instances[i] = 1;
+  L.stats.bound = P.records;
+}
+
 extern "C" {
 
 int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instances)
@@ -2880,7 +3008,11 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   }
   if(total == 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: the table has no triangles");
   prefix[numInstances] = uint32_t(total);
-  if(c->ds.lightInfo.trigLightSize > 0) {   // the emitter rule: light records, alias table and binding name instances by index
+  const bool derive = c->emit.on;   // the emitter mode: the light records follow from the table, so the emitter rule gives way to the template rule
+  EmitPlan plan;
+  if(derive) {
+    if(const int prc = planEmitters(c, "rt_set_instances", numInstances, instances, c->emit.meshFirstRow, c->emit.meshRows, c->emit.puncWeight, plan)) return prc;
+  } else if(c->ds.lightInfo.trigLightSize > 0) {   // the emitter rule: light records, alias table and binding name instances by index
     for(uint32_t i = 0; i < nOld; i++)
       if((emissiveMesh(c, c->instances[i].primMesh) || (i < c->lights.instances.size() && c->lights.instances[i])) && (i >= numInstances || memcmp(&c->instances[i], &instances[i], sizeof(rt_instance)) != 0))
         return refuse(i, "an emissive instance must stay in place, byte for byte (move it with rt_update_instances)");
@@ -2947,7 +3079,22 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   }
   rt_ctx::Rebuild& W = fits ? B : fresh;
   // what a call that fails puts back: the shared working buffers describe the context's table again, new buffers go
-  auto giveUp = [&] { if(fits) { B.work.n = uint32_t(c->numTris); B.work.table = B.table[B.icur]; } else freePool(freshPool); };
+  // the emitter mode's light buffers: the set the context does not use, or a new one with slack where that is absent or too small
+  rt_ctx::Emit& EM = c->emit;
+  const int es = EM.cur == 0 ? 1 : 0;
+  rt_ctx::Emit::Set freshSet;
+  const bool setFits = !derive || (EM.set[es].rec && plan.records <= EM.set[es].recCap && plan.ids.size() <= EM.set[es].emitCap);
+  auto giveUp = [&] { if(fits) { B.work.n = uint32_t(c->numTris); B.work.table = B.table[B.icur]; } else freePool(freshPool); freePool(freshSet.pool); };
+  if(!setFits) {
+    const hipError_t e = allocEmitSet(freshSet, plan.records, uint32_t(plan.ids.size()));
+    if(e != hipSuccess) {
+      giveUp();
+      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+  }
+  rt_ctx::Emit::Set& LS = setFits ? EM.set[es] : freshSet;
+  if(derive) for(hipEvent_t& e : c->evEmit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
   for(hipEvent_t& e : c->evRebuild) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
   for(hipEvent_t& e : c->evInst) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
   for(hipEvent_t& e : c->evRefit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
@@ -2968,6 +3115,9 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     x.triRef = W.triRef[ti]; x.table = W.table[ti]; x.flipBits = W.dFlip; x.numInst = numInstances; x.numTris = n;
     if((he = launchExpandInstances(s, x)) != hipSuccess) break;
     if((he = hipEventRecord(c->evInst[1], s)) != hipSuccess) break;
+    if(derive) {   // the light records and the binding of the new table, into the spare set: the new instance rows are in place on this stream
+      if((he = enqueueLightExpand(c, plan, LS, W.inst[ti], EM.dRows, EM.dMeshFirstRow, LS.rec, LS.src)) != hipSuccess) break;
+    }
     if((he = hipMemsetAsync(W.dDirty, 0xff, words * 4, s)) != hipSuccess) break;   // every instance marked moved
     if((he = hipMemsetAsync(W.dCounters, 0, 16, s)) != hipSuccess) break;
     W.work.n = n; W.work.table = W.table[ti];
@@ -2996,8 +3146,19 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   DevScene next = c->ds;
   next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri; next.triRef = W.triRef[ti]; next.instances = W.inst[ti];
   next.alphaRec = TP.dAlpha; next.triPad = triPad;
+  if(derive) { next.trigLights = LS.rec; next.lightInfo.trigLightSize = plan.records; next.lightInfo.trigSampProb = plan.trigSampProb; }
   if((rc = adoptDeviceTree(c, next, res, n))) { giveUp(); return rc; }
   if(!fits) { freePool(c->rebuildAllocs); c->rebuildAllocs.swap(freshPool); B = fresh; }
+  if(derive) {   // lights and tree change hands together
+    if(!setFits) { freePool(EM.set[es].pool); EM.set[es] = std::move(freshSet); freshSet.pool.clear(); }
+    EM.cur = es;
+    installDerivedBinding(c, plan, numInstances, EM.set[es].src);
+    rt_emitter_stats lightStats{};
+    lightStats.enabled = 1u; lightStats.records = plan.records; lightStats.emittingInstances = uint32_t(plan.ids.size()); lightStats.bytesUploaded = emitPlanBytes(plan);
+    lightStats.reallocated = setFits ? 0u : 1u;
+    (void)hipEventElapsedTime(&lightStats.expandMs, c->evEmit[0], c->evEmit[1]);
+    EM.stats = lightStats;
+  }
   B.icur = ti; B.cur = ts;
   c->instances.assign(instances, instances + numInstances);
   c->numTris = n;
@@ -3310,7 +3471,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
       }
     }
     const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-    if(c->lights.bound == 0 && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer); with a binding the refit tail rewrites the records
+    if(c->lights.bound == 0 && !c->emit.on && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer); with a binding the refit tail rewrites the records
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
     restFirst[k] = uint32_t(totalVerts);
     totalVerts += pm.vertexCount; totalJoints += sk.jointCount;
@@ -3449,7 +3610,7 @@ int rt_set_morph_targets(rt_ctx* c, uint32_t numSets, const rt_morph_set* sets, 
       if(!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: non-finite delta");
     }
     const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-    if(c->lights.bound == 0 && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
+    if(c->lights.bound == 0 && !c->emit.on && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
     if(D.skinOfMesh.empty() || D.skinOfMesh[ms.primMesh] < 0) { restFirst[k] = uint32_t(poolVerts); poolVerts += pm.vertexCount; }
     totalTargets += ms.targetCount;
@@ -3554,6 +3715,7 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
 {
   if(!c) return RT_ERR_INVALID_ARG;
   if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_light_sources: no scene uploaded");
+  if(c->emit.on) return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: the emitter mode is on (the binding is derived from the instance table; rt_set_emitter_meshes with 0 meshes switches it off)");
   rt_ctx::Lights& L = c->lights;
   if(numTrig == 0) {
     for(const rt_skin& sk : c->deform.skins) {
@@ -3660,6 +3822,110 @@ int rt_get_light_stats(rt_ctx* c, rt_light_stats* out)
 {
   if(!c || !out) return RT_ERR_INVALID_ARG;
   *out = c->lights.stats;
+  return RT_OK;
+}
+
+/* ---- emitters: the mode's switch (include/rt_abi.h "Emitters") ---- */
+int rt_set_emitter_meshes(rt_ctx* c, uint32_t numMeshes, const rt_emitter_mesh* meshes, uint32_t numRows, const rt_emitter_row* rows, float puncLightWeight)
+{
+  if(int rc = needTree(c, "rt_set_emitter_meshes")) return rc;
+  rt_ctx::Emit& EM = c->emit;
+  if(numMeshes == 0) {   // off: records, binding and lightInfo stay; the templates go with the next switch-on or upload
+    EM.on = false;
+    EM.stats.enabled = 0u;
+    return RT_OK;
+  }
+  if(!meshes || (numRows && !rows)) return fail(c, RT_ERR_INVALID_ARG, "rt_set_emitter_meshes: NULL template array");
+  if(!std::isfinite(puncLightWeight) || puncLightWeight < 0.f) return fail(c, RT_ERR_INVALID_ARG, "rt_set_emitter_meshes: puncLightWeight must be finite and not negative");
+  auto refuse = [&](uint32_t m, const std::string& what) { c->err = "rt_set_emitter_meshes: template " + std::to_string(m) + ": " + what; return RT_ERR_INVALID_ARG; };
+  std::vector<int64_t> first(c->primMeshes.size(), -1);
+  std::vector<uint32_t> count(c->primMeshes.size(), 0u);
+  for(uint32_t m = 0; m < numMeshes; m++) {
+    const rt_emitter_mesh& em = meshes[m];
+    if(em.primMesh >= c->primMeshes.size()) return refuse(m, "prim mesh out of range");
+    if(first[em.primMesh] >= 0) return refuse(m, "prim mesh " + std::to_string(em.primMesh) + " is listed twice");
+    const rt_prim_mesh& pm = c->primMeshes[em.primMesh];
+    if(pm.materialIndex < 0 || !emissiveMesh(c, em.primMesh)) return refuse(m, "prim mesh " + std::to_string(em.primMesh) + " is not emissive by the scene's light rule");
+    if(uint64_t(em.firstRow) + em.rowCount > numRows) return refuse(m, "row range outside rows");
+    for(uint32_t r = em.firstRow; r < em.firstRow + em.rowCount; r++) {
+      if(rows[r].triangle >= pm.indexCount / 3u) return refuse(m, "row " + std::to_string(r) + ": triangle beyond the prim mesh's index list");
+      for(const float v : rows[r].uv) if(!std::isfinite(v)) return refuse(m, "row " + std::to_string(r) + ": non-finite uv");
+    }
+    first[em.primMesh] = int64_t(em.firstRow); count[em.primMesh] = em.rowCount;
+  }
+  EmitPlan plan;
+  if(const int rc = planEmitters(c, "rt_set_emitter_meshes", uint32_t(c->instances.size()), c->instances.data(), first, count, puncLightWeight, plan)) return rc;
+  if(plan.records != c->ds.lightInfo.trigLightSize) {
+    c->err = "rt_set_emitter_meshes: the templates derive " + std::to_string(plan.records) + " records, the device holds " + std::to_string(c->ds.lightInfo.trigLightSize);
+    return RT_ERR_INVALID_ARG;
+  }
+  if(memcmp(&plan.trigSampProb, &c->ds.lightInfo.trigSampProb, 4) != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_emitter_meshes: the derived trigSampProb differs from the device's (puncLightWeight)");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  // Templates, the plan's words, scratch records and the candidate binding in pools of their own: nothing of the context changes before the derived records equal the
+  // device's in all 96 bytes.
+  std::vector<void*> fresh, binding, temp;
+  std::vector<uint32_t> firstWords(first.size());
+  for(size_t m = 0; m < first.size(); m++) firstWords[m] = first[m] < 0 ? 0u : uint32_t(first[m]);
+  const rt_emitter_row* dRows = nullptr;
+  const uint32_t* dFirst = nullptr;
+  const rt_light_source* noSrc = nullptr; const rt_light_source* dSrc = nullptr;
+  uint32_t* dCounter = nullptr;
+  rt_trig_light* dScratch = nullptr;
+  rt_ctx::Emit::Set S;   // staging only: its arrays live in temp
+  const uint32_t n = plan.records;
+  int rc = upload(c, fresh, rows, size_t(numRows), &dRows);
+  if(!rc) rc = upload(c, fresh, firstWords.data(), firstWords.size(), &dFirst);
+  if(!rc) rc = upload(c, binding, noSrc, size_t(n), &dSrc);
+  if(!rc) rc = allocZeroed(c, binding, 1, &dCounter);
+  if(!rc) rc = allocZeroed(c, temp, size_t(n), &dScratch);
+  if(!rc) rc = allocZeroed(c, temp, size_t(n), &S.alias);
+  if(!rc) rc = allocZeroed(c, temp, plan.prefix.size(), &S.prefix);
+  if(!rc) rc = allocZeroed(c, temp, plan.ids.size(), &S.ids);
+  std::vector<rt_trig_light> recs(n), eval(n);
+  hipError_t he = hipSuccess;
+  if(!rc) {
+    he = hipDeviceSynchronize();   // the arrays above were cleared on the null stream (as in rt_set_light_sources)
+    for(hipEvent_t& e : c->evLights) if(he == hipSuccess && !e) he = hipEventCreate(&e);
+    for(hipEvent_t& e : c->evEmit) if(he == hipSuccess && !e) he = hipEventCreate(&e);
+    if(he == hipSuccess) he = enqueueLightExpand(c, plan, S, c->ds.instances, dRows, dFirst, dScratch, const_cast<rt_light_source*>(dSrc));
+    if(he == hipSuccess) he = hipStreamSynchronize(c->stream);
+    if(he == hipSuccess && n) he = hipMemcpy(eval.data(), dScratch, size_t(n) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
+    if(he == hipSuccess && n) he = hipMemcpy(recs.data(), c->ds.trigLights, size_t(n) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
+  }
+  freePool(temp);
+  if(rc || he != hipSuccess) {
+    freePool(fresh); freePool(binding);
+    if(rc) return rc;
+    c->err = std::string("rt_set_emitter_meshes: ") + hipGetErrorString(he);
+    return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+  }
+  for(uint32_t k = 0; k < n; k++)
+    if(memcmp(&recs[k], &eval[k], sizeof(rt_trig_light)) != 0) {
+      freePool(fresh); freePool(binding);
+      const uint32_t e = uint32_t(std::upper_bound(plan.prefix.begin(), plan.prefix.end() - 1, k) - plan.prefix.begin()) - 1u;
+      c->err = "rt_set_emitter_meshes: record " + std::to_string(k) + " on the device differs from the one derived for row " + std::to_string(k - plan.prefix[e]) +
+               " of instance " + std::to_string(plan.ids[e]) + " (stale records: rt_update_lights first)";
+      return RT_ERR_INVALID_ARG;
+    }
+  freePool(c->emitAllocs); c->emitAllocs = fresh;
+  freePool(c->lightAllocs); c->lightAllocs = binding;
+  c->lights.dCounter = dCounter;
+  installDerivedBinding(c, plan, c->instances.size(), const_cast<rt_light_source*>(dSrc));
+  EM.on = true;
+  EM.meshFirstRow = first; EM.meshRows = count; EM.puncWeight = puncLightWeight;
+  EM.dRows = const_cast<rt_emitter_row*>(dRows); EM.dMeshFirstRow = const_cast<uint32_t*>(dFirst);
+  EM.stats = rt_emitter_stats{};
+  EM.stats.enabled = 1u; EM.stats.records = n; EM.stats.emittingInstances = uint32_t(plan.ids.size());
+  EM.stats.bytesUploaded = uint32_t(size_t(numRows) * sizeof(rt_emitter_row) + firstWords.size() * 4) + emitPlanBytes(plan);
+  (void)hipEventElapsedTime(&EM.stats.expandMs, c->evEmit[0], c->evEmit[1]);
+  return RT_OK;
+}
+
+int rt_get_emitter_stats(rt_ctx* c, rt_emitter_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->emit.stats;
   return RT_OK;
 }
 

@@ -34,6 +34,7 @@ def host_lib():
             "rth_scene_set_instances": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
             "rth_scene_light_sources": [C.c_void_p, C.c_void_p, C.c_uint32],
+            "rth_scene_emitter_meshes": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_env_destroy": [C.c_void_p], "rth_env_load": [C.c_void_p, C.c_char_p], "rth_env_set": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
             "rth_env_make_sky": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint32], "rth_env_integral": [C.c_void_p], "rth_env_average": [C.c_void_p],
@@ -138,6 +139,14 @@ class Scene:
         if n:
             host_lib().rth_scene_light_sources(self._h, out.ctypes.data, n)
         return out
+    def emitterMeshes(self):
+        """Scene::emitterMeshes: (abi.EMITTER_MESH_DT entries, abi.EMITTER_ROW_DT rows), the templates Renderer.set_emitter_meshes takes (with lightWeights[0])"""
+        nm, nr = C.c_uint32(0), C.c_uint32(0)
+        if host_lib().rth_scene_emitter_meshes(self._h, None, 0, C.byref(nm), None, 0, C.byref(nr)) != 0:
+            raise RuntimeError("Scene.emitterMeshes failed")
+        meshes, rows = np.zeros(nm.value, dtype=abi.EMITTER_MESH_DT), np.zeros(nr.value, dtype=abi.EMITTER_ROW_DT)
+        host_lib().rth_scene_emitter_meshes(self._h, meshes.ctypes.data, nm.value, C.byref(nm), rows.ctypes.data, nr.value, C.byref(nr))
+        return meshes, rows
     def desc(self, env=None):
         d = abi.SceneDesc()
         host_lib().rth_scene_desc(self._h, env._h if env is not None else None, C.byref(d))

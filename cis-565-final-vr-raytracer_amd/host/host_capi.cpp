@@ -92,6 +92,20 @@ uint32_t rth_scene_light_sources(void* s, rt_light_source* out, uint32_t cap)
     return uint32_t(v.size());
   } catch(...) { return 0u; }
 }
+// Scene::emitterMeshes: writes the counts; copies min(cap, count) entries of each list (either output may be NULL with cap 0: the counts alone)
+int rth_scene_emitter_meshes(void* s, rt_emitter_mesh* meshes, uint32_t meshCap, uint32_t* numMeshes, rt_emitter_row* rows, uint32_t rowCap, uint32_t* numRows)
+{
+  try {
+    std::vector<rt_emitter_mesh> m;
+    std::vector<rt_emitter_row> r;
+    static_cast<Scene*>(s)->emitterMeshes(m, r);
+    *numMeshes = uint32_t(m.size()); *numRows = uint32_t(r.size());
+    const size_t nm = std::min<size_t>(m.size(), meshCap), nr = std::min<size_t>(r.size(), rowCap);
+    if(meshes && nm) memcpy(meshes, m.data(), nm * sizeof(rt_emitter_mesh));
+    if(rows && nr) memcpy(rows, r.data(), nr * sizeof(rt_emitter_row));
+    return 0;
+  } catch(...) { return -1; }
+}
 void rth_scene_desc(void* s, void* env, rt_scene_desc* out) { *out = static_cast<Scene*>(s)->getDesc(static_cast<HdrSampling*>(env)); }
 
 void* rth_env_create() { return new(std::nothrow) HdrSampling(); }

@@ -249,6 +249,28 @@ std::vector<rt_light_source> Scene::lightSources() const
   return out;
 }
 
+void Scene::emitterMeshes(std::vector<rt_emitter_mesh>& meshes, std::vector<rt_emitter_row>& rows) const
+{
+  const GltfScene& g = m_gltf;
+  meshes.clear(); rows.clear();
+  for(size_t m = 0; m < g.primMeshes.size(); m++) {   // the light rule, the loop bound and the texcoords of createTrigLightBuffer, per prim mesh
+    const GltfPrimMesh& pm = g.primMeshes[m];
+    if(pm.materialIndex < 0 || !(luminance(g.materials[size_t(pm.materialIndex)].emissiveFactor) > 1e-2f)) continue;
+    rt_emitter_mesh em{uint32_t(m), uint32_t(rows.size()), 0u, 0u};
+    for(uint32_t idx = pm.firstIndex; idx + 1 < pm.firstIndex + pm.indexCount && idx + 2 < pm.firstIndex + pm.indexCount; idx += 3) {  // (quirk 11; a partial last triangle has no template row)
+      rt_emitter_row r{};
+      r.triangle = (idx - pm.firstIndex) / 3u;
+      for(int k = 0; k < 3; k++) {
+        const uint32_t v = g.indices[idx + k] + pm.vertexOffset;
+        r.uv[2 * k] = g.texcoords0[v][0]; r.uv[2 * k + 1] = g.texcoords0[v][1];
+      }
+      rows.push_back(r);
+    }
+    em.rowCount = uint32_t(rows.size()) - em.firstRow;
+    meshes.push_back(em);
+  }
+}
+
 void Scene::updateCamera(int width, int height)  // scene.cpp:777-795
 {
   const float aspect = float(width) / float(height);

@@ -102,6 +102,10 @@ class Scene {
   // sources[k].triangle (index-list position / 3, relative to the prim mesh) of node = instance sources[k].instance.  rt_set_light_sources takes the list; the
   // update calls then move the records with the geometry on the device, and updateInstances / updateVertices + rt_update_lights are no longer needed for emitters.
   std::vector<rt_light_source> lightSources() const;
+  // The emitter templates (include/rt_abi.h "Emitters"): one entry per emissive prim mesh that has a material (the light rule of createTrigLightBuffer), its rows
+  // the mesh's triangles ascending with the raw texcoords of their vertices, under createTrigLightBuffer's loop bound.  With them rt_set_emitter_meshes derives, for
+  // any instance table, the records setInstances computes; m_puncLightWeight is the call's last argument.
+  void emitterMeshes(std::vector<rt_emitter_mesh>& meshes, std::vector<rt_emitter_row>& rows) const;
 
   float m_puncLightWeight = 0.f, m_trigLightWeight = 0.f;  // scene.hpp:79-80
   rt_light_buf_info m_lightBufInfo{};                      // scene.hpp:113 (zero-initialised here: quirk 10)

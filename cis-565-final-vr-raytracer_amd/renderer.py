@@ -26,7 +26,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_instances", "rt_get_instances_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
-               "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats",
+               "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats", "rt_set_emitter_meshes", "rt_get_emitter_stats",
                "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
@@ -155,6 +155,9 @@ def hip_lib():
             L.rt_set_light_sources.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
             L.rt_lights_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
             L.rt_get_light_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_emitter_meshes"):   # emitters (absent from older A/B libraries)
+            L.rt_set_emitter_meshes.argtypes = abi.SET_EMITTER_MESHES_ARGTYPES
+            L.rt_get_emitter_stats.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "rt_set_morph_targets"):   # morph targets (absent from older A/B libraries)
             L.rt_set_morph_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
             L.rt_update_morphs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -622,6 +625,21 @@ class Renderer:
     def light_stats(self):
         s = abi.LightStats()
         self._chk(hip_lib().rt_get_light_stats(self._h, C.byref(s)), "rt_get_light_stats")
+        return s
+
+    # ---- emitters (include/rt_abi.h "Emitters")
+    def set_emitter_meshes(self, meshes=None, rows=None, punc_light_weight=0.0):
+        """rt_set_emitter_meshes: meshes / rows = abi.EMITTER_MESH_DT / abi.EMITTER_ROW_DT records (host.Scene.emitterMeshes()), punc_light_weight = the scene's
+        punctual weight (host.Scene.lightWeights[0]).  Switches the emitter mode on: set_instances then derives the triangle-light records of the new table on the
+        GPU, so emissive instances may be added and removed.  No meshes: switches it off"""
+        m = np.zeros(0, abi.EMITTER_MESH_DT) if meshes is None else np.ascontiguousarray(meshes, dtype=abi.EMITTER_MESH_DT).reshape(-1)
+        r = np.zeros(0, abi.EMITTER_ROW_DT) if rows is None else np.ascontiguousarray(rows, dtype=abi.EMITTER_ROW_DT).reshape(-1)
+        self._chk(hip_lib().rt_set_emitter_meshes(self._h, m.size, m.ctypes.data if m.size else None, r.size, r.ctypes.data if r.size else None,
+                                                  C.c_float(punc_light_weight)), "rt_set_emitter_meshes")
+
+    def emitter_stats(self):
+        s = abi.EmitterStats()
+        self._chk(hip_lib().rt_get_emitter_stats(self._h, C.byref(s)), "rt_get_emitter_stats")
         return s
 
     # ---- object motion vectors (include/rt_abi.h "Object motion vectors", DESIGN.md §20)

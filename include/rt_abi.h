@@ -842,8 +842,8 @@ int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
  *   mesh, and a call that makes templates 80 bytes per triangle of the meshes concerned.
  *   Failure: an allocation that fails (RT_ERR_OOM), a tree deeper than the traversal stack (RT_ERR_INVALID_ARG), a HIP error or a builder invariant (RT_ERR_HIP)
  *   leave the previous instance table, tree, record table and refit state in place and usable.
- *   Not done: rt_mgpu_* contexts and the row-tiled hosts (they upload the new scene); emissive instances added, removed or re-indexed; new prim meshes or
- *   triangles; event-ordered instead of drained updates; SAH / spatial splits on the device (DESIGN.md §19's frame cost applies until a host build).
+ *   Not done: rt_mgpu_* contexts and the row-tiled hosts (they upload the new scene); new prim meshes or
+ *   triangles (emissive instances added, removed or re-indexed: the emitter mode, "Emitters" below); event-ordered instead of drained updates; SAH / spatial splits on the device (DESIGN.md §19's frame cost applies until a host build).
  * rt_get_instances_stats: what the last rt_set_instances that succeeded did.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -1040,6 +1040,67 @@ int rt_set_light_sources(rt_ctx* ctx, uint32_t numTrig, const rt_light_source* s
 int rt_lights_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
 int rt_get_light_stats(rt_ctx* ctx, rt_light_stats* out);
 /* ------------------------------------------------------------------------------------------------------------------
+ * Emitters (added within ABI 2.4, no version bump; csrc/light_derive.hip).  rt_set_instances refuses an emissive instance that is added, removed or
+ * re-indexed (the emitter rule above), because the number of triangle-light records is fixed by rt_upload_scene: a lamp can be switched on only by a new scene.
+ * In the EMITTER MODE (opt-in, default off) the context DERIVES the triangle-light records from the instance table, so rt_set_instances may add and remove
+ * emitters.  With the mode off every call behaves exactly as without this section, the emitter rule and its messages included.
+ * Why the host hands over templates: a record's uv0..uv2 are the RAW texcoords of its vertices, while the device vertex rows carry the tangent's handedness in the
+ * LSB of texcoord.y; the raw bit is not on the device.  So the host hands the raw texcoords over once per emissive prim mesh: the TEMPLATE of the mesh, a list of
+ * rows {triangle, uv0, uv1, uv2}, in the sense of the alpha templates of rt_set_instances.
+ *
+ * The derived list of an instance table: walk the instances in index order; for every instance whose prim mesh has a template, emit the template's rows in
+ *   template order.  (The host Scene's createTrigLightBuffer order when the template lists the triangles ascending; the host owns the loop bound of that function.)
+ *   The record of (instance i, row r): matIndex = the prim mesh's materialIndex; transformIndex = 0xffffffff; v_k = xformPointRaw(objectToWorld_i,
+ *   position[indices[firstIndex + 3 r.triangle + k] + vertexOffset]), the expression of "Light sources" above (fp32, no contraction); uv0 uv1 uv2 = r.uv; pad = 0;
+ *   impSamp from the alias table of the list.  The binding entry of the record is {i, r.triangle}.
+ *   Alias table: made on the CPU inside the library (Vose's construction is sequential and its weights do not depend on geometry): the weight of a record is
+ *   luminance(emissiveFactor) of its material, `total` is the fp32 sum of the weights in record order, the table is the host Scene's construction
+ *   (host/alias_table.hpp, the same code), impSamp = {failId, prob, w / total, w[failId] / total}.  lightInfo.trigLightSize = the length of the list;
+ *   lightInfo.trigSampProb = total / (total + puncLightWeight) when the list or the punctual lights are not empty, and keeps its value otherwise.
+ *
+ * rt_set_emitter_meshes(ctx, numMeshes, meshes, numRows, rows, puncLightWeight), numMeshes > 0: switches the mode on (or replaces the templates while it is on).
+ *   meshes[m] = {primMesh, firstRow, rowCount, reserved}: the template of primMesh is rows[firstRow .. firstRow + rowCount); puncLightWeight: the summed weight of
+ *   the punctual lights (the host Scene's m_puncLightWeight; 0 without punctual lights).  Valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise).
+ *   The call derives ALL records of the CURRENT instance table into scratch memory with the kernel every later call uses and compares all 96 bytes of every
+ *   record, the count and trigSampProb with the device's: a difference refuses the call and rt_last_error names the first differing record.  So switching the mode
+ *   on never changes a bit of a consistent scene; a host whose records went stale calls rt_update_lights first.  On success the derived (instance, triangle) list
+ *   becomes the light-source binding (rt_get_light_stats.bound = the count; a binding set before is replaced): rt_update_instances, rt_update_vertices,
+ *   rt_update_skins and rt_update_morphs move the records of emitters, spawned ones included, through the refit tail of "Light sources".
+ *   Refusals (RT_ERR_INVALID_ARG, nothing changed): NULL meshes, or NULL rows with numRows > 0; a prim mesh out of range or listed twice; a prim mesh that is not
+ *   emissive by the scene's light rule (luminance of its material's emissiveFactor > 1e-2) or that has no material; an emissive prim mesh that has an instance
+ *   but no template; a row range outside rows; a row whose triangle is >= indexCount / 3 of its mesh; a non-finite uv; a non-finite or negative
+ *   puncLightWeight; derived records that differ from the device's.
+ * rt_set_emitter_meshes(ctx, 0, NULL, 0, NULL, any): switches the mode off.  Records, binding and lightInfo stay as they are; the emitter rule applies again.
+ * rt_set_instances while the mode is on: the emitter rule is replaced by "every emissive prim mesh the new table uses has a template" (RT_ERR_INVALID_ARG, the
+ *   message names the first instance without one).  The call derives the records, the binding, the alias table and lightInfo of the new table; a list of zero
+ *   records is valid, and so is going from zero records back to some.  Records and binding are written to spare buffers by k_light_expand on the main stream,
+ *   after the new instance rows are in place, and swapped together with lightInfo and the tree on success: every failure of rt_set_instances leaves the previous
+ *   lights in place.  There are two sets of light buffers; the one a call writes is allocated with 1/8 slack over its record and emitting-instance counts when it
+ *   is absent or too small (rt_emitter_stats.reallocated = 1).
+ *   Bus traffic beyond rt_set_instances' own: records * 16 + (2 * emittingInstances + 1) * 4 bytes: the alias entries, one prefix word per emitting instance plus
+ *   one, and one instance id per emitting instance.  No vertex, texcoord or position crosses the bus.
+ * Other calls while the mode is on: rt_set_light_sources is refused (RT_ERR_INVALID_ARG: the binding is derived).  rt_update_lights works with the CURRENT counts
+ *   (the next rt_set_instances derives the records anew; a changed punctual weight is handed over by rt_set_emitter_meshes).  rt_set_skins and rt_set_morph_targets
+ *   accept an emissive mesh, as with a binding.  rt_upload_scene drops the mode and the templates; rt_build_accel, rt_rebuild_accel and rt_resize keep them.  The
+ *   reference-mode sums reset as rt_set_instances resets them.  Direct-light reservoirs hold Li / wi / dist of their sample, not a light index, so no history plane
+ *   names a record: a lamp that was removed fades through ReSTIR's own lag, one frame with the temporal pass.
+ *   Scope: the single-GPU context only.  rt_mgpu_* contexts, rt_run_stage hosts and restir_amd/tiled.py are unchanged.  Punctual lights stay the host's business.
+ * rt_get_emitter_stats: the mode, and what the last rt_set_emitter_meshes / rt_set_instances that succeeded with the mode on did to the lights.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct { uint32_t primMesh, firstRow, rowCount, reserved; } rt_emitter_mesh;   /* 16 B */
+typedef struct { uint32_t triangle; float uv[6]; uint32_t pad; } rt_emitter_row;       /* 32 B: uv0 uv1 uv2 */
+typedef struct {
+  uint32_t enabled;            /* 1: the emitter mode is on */
+  uint32_t records;            /* triangle-light records after the call */
+  uint32_t emittingInstances;  /* instances of the table whose prim mesh has a template */
+  uint32_t bytesUploaded;      /* light bytes the call moved host -> device (switching on: the templates, 32 B per row + 4 B per prim mesh, and the formula above) */
+  uint32_t reallocated;        /* 1: the light buffers the call wrote were absent or too small and were allocated */
+  float    expandMs;           /* HIP-event time of k_light_expand in that call */
+  uint32_t reserved[2];
+} rt_emitter_stats;            /* 32 B */
+int rt_set_emitter_meshes(rt_ctx* ctx, uint32_t numMeshes, const rt_emitter_mesh* meshes, uint32_t numRows, const rt_emitter_row* rows, float puncLightWeight);
+int rt_get_emitter_stats(rt_ctx* ctx, rt_emitter_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
  * Morph targets (added within ABI 2.4, no version bump; csrc/morph.hip).  glTF's second deformation mechanism (blend shapes: faces, correctives,
  * cloth presets) on the GPU: a prim mesh has a SET of targets, a target is a plane of position deltas (plus, optionally, a plane of normal deltas and one of
  * tangent deltas), and a pose is one weight per target.  rt_set_morph_targets uploads the deltas once; rt_update_morphs takes weights, re-poses the meshes from
@@ -1154,6 +1215,7 @@ static_assert(sizeof(rt_deform_stats) == 32, "rt_deform_stats");
 static_assert(sizeof(rt_skin_influence) == 24, "rt_skin_influence");
 static_assert(sizeof(rt_light_source) == 8, "rt_light_source");
 static_assert(sizeof(rt_light_stats) == 32, "rt_light_stats");
+static_assert(sizeof(rt_emitter_mesh) == 16 && sizeof(rt_emitter_row) == 32 && sizeof(rt_emitter_stats) == 32, "rt_emitter_mesh / _row / _stats");
 static_assert(sizeof(rt_morph_set) == 16, "rt_morph_set");
 static_assert(sizeof(rt_morph_delta) == 16, "rt_morph_delta");
 static_assert(sizeof(rt_morph_stats) == 32, "rt_morph_stats");
