@@ -72,6 +72,31 @@ def world_bounds(desc, i):
     return w.min(axis=0), w.max(axis=0)
 
 
+# ---- rays for the comparisons of an edited context with a fresh one
+def make_rays(desc, ids, n, seed):
+    """n rays (origin, direction, tmax, a random word) over the scene, half of them through the boxes of the instances `ids`"""
+    rng = np.random.default_rng(seed)
+    inst = instances_of(desc)
+    lo = np.min([world_bounds(desc, i)[0] for i in range(len(inst))], axis=0)
+    hi = np.max([world_bounds(desc, i)[1] for i in range(len(inst))], axis=0)
+    c, rad = 0.5 * (lo + hi), 0.5 * np.linalg.norm(hi - lo)
+    target = lo + rng.random((n, 3)) * (hi - lo)
+    for k in range(n // 2):      # half of the rays through the moved instances' new boxes
+        a, b = world_bounds(desc, ids[k % len(ids)])
+        target[k] = a + rng.random(3) * (b - a)
+    d = rng.normal(size=(n, 3))
+    origin = c + 1.5 * rad * d / np.linalg.norm(d, axis=1, keepdims=True)
+    inside = rng.random(n) < 0.25
+    origin[inside] = lo + rng.random((int(inside.sum()), 3)) * (hi - lo)
+    dirs = target - origin
+    dist = np.linalg.norm(dirs, axis=1, keepdims=True)
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:3], rays[:, 3:6] = origin, dirs / dist
+    rays[:, 6] = (dist[:, 0] * rng.uniform(0.3, 2.0, n)).astype(np.float32)
+    rays[:, 7] = rng.integers(0, 2 ** 32, n, dtype=np.uint32).view(np.float32)
+    return rays
+
+
 # ---- moves: 3 x 4 row-major matrices applied in world space on top of an instance's matrix
 def compose(a, b):
     """a . b for two 3 x 4 affine matrices (12 floats each), rounded to float32"""

@@ -92,27 +92,7 @@ def test_device_tree_equals_the_checker_word_for_word(lib, name):
 
 
 # ---- rays: the updated context against a fresh context that uploaded and built the moved scene ----------------------------------------------------------------
-def make_rays(desc, ids, n, seed):
-    rng = np.random.default_rng(seed)
-    inst = refit.instances_of(desc)
-    lo = np.min([refit.world_bounds(desc, i)[0] for i in range(len(inst))], axis=0)
-    hi = np.max([refit.world_bounds(desc, i)[1] for i in range(len(inst))], axis=0)
-    c, rad = 0.5 * (lo + hi), 0.5 * np.linalg.norm(hi - lo)
-    target = lo + rng.random((n, 3)) * (hi - lo)
-    for k in range(n // 2):      # half of the rays through the moved instances' new boxes
-        a, b = refit.world_bounds(desc, ids[k % len(ids)])
-        target[k] = a + rng.random(3) * (b - a)
-    d = rng.normal(size=(n, 3))
-    origin = c + 1.5 * rad * d / np.linalg.norm(d, axis=1, keepdims=True)
-    inside = rng.random(n) < 0.25
-    origin[inside] = lo + rng.random((int(inside.sum()), 3)) * (hi - lo)
-    dirs = target - origin
-    dist = np.linalg.norm(dirs, axis=1, keepdims=True)
-    rays = np.zeros((n, 8), np.float32)
-    rays[:, 0:3], rays[:, 3:6] = origin, dirs / dist
-    rays[:, 6] = (dist[:, 0] * rng.uniform(0.3, 2.0, n)).astype(np.float32)
-    rays[:, 7] = rng.integers(0, 2 ** 32, n, dtype=np.uint32).view(np.float32)
-    return rays
+make_rays = refit.make_rays      # (lives in tests/refit.py: the CPU tests aim the same rays without importing this module)
 
 
 @pytest.mark.parametrize("name", ["cornell", "street"])
