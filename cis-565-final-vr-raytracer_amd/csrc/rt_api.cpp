@@ -21,6 +21,7 @@
 #include "bvh8_builder.h"
 #include "stages.h"
 #include "primary_replay.h"
+#include "parity_history.h"
 #include "reference.h"
 #include "svgf.h"
 #include "gi_spatial.h"
@@ -63,9 +64,12 @@ struct rt_ctx {
   void* dSky = nullptr;      // SkyPre (csrc/sky.h), valid while sunAndSky.in_use == 1
   void* dPick = nullptr;     // rt_pick_result written by k_pick
   rt_sun_and_sky sunAndSky{};
-  void* spareG = nullptr; void* spareMotion = nullptr;   // third G-buffer / second motion buffer (rotated per pipelined frame)
-  // overlap 3 (three frames in flight): one more of each, and a third noisy / filtered direct image — direct(f) then only waits for frame f-3 (rt_render_frame)
-  void* spareG2 = nullptr; void* spareMotion2 = nullptr; void* spareDirRes = nullptr;
+  // The ring of frames in flight: per rotated kind, the buffers that wait beside the live one (ringLive), next one first.  Overlap 2 swaps the live G-buffer and
+  // motion buffer with their first spare (third G-buffer / second motion buffer, rotated per pipelined frame); overlap 3 (three frames in flight) shifts through
+  // both spares and also rotates the noisy / filtered direct image, which has one spare — direct(f) then only waits for frame f-3 (rt_render_frame).  The
+  // instance and delta images of rt_set_object_motion rotate with the motion buffer.
+  enum Ring { RING_G, RING_MOTION, RING_DIRECT, RING_INST, RING_DELTA, RING_KINDS };
+  void* spare[RING_KINDS][2] = {};
   // The noisy indirect colour (RT_BUF_DENOISE_IND_A: written by the indirect stage, read and rewritten by its five filter levels) exists twice, by frame parity:
   // indirect(f+1) must not wait for the filters of frame f (round 3: that wait made a rank's period indirect + filters instead of max(direct, indirect)).
   // The boundary id names the buffer of the frame most recently passed to rt_render_frame / rt_run_stage / rt_select_frame.
@@ -115,36 +119,29 @@ struct rt_ctx {
   uint32_t refN = 0;           // samples in refAcc; 0 = the sums are stale and are cleared by the next rt_reference_render
   bool refKeyValid = false;    // the RtxState inputs of the integral the sums were taken with (the others reset refN where they change)
   int32_t refMaxDepth = 0, refMIS = 0; float refHdrMultiplier = 0.f, refEnvironmentProb = 0.f;
+  // The history of a temporal pass: its planes by frame parity (up to four per parity) and, next to them, the host state that says what they are worth.
+  // Frame f reads parity f-1 and writes parity f; when it may is parity_history.h's rule.
+  struct History { void* plane[2][4] = {}; rt::ParityHistory state; };
   // rt_set_denoiser (csrc/svgf.hip).  SVGF history: [frame parity][direct colour + n, indirect colour + n, direct moments, indirect moments], allocated by the
-  // first frame rendered in SVGF mode, freed by rt_resize / rt_destroy.  Frame f reads parity (f + 1) & 1 and writes f & 1.
+  // first frame rendered in SVGF mode, freed by rt_resize / rt_destroy.
   rt_denoiser den{RT_DENOISER_ATROUS, 0.2f, 0.2f, 32, 4.0f, 4.0f, {0, 0}};
-  void* svgfHist[2][4] = {};
-  bool svgfValid = false;    // the history of parity svgfParity may be read by the next frame (host-side, consumed when a frame is enqueued)
-  int svgfParity = -1;       // parity of the last SVGF frame (-1: none since the history was allocated)
+  History histSvgf;
   // rt_set_gi_spatial (csrc/gi_spatial.hip).  The pass's reservoirs, allocated by the first frame rendered with the mode on, freed by rt_resize / rt_destroy.
   rt_gi_spatial gis{RT_GI_SPATIAL_OFF, 4, 10, 0.9f, 0.1f, 10.0f, {0, 0}};
   void* gisResv = nullptr;
   bool gisWritten = false;   // a frame with the mode on has been enqueued since gisResv was allocated
   // rt_set_taa (csrc/taa.hip).  History: [frame parity][direct, indirect, n], allocated by the first frame rendered with the mode on, freed by rt_resize /
-  // rt_destroy.  Frame f reads parity (f + 1) & 1 and writes f & 1.
+  // rt_destroy.
   rt_taa taa{RT_TAA_OFF, 8, 0.1f, 1.0f, {0, 0, 0, 0}};
-  void* taaHist[2][3] = {};
-  bool taaValid = false;     // the history of parity taaLast may be read by the next frame (host-side, consumed when a frame is enqueued)
-  int taaLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
-  bool taaHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame taaFrame[parity] (rt_tonemap)
-  int taaFrame[2] = {0, 0};
+  History histTaa;
   // rt_set_upscale (csrc/upscale.hip).  History at the output size: [frame parity][direct, indirect, n], allocated by the first resolved frame
   // together with the output-size RGBA8 target and the tonemap's scratch (row sums, means, mip pyramids), freed by rt_resize / rt_destroy / an rt_set_upscale
-  // that changes the output size.  Frame f reads parity (f + 1) & 1 and writes f & 1.  The fields mirror TAA's.
+  // that changes the output size.
   rt_upscale ups{RT_UPSCALE_OFF, 0, 0, 16, 0.1f, 1.0f, {0, 0}};
-  void* upsHist[2][3] = {};
-  int upsW = 0, upsH = 0;    // the output size upsHist was allocated for
+  History histUps;
+  int upsW = 0, upsH = 0;    // the output size histUps was allocated for
   void* upsLdr = nullptr; double* upsRowSums = nullptr; float* upsMean = nullptr; float4* upsMipD = nullptr; float4* upsMipI = nullptr;
   bool upsLdrWritten = false;
-  bool upsValid = false;     // the history of parity upsLast may be read by the next frame (host-side, consumed when a frame is enqueued)
-  int upsLast = -1;          // parity of the last resolved frame (-1: none since the history was allocated)
-  bool upsHeld[2] = {false, false};   // the history of this parity holds the resolved images of frame upsFrame[parity] (rt_upscale_tonemap)
-  int upsFrame[2] = {0, 0};
   // rt_update_instances (csrc/refit.hip).  Made by the first update after a build from the device tree (ensureRefitState) and dropped with the tree: the record -> node
   // map, the contiguous node range of every level, per instance its largest |world coordinate| (the pad is a reduction over instances) and its handedness.
   // The device arrays live in accelAllocs.
@@ -260,7 +257,7 @@ struct rt_ctx {
   bool omPending = false;    // some omMoved flag is set
   // the instance image (lifetime of RT_BUF_MOTION: rotated with it) and the per-instance camera table (rewritten only by frames with motion, which follow the
   // drain of rt_update_instances, so one copy serves the frames in flight); allocated once the mode has been switched on
-  void* omInst = nullptr; void* omInstSpare = nullptr; void* omInstSpare2 = nullptr;
+  void* omInst = nullptr;    // (its ring partners: spare[RING_INST])
   bool omInstValid = false;  // a frame has written omInst since rt_resize
   void* omTable = nullptr; size_t omTableRows = 0;
   std::vector<OmCamera> omHost;
@@ -272,7 +269,7 @@ struct rt_ctx {
   void* vmPlane = nullptr;
   std::vector<uint8_t> vmDeformed;
   bool vmPending = false;    // some vmDeformed flag is set
-  void* vmDelta = nullptr; void* vmDeltaSpare = nullptr; void* vmDeltaSpare2 = nullptr;
+  void* vmDelta = nullptr;   // (its ring partners: spare[RING_DELTA])
   bool vmDeltaValid = false; // a vertex-mode frame has written vmDelta since rt_resize
   void* vmTable = nullptr; size_t vmTableRows = 0;
   std::vector<VmRow> vmHost;
@@ -484,11 +481,89 @@ static void buildOpacityMap(const AlphaRec& a, const std::vector<uint8_t>* alpha
 }
 
 static int fail(rt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
-// the SVGF history (the caller has drained the context)
-static void freeSvgfHistory(rt_ctx* c)
+// a device buffer of at least 256 bytes with every byte set to `fill` (on the null stream: the caller synchronises the device before its streams touch it)
+static hipError_t mallocFilled(void** p, size_t bytes, int fill)
 {
-  for(auto& par : c->svgfHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
-  c->svgfValid = false; c->svgfParity = -1;
+  bytes = std::max<size_t>(bytes, 256);
+  const hipError_t e = hipMalloc(p, bytes);
+  if(e != hipSuccess) { *p = nullptr; return e; }
+  return hipMemset(*p, fill, bytes);
+}
+// the planes of a temporal pass's history (the caller has drained the context)
+static void freeHistory(rt_ctx::History& h)
+{
+  for(auto& par : h.plane) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
+  h.state.reset();
+}
+// Both parities of the history of `pass`, one plane per entry of `bytes` (rt_render_frame's first frame with the pass on; the caller has drained the context).
+// Zeroed: nothing reads a plane before a frame wrote it.  All or nothing.
+static int allocHistory(rt_ctx* c, rt_ctx::History& h, std::initializer_list<size_t> bytes, const char* pass)
+{
+  bool ok = true;
+  for(auto& par : h.plane) {
+    void** p = par;
+    for(size_t b : bytes) ok = ok && mallocFilled(p++, b, 0) == hipSuccess;
+  }
+  if(!ok) { freeHistory(h); c->err = std::string("rt_render_frame: hipMalloc of the ") + pass + " history failed"; return RT_ERR_OOM; }
+  RT_HIP(c, hipDeviceSynchronize());
+  h.state.reset();
+  return RT_OK;
+}
+// The arguments of the resolve of frame `frames` that TAA and temporal upsampling share (TaaArgs / UpscaleArgs): the frame's images and G-buffers, the
+// history planes [direct, indirect, n] the pass reads and writes, and the pass's settings.
+template <class Args, class Settings> static Args resolveArgs(const rt_ctx* c, const rt_ctx::History& h, const Settings& s, const DevFrame& F, int frames, bool histValid)
+{
+  Args A{};
+  void* const* cur = h.plane[rt::frameParity(frames)]; void* const* prev = h.plane[rt::otherParity(frames)];
+  A.thisG = F.thisG; A.lastG = F.lastG;
+  A.curD = F.thisDirectResult; A.curI = F.thisIndirectResult;
+  A.prevD = static_cast<const float4*>(prev[0]); A.prevI = static_cast<const float4*>(prev[1]); A.prevN = static_cast<const float*>(prev[2]);
+  A.outD = static_cast<float4*>(cur[0]); A.outI = static_cast<float4*>(cur[1]); A.outN = static_cast<float*>(cur[2]);
+  A.W = c->W; A.H = c->H;
+  A.histValid = histValid ? 1 : 0;
+  A.alpha = s.alpha; A.clipGamma = s.clipGamma;
+  return A;
+}
+// the tail of the *_readback calls, after their own argument checks: drain the context, then copy `bytes` bytes of device memory to the host
+static int readbackDrained(rt_ctx* c, const void* src, void* dst, size_t bytes)
+{
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(bytes) RT_HIP(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+// a new scene or a new tree: the next frame of every temporal pass starts without history
+static void invalidateHistories(rt_ctx* c) { for(rt_ctx::History* h : {&c->histSvgf, &c->histTaa, &c->histUps}) h->state.invalidate(); }
+// The ring of frames in flight (rt_ctx::spare).  The live buffer of a kind for frame `frames`: the boundary ids keep their meaning across rotations.
+static void*& ringLive(rt_ctx* c, int kind, int frames)
+{
+  switch(kind) {
+    case rt_ctx::RING_G: return c->bufs[RT_BUF_GBUFFER0 + rt::frameParity(frames)];
+    case rt_ctx::RING_MOTION: return c->bufs[RT_BUF_MOTION];
+    case rt_ctx::RING_DIRECT: return c->bufs[RT_BUF_DIRECT_RESULT0 + rt::frameParity(frames)];
+    case rt_ctx::RING_INST: return c->omInst;
+    default: return c->vmDelta;
+  }
+}
+// three frames in flight: rt_set_overlap 3, and rt_resize made every buffer the deeper ring needs
+static bool ringDeep(const rt_ctx* c) { return c->overlap >= 3 && c->spare[rt_ctx::RING_G][1] && c->spare[rt_ctx::RING_MOTION][1] && c->spare[rt_ctx::RING_DIRECT][0]; }
+// one kind moves on by a frame: the two-deep swap with the first spare, or the three-deep shift (the next spare becomes live, the live buffer waits longest)
+static void rotate(void*& live, void* spare[2], bool deep)
+{
+  if(deep) { void* t = live; live = spare[0]; spare[0] = spare[1]; spare[1] = t; }
+  else std::swap(live, spare[0]);
+}
+// Every kind that exists moves on by a frame.  The direct image rotates only at three frames in flight, where its two parities and its one spare make the three.
+static void rotateRing(rt_ctx* c, int frames, bool deep)
+{
+  for(int kind = 0; kind < rt_ctx::RING_KINDS; kind++) {
+    void*& live = ringLive(c, kind, frames);
+    if(live && (kind != rt_ctx::RING_DIRECT || deep)) rotate(live, c->spare[kind], deep && kind != rt_ctx::RING_DIRECT);
+  }
+}
+static void freeSpares(rt_ctx* c, std::initializer_list<int> kinds)
+{
+  for(int kind : kinds) for(void*& p : c->spare[kind]) { if(p) (void)hipFree(p); p = nullptr; }
 }
 // the GI spatial reservoirs (the caller has drained the context)
 static void freeGiSpatial(rt_ctx* c)
@@ -500,11 +575,10 @@ static void freeGiSpatial(rt_ctx* c)
 // (the caller has drained the context)
 static void freeObjectMotion(rt_ctx* c)
 {
-  for(void** p : {&c->omInst, &c->omInstSpare, &c->omInstSpare2}) if(*p) { (void)hipFree(*p); *p = nullptr; }
-  c->omInstValid = false;
+  for(void** p : {&c->omInst, &c->vmDelta}) if(*p) { (void)hipFree(*p); *p = nullptr; }
+  freeSpares(c, {rt_ctx::RING_INST, rt_ctx::RING_DELTA});
+  c->omInstValid = c->vmDeltaValid = false;
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;
-  for(void** p : {&c->vmDelta, &c->vmDeltaSpare, &c->vmDeltaSpare2}) if(*p) { (void)hipFree(*p); *p = nullptr; }
-  c->vmDeltaValid = false;
   std::fill(c->vmDeformed.begin(), c->vmDeformed.end(), uint8_t(0)); c->vmPending = false;   // (the plane is sized by the scene: it stays)
 }
 // The previous-position plane of per-vertex motion vectors: one float4 per vertex of the uploaded scene, zeroed (a row is read only after a capture wrote it).
@@ -529,20 +603,13 @@ static int capturePrevPositions(rt_ctx* c, hipStream_t s, uint32_t mesh)
   c->vmDeformed[mesh] = 1; c->vmPending = true;
   return RT_OK;
 }
-// the TAA history (the caller has drained the context)
-static void freeTaaHistory(rt_ctx* c)
-{
-  for(auto& par : c->taaHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
-  c->taaValid = false; c->taaLast = -1; c->taaHeld[0] = c->taaHeld[1] = false;
-}
 // the upsampling history and what rt_upscale_tonemap needs at the output size (the caller has drained the context)
 static void freeUpscaleHistory(rt_ctx* c)
 {
-  for(auto& par : c->upsHist) for(void*& p : par) { if(p) (void)hipFree(p); p = nullptr; }
+  freeHistory(c->histUps);
   for(void* p : {c->upsLdr, static_cast<void*>(c->upsRowSums), static_cast<void*>(c->upsMean), static_cast<void*>(c->upsMipD), static_cast<void*>(c->upsMipI)}) if(p) (void)hipFree(p);
   c->upsLdr = nullptr; c->upsRowSums = nullptr; c->upsMean = nullptr; c->upsMipD = c->upsMipI = nullptr;
   c->upsW = c->upsH = 0; c->upsLdrWritten = false;
-  c->upsValid = false; c->upsLast = -1; c->upsHeld[0] = c->upsHeld[1] = false;
 }
 
 // Stream priorities of the frames-in-flight schedule.  RESTIR_PRIO = 0..3 (rounds 2-4: 0 none, 1 indirect + filter streams high, 2 indirect stream high — the
@@ -687,13 +754,12 @@ int rt_destroy(rt_ctx* c)
   freePool(c->skinAllocs); freePool(c->deformAllocs); freePool(c->lightAllocs); freePool(c->morphAllocs); freePool(c->instAllocs);
   dropEmitters(c);
   for(int i = 0; i < RT_BUF_COUNT; i++) if(c->bufs[i]) (void)hipFree(c->bufs[i]);
-  for(void* p : {c->spareG, c->spareMotion, c->spareG2, c->spareMotion2, c->spareDirRes, c->omInst, c->omInstSpare, c->omInstSpare2, c->omTable, c->vmPlane, c->vmDelta, c->vmDeltaSpare,
-                  c->vmDeltaSpare2, c->vmTable}) if(p) (void)hipFree(p);
+  freeSpares(c, {rt_ctx::RING_G, rt_ctx::RING_MOTION, rt_ctx::RING_DIRECT, rt_ctx::RING_INST, rt_ctx::RING_DELTA});
+  for(void* p : {c->omInst, c->omTable, c->vmPlane, c->vmDelta, c->vmTable}) if(p) (void)hipFree(p);
   for(void* p : c->indA) if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p);
   for(hipStream_t& q : c->indStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
   for(hipStream_t& q : c->sideStreams) { if(q) (void)hipStreamDestroy(q); q = nullptr; }
-  c->indStream = c->sideStream = nullptr;
-  if(c->indStream) (void)hipStreamDestroy(c->indStream);
+  c->indStream = c->sideStream = nullptr;   // (the per-level arrays own the streams)
   for(int i = 0; i < 4; i++) { if(c->evD[i]) (void)hipEventDestroy(c->evD[i]); if(c->evI[i]) (void)hipEventDestroy(c->evI[i]); if(c->evDone[i]) (void)hipEventDestroy(c->evDone[i]); }
   if(c->dCounters) (void)hipFree(c->dCounters);
   freeVis(c);
@@ -701,13 +767,12 @@ int rt_destroy(rt_ctx* c)
   if(c->dPick) (void)hipFree(c->dPick);
   if(c->refAcc) (void)hipFree(c->refAcc);
   if(c->refMean) (void)hipFree(c->refMean);
-  freeSvgfHistory(c);
+  freeHistory(c->histSvgf);
   freeGiSpatial(c);
-  freeTaaHistory(c);
+  freeHistory(c->histTaa);
   freeUpscaleHistory(c);
   for(auto& E : c->evSets) for(int i = 0; i < rt_ctx::MAX_EV; i++) (void)hipEventDestroy(E.ev[i]);
   if(c->ownStream) (void)hipStreamDestroy(c->ownStream);
-  if(c->sideStream) (void)hipStreamDestroy(c->sideStream);
   if(c->evFork) (void)hipEventDestroy(c->evFork);
   if(c->evJoin) (void)hipEventDestroy(c->evJoin);
   for(hipEvent_t e : c->evRefit) if(e) (void)hipEventDestroy(e);
@@ -803,9 +868,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   c->rebuild = rt_ctx::Rebuild{};
   c->haveScene = c->haveAccel = false;
   c->refN = 0;   // a new scene: the reference sums start again
-  c->svgfValid = false;
-  c->taaValid = false;
-  c->upsValid = false;
+  invalidateHistories(c);
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // object motion: nothing of the new scene has moved
   if(c->vmPlane) { (void)hipFree(c->vmPlane); c->vmPlane = nullptr; }   // ... or has been deformed; the plane is made again for the new vertex array below
   c->vmDeformed.clear(); c->vmPending = false;
@@ -1015,9 +1078,7 @@ int rt_build_accel(rt_ctx* c)
   c->rebuild = rt_ctx::Rebuild{};
   c->haveAccel = false;
   c->refN = 0;
-  c->svgfValid = false;
-  c->taaValid = false;
-  c->upsValid = false;
+  invalidateHistories(c);
   // Host products (BVH8, alpha records, opacity micro-maps): built once per distinct scene in this process and shared by every context that uploads
   // the same scene — the N ranks of an rt_mgpu context, or an application's contexts on several devices (1.4-1.6 s per build at 2.8 M triangles).
   std::shared_ptr<const HostAccel> ha;
@@ -1081,13 +1142,13 @@ int rt_resize(rt_ctx* c, int w, int h)
   reopenPriorityDecision(c);
   for(void*& p : c->indA) { if(p && p != c->bufs[RT_BUF_DENOISE_IND_A]) (void)hipFree(p); p = nullptr; }
   for(int i = 0; i < RT_BUF_COUNT; i++) { if(c->bufs[i]) (void)hipFree(c->bufs[i]); c->bufs[i] = nullptr; c->bufBytes[i] = 0; }
-  for(void** p : {&c->spareG, &c->spareMotion, &c->spareG2, &c->spareMotion2, &c->spareDirRes}) if(*p) { (void)hipFree(*p); *p = nullptr; }
+  freeSpares(c, {rt_ctx::RING_G, rt_ctx::RING_MOTION, rt_ctx::RING_DIRECT});   // (freeObjectMotion: the other two kinds)
   c->W = c->H = 0;
   for(void* p : {static_cast<void*>(c->refAcc), static_cast<void*>(c->refMean)}) if(p) (void)hipFree(p);
   c->refAcc = nullptr; c->refMean = nullptr; c->refN = 0;
-  freeSvgfHistory(c);
+  freeHistory(c->histSvgf);
   freeGiSpatial(c);
-  freeTaaHistory(c);
+  freeHistory(c->histTaa);
   freeUpscaleHistory(c);
   freeObjectMotion(c);
   freeVis(c);
@@ -1103,16 +1164,10 @@ int rt_resize(rt_ctx* c, int w, int h)
       RT_HIP(c, hipMalloc(&c->indA[1], alloc));
       RT_HIP(c, hipMemset(c->indA[1], 0, alloc));
     }
-    if(i == RT_BUF_GBUFFER0 || i == RT_BUF_MOTION) {  // rotation partners for frames in flight (rt_render_frame, overlap 2)
-      for(void** spare : {(i == RT_BUF_MOTION) ? &c->spareMotion : &c->spareG, (i == RT_BUF_MOTION) ? &c->spareMotion2 : &c->spareG2}) {
-        RT_HIP(c, hipMalloc(spare, alloc));
-        RT_HIP(c, hipMemset(*spare, 0, alloc));
-      }
-    }
-    if(i == RT_BUF_DIRECT_RESULT0) {   // overlap 3: the direct image of frame f-3 is the one direct(f) overwrites
-      RT_HIP(c, hipMalloc(&c->spareDirRes, alloc));
-      RT_HIP(c, hipMemset(c->spareDirRes, 0, alloc));
-    }
+    // rotation partners for frames in flight (rt_render_frame, overlap 2): two of the G-buffer and of the motion buffer, and one of the direct image (overlap 3:
+    // the direct image of frame f-3 is the one direct(f) overwrites)
+    const int kind = i == RT_BUF_GBUFFER0 ? rt_ctx::RING_G : (i == RT_BUF_MOTION ? rt_ctx::RING_MOTION : (i == RT_BUF_DIRECT_RESULT0 ? rt_ctx::RING_DIRECT : -1));
+    for(int s = 0; kind >= 0 && s < (kind == rt_ctx::RING_DIRECT ? 1 : 2); s++) RT_HIP(c, mallocFilled(&c->spare[kind][s], alloc, 0));
   }
   // internal scratch
   freePool(c->scratchAllocs);
@@ -1203,26 +1258,12 @@ static void reopenPriorityDecision(rt_ctx* c)
   c->indStream = c->sideStream = nullptr;
 }
 
-// The SVGF history of both parities (rt_render_frame's first SVGF frame; the caller has drained the context).  Zeroed: nothing reads it before a frame wrote it.
-static int allocSvgfHistory(rt_ctx* c)
-{
-  const size_t n = size_t(c->W) * c->H, nh = size_t(c->W / 2) * (c->H / 2);
-  const size_t bytes[4] = {n * sizeof(float4), nh * sizeof(float4), n * sizeof(float2), nh * sizeof(float2)};
-  for(auto& par : c->svgfHist)
-    for(int k = 0; k < 4; k++) {
-      if(hipMalloc(&par[k], std::max<size_t>(bytes[k], 256)) != hipSuccess) { par[k] = nullptr; freeSvgfHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the SVGF history failed"); }
-      RT_HIP(c, hipMemset(par[k], 0, std::max<size_t>(bytes[k], 256)));
-    }
-  RT_HIP(c, hipDeviceSynchronize());
-  c->svgfValid = false; c->svgfParity = -1;
-  return RT_OK;
-}
-
 // the arguments of one SVGF chain of frame `frames` (ind: the half-resolution indirect component)
 static SvgfArgs svgfArgs(const rt_ctx* c, const DevFrame& F, const rt_state& st, int frames, bool ind, bool histValid)
 {
   SvgfArgs A{};
-  const int cur = frames & 1, prev = (frames + 1) & 1, k = ind ? 1 : 0;
+  const int k = ind ? 1 : 0;
+  void* const* cur = c->histSvgf.plane[rt::frameParity(frames)]; void* const* prev = c->histSvgf.plane[rt::otherParity(frames)];
   A.thisG = F.thisG; A.lastG = F.lastG; A.motion = F.motion;
   A.noisy = ind ? F.denoiseIndA : F.thisDirectResult;
   // the A-Trous temporaries: direct DirA <-> DirB; indirect thisIndirectResult (scratch, as in the A-Trous chain) <-> the noisy buffer, read by then
@@ -1230,8 +1271,8 @@ static SvgfArgs svgfArgs(const rt_ctx* c, const DevFrame& F, const rt_state& st,
   A.bufB = ind ? F.denoiseIndA : F.denoiseDirB;
   A.out = ind ? F.denoiseIndB : F.thisDirectResult;
   A.geomN = ind ? F.geomNh : F.geomN; A.geomP = ind ? F.geomPh : F.geomP;
-  A.prevC = static_cast<const float4*>(c->svgfHist[prev][k]); A.prevM = static_cast<const float2*>(c->svgfHist[prev][2 + k]);
-  A.histC = static_cast<float4*>(c->svgfHist[cur][k]); A.histM = static_cast<float2*>(c->svgfHist[cur][2 + k]);
+  A.prevC = static_cast<const float4*>(prev[k]); A.prevM = static_cast<const float2*>(prev[2 + k]);
+  A.histC = static_cast<float4*>(cur[k]); A.histM = static_cast<float2*>(cur[2 + k]);
   A.W = c->W; A.H = c->H;
   A.bx = ind ? c->W / 2 : c->W; A.by = ind ? c->H / 2 : c->H;
   A.histValid = histValid ? 1 : 0;
@@ -1270,93 +1311,39 @@ static GiSpatialArgs giSpatialArgs(const rt_ctx* c, const DevFrame& F)
 // The instance images of rt_set_object_motion (callers have drained the context); they start as "miss everywhere"
 static int allocObjectMotion(rt_ctx* c)
 {
-  const size_t bytes = size_t(c->W) * c->H * sizeof(uint32_t);
-  for(void** p : {&c->omInst, &c->omInstSpare, &c->omInstSpare2}) {
-    if(*p) continue;
-    RT_HIP(c, hipMalloc(p, std::max<size_t>(bytes, 256)));
-    RT_HIP(c, hipMemset(*p, 0xff, std::max<size_t>(bytes, 256)));
-  }
-  if(c->vmEver) {   // the delta images of per-vertex motion vectors: zero = "nothing moved"
-    const size_t db = std::max<size_t>(size_t(c->W) * c->H * sizeof(float4), 256);
-    for(void** p : {&c->vmDelta, &c->vmDeltaSpare, &c->vmDeltaSpare2}) {
-      if(*p) continue;
-      RT_HIP(c, hipMalloc(p, db));
-      RT_HIP(c, hipMemset(*p, 0, db));
-    }
-  }
-  RT_HIP(c, hipDeviceSynchronize());
-  return RT_OK;
-}
-// The TAA history of both parities (rt_render_frame's first frame with the mode on; the caller has drained the context).  Zeroed: nothing reads it before a
-// frame wrote it.
-static int allocTaaHistory(rt_ctx* c)
-{
   const size_t n = size_t(c->W) * c->H;
-  const size_t bytes[3] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float)};
-  for(auto& par : c->taaHist)
-    for(int k = 0; k < 3; k++) {
-      if(hipMalloc(&par[k], std::max<size_t>(bytes[k], 256)) != hipSuccess) { par[k] = nullptr; freeTaaHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the TAA history failed"); }
-      RT_HIP(c, hipMemset(par[k], 0, std::max<size_t>(bytes[k], 256)));
-    }
+  for(void** p : {&c->omInst, &c->spare[rt_ctx::RING_INST][0], &c->spare[rt_ctx::RING_INST][1]}) if(!*p) RT_HIP(c, mallocFilled(p, n * sizeof(uint32_t), 0xff));
+  if(c->vmEver)   // the delta images of per-vertex motion vectors: zero = "nothing moved"
+    for(void** p : {&c->vmDelta, &c->spare[rt_ctx::RING_DELTA][0], &c->spare[rt_ctx::RING_DELTA][1]}) if(!*p) RT_HIP(c, mallocFilled(p, n * sizeof(float4), 0));
   RT_HIP(c, hipDeviceSynchronize());
-  c->taaValid = false; c->taaLast = -1; c->taaHeld[0] = c->taaHeld[1] = false;
   return RT_OK;
 }
 
-// the arguments of the TAA resolve of frame `frames`
-static TaaArgs taaArgs(const rt_ctx* c, const DevFrame& F, int frames, bool histValid)
+// A per-instance device table of a motion-vector mode grows to `rows` rows: its readers are drained first, and the frame that asked rewrites every row.
+static int growTable(rt_ctx* c, void** table, size_t* have, size_t rows, size_t rowBytes)
 {
-  TaaArgs A{};
-  const int cur = frames & 1, prev = (frames + 1) & 1;
-  A.thisG = F.thisG; A.lastG = F.lastG;
-  A.curD = F.thisDirectResult; A.curI = F.thisIndirectResult;
-  A.prevD = static_cast<const float4*>(c->taaHist[prev][0]); A.prevI = static_cast<const float4*>(c->taaHist[prev][1]);
-  A.prevN = static_cast<const float*>(c->taaHist[prev][2]);
-  A.outD = static_cast<float4*>(c->taaHist[cur][0]); A.outI = static_cast<float4*>(c->taaHist[cur][1]); A.outN = static_cast<float*>(c->taaHist[cur][2]);
-  A.W = c->W; A.H = c->H;
-  A.histValid = histValid ? 1 : 0;
-  A.alpha = c->taa.alpha; A.clipGamma = c->taa.clipGamma;
-  return A;
+  if(*have >= rows) return RT_OK;
+  RT_HIP(c, syncAll(c));
+  if(*table) { (void)hipFree(*table); *table = nullptr; *have = 0; }
+  RT_HIP(c, hipMalloc(table, rows * rowBytes));
+  *have = rows;
+  return RT_OK;
 }
 
-// The upsampling history of both parities at the output size, the RGBA8 target and the tonemap's scratch (rt_render_frame's first frame with the mode on; the
-// caller has drained the context).  Zeroed: nothing reads it before a frame wrote it.
+// The upsampling history at the output size with the RGBA8 target and the tonemap's scratch (rt_render_frame's first frame with the mode on; the caller has
+// drained the context).  All or nothing; the history comes last, and its device synchronisation covers the rest.
 static int allocUpscaleHistory(rt_ctx* c)
 {
   const int wo = c->ups.outWidth, ho = c->ups.outHeight;
   const size_t n = size_t(wo) * ho;
-  auto get = [&](void** p, size_t bytes) -> bool {
-    bytes = std::max<size_t>(bytes, 256);
-    if(hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return false; }
-    return hipMemset(*p, 0, bytes) == hipSuccess;
-  };
-  bool ok = true;
-  const size_t bytes[3] = {n * sizeof(float4), n * sizeof(float4), n * sizeof(float)};
-  for(auto& par : c->upsHist) for(int k = 0; k < 3 && ok; k++) ok = get(&par[k], bytes[k]);
-  ok = ok && get(&c->upsLdr, n * 4) && get(reinterpret_cast<void**>(&c->upsRowSums), size_t(ho) * 6 * sizeof(double)) && get(reinterpret_cast<void**>(&c->upsMean), 8 * sizeof(float)) &&
-       get(reinterpret_cast<void**>(&c->upsMipD), (n + 64) * sizeof(float4)) && get(reinterpret_cast<void**>(&c->upsMipI), (n + 64) * sizeof(float4));   // (sized as rt_resize sizes the render-size ones)
-  if(!ok) { freeUpscaleHistory(c); return fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the upsampling history failed"); }
-  RT_HIP(c, hipDeviceSynchronize());
+  auto get = [](auto** p, size_t bytes) { return mallocFilled(reinterpret_cast<void**>(p), bytes, 0) == hipSuccess; };
+  const bool ok = get(&c->upsLdr, n * 4) && get(&c->upsRowSums, size_t(ho) * 6 * sizeof(double)) && get(&c->upsMean, 8 * sizeof(float)) &&
+                  get(&c->upsMipD, (n + 64) * sizeof(float4)) && get(&c->upsMipI, (n + 64) * sizeof(float4));   // (sized as rt_resize sizes the render-size ones)
+  const int rc = ok ? allocHistory(c, c->histUps, {n * sizeof(float4), n * sizeof(float4), n * sizeof(float)}, "upsampling")
+                    : fail(c, RT_ERR_OOM, "rt_render_frame: hipMalloc of the upsampling history failed");
+  if(rc) { freeUpscaleHistory(c); return rc; }
   c->upsW = wo; c->upsH = ho; c->upsLdrWritten = false;
-  c->upsValid = false; c->upsLast = -1; c->upsHeld[0] = c->upsHeld[1] = false;
   return RT_OK;
-}
-
-// the arguments of the upsampling resolve of frame `frames`; delta is the frame's jitter offset in render pixels
-static UpscaleArgs upscaleArgs(const rt_ctx* c, const DevFrame& F, int frames, bool histValid, const float delta[2])
-{
-  UpscaleArgs A{};
-  const int cur = frames & 1, prev = (frames + 1) & 1;
-  A.thisG = F.thisG; A.lastG = F.lastG;
-  A.curD = F.thisDirectResult; A.curI = F.thisIndirectResult;
-  A.prevD = static_cast<const float4*>(c->upsHist[prev][0]); A.prevI = static_cast<const float4*>(c->upsHist[prev][1]);
-  A.prevN = static_cast<const float*>(c->upsHist[prev][2]);
-  A.outD = static_cast<float4*>(c->upsHist[cur][0]); A.outI = static_cast<float4*>(c->upsHist[cur][1]); A.outN = static_cast<float*>(c->upsHist[cur][2]);
-  A.W = c->W; A.H = c->H; A.Wo = c->upsW; A.Ho = c->upsH;
-  A.histValid = histValid ? 1 : 0;
-  A.alpha = c->ups.alpha; A.clipGamma = c->ups.clipGamma;
-  A.dx = delta[0]; A.dy = delta[1];
-  return A;
 }
 // the ratio limits of rt_set_upscale for a render size
 static bool upscaleRatioOk(int w, int h, int wo, int ho) { return wo >= w && ho >= h && int64_t(wo) <= 4 * int64_t(w) && int64_t(ho) <= 4 * int64_t(h); }
@@ -1364,7 +1351,7 @@ static bool upscaleRatioOk(int w, int h, int wo, int ho) { return wo >= w && ho 
 static DevFrame makeFrame(rt_ctx* c, int frames)
 {
   selectFrame(c, frames);
-  const int cur = frames & 1, last = (frames + 1) & 1;  // m_descSet[(frames+1)%2]: this = [!i] (renderer.cpp:157, 346-356)
+  const int cur = rt::frameParity(frames), last = rt::otherParity(frames);  // m_descSet[(frames+1)%2]: this = [!i] (renderer.cpp:157, 346-356)
   DevFrame F{};
   F.stackLds = stackLdsEnv() ? stackLdsEnv() : (c->overlap >= 2 ? 6 : 0);
   F.thisG = static_cast<uint4*>(c->bufs[RT_BUF_GBUFFER0 + cur]); F.lastG = static_cast<const uint4*>(c->bufs[RT_BUF_GBUFFER0 + last]);
@@ -1458,19 +1445,26 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
   if(c->prioDecided && !c->prioExplicit && !c->prioFromEnv && c->denoiseSeen >= 0 && (st->denoise > 0) != (c->denoiseSeen > 0)) { RT_HIP(c, syncAll(c)); reopenPriorityDecision(c); }
   // SVGF (rt_set_denoiser) replaces both A-Trous chains at their place in every schedule; its history is allocated by the first frame that needs it
   const bool svgf = c->den.mode == RT_DENOISER_SVGF && st->denoise > 0;
-  if(svgf && !c->svgfHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocSvgfHistory(c))) return rc; }
+  const size_t nPix = size_t(c->W) * c->H, nHalf = size_t(c->W / 2) * (c->H / 2);
+  if(svgf && !c->histSvgf.plane[0][0]) {
+    RT_HIP(c, syncAll(c));
+    if((rc = allocHistory(c, c->histSvgf, {nPix * sizeof(float4), nHalf * sizeof(float4), nPix * sizeof(float2), nHalf * sizeof(float2)}, "SVGF"))) return rc;
+  }
   // GI spatial reuse (rt_set_gi_spatial): a pass right after the indirect stage on its stream in every schedule; its reservoirs are allocated by the first frame that needs them
   const bool gis = c->gis.mode != RT_GI_SPATIAL_OFF;
   if(gis && !c->gisResv) { RT_HIP(c, syncAll(c)); if((rc = allocGiSpatial(c))) return rc; }
   // TAA (rt_set_taa): frames with debugging_mode == 0 are rendered with the jittered camera and resolved by a pass right after compose on its stream in every
   // schedule; its history is allocated by the first frame that needs it
   const bool taa = c->taa.mode == RT_TAA_ON && st->debugging_mode == 0;
-  if(taa && !c->taaHist[0][0]) { RT_HIP(c, syncAll(c)); if((rc = allocTaaHistory(c))) return rc; }
+  if(taa && !c->histTaa.plane[0][0]) {
+    RT_HIP(c, syncAll(c));
+    if((rc = allocHistory(c, c->histTaa, {nPix * sizeof(float4), nPix * sizeof(float4), nPix * sizeof(float)}, "TAA"))) return rc;
+  }
   rt_scene_camera cam = c->cam;   // the camera of this frame's launches (c->cam stays what rt_set_camera stored)
   if(taa) (void)rt_taa_jitter_camera(&c->cam, frames, c->taa.jitterPhases, c->W, c->H, &cam);
   // Temporal upsampling (rt_set_upscale; never together with TAA): the same, with its own jitter phases and a resolve into a history at the output size
   const bool ups = c->ups.mode == RT_UPSCALE_TEMPORAL && st->debugging_mode == 0;
-  if(ups && (!c->upsHist[0][0] || c->upsW != c->ups.outWidth || c->upsH != c->ups.outHeight)) {
+  if(ups && (!c->histUps.plane[0][0] || c->upsW != c->ups.outWidth || c->upsH != c->ups.outHeight)) {
     RT_HIP(c, syncAll(c));
     freeUpscaleHistory(c);
     if((rc = allocUpscaleHistory(c))) return rc;
@@ -1487,12 +1481,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if(omMotion && c->counting)
       return fail(c, RT_ERR_INVALID_ARG, "rt_render_frame: instances are in motion with object motion vectors on (rt_set_object_motion) and counting on (rt_set_counting): the counting build has no object-motion form");
     if(omMotion) {
-      if(c->omTableRows < nInst) {
-        RT_HIP(c, syncAll(c));
-        if(c->omTable) { (void)hipFree(c->omTable); c->omTable = nullptr; c->omTableRows = 0; }
-        RT_HIP(c, hipMalloc(&c->omTable, nInst * sizeof(OmCamera)));
-        c->omTableRows = nInst;
-      }
+      if((rc = growTable(c, &c->omTable, &c->omTableRows, nInst, sizeof(OmCamera)))) return rc;
       c->omHost.resize(nInst);
       for(size_t i = 0; i < nInst; i++) {
         rt_scene_camera ci = cam;
@@ -1519,12 +1508,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if(vmMotion && c->counting)
       return fail(c, RT_ERR_INVALID_ARG, "rt_render_frame: instances are in motion or meshes deformed with per-vertex motion vectors on (rt_set_object_motion) and counting on (rt_set_counting): the counting build has no motion-vector form");
     if(vmMotion) {
-      if(c->vmTableRows < nInst) {
-        RT_HIP(c, syncAll(c));
-        if(c->vmTable) { (void)hipFree(c->vmTable); c->vmTable = nullptr; c->vmTableRows = 0; }
-        RT_HIP(c, hipMalloc(&c->vmTable, nInst * sizeof(VmRow)));
-        c->vmTableRows = nInst;
-      }
+      if((rc = growTable(c, &c->vmTable, &c->vmTableRows, nInst, sizeof(VmRow)))) return rc;
       c->vmHost.resize(nInst);
       for(size_t i = 0; i < nInst; i++) {
         VmRow& r = c->vmHost[i];
@@ -1533,31 +1517,22 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       }
     }
   }
-  const bool decide = c->overlap >= 2 && !c->prioDecided && c->spareG && c->spareMotion;
+  const bool haveRing = c->spare[rt_ctx::RING_G][0] && c->spare[rt_ctx::RING_MOTION][0];
+  const bool decide = c->overlap >= 2 && !c->prioDecided && haveRing;
   if(decide) { RT_HIP(c, syncAll(c)); harvestTimings(c); }
   const double tracedBefore = c->accStage[RT_STAGE_DIRECT] + c->accStage[RT_STAGE_INDIRECT];
   const double filterBefore = c->accStage[RT_STAGE_DENOISE_DIRECT] + c->accStage[RT_STAGE_DENOISE_INDIRECT] + c->accStage[RT_STAGE_COMPOSE];
   rt_ctx::EvSet& E = c->evSets[c->evUsed];
   if(c->overlap >= 1 && !decide) RT_HIP(c, ensureOverlapStreams(c));
-  const bool pipelined = !decide && c->overlap >= 2 && c->sideStream && c->indStream && c->spareG && c->spareMotion;
+  const bool pipelined = !decide && c->overlap >= 2 && c->sideStream && c->indStream && haveRing;
+  const bool deep = ringDeep(c);
   if(pipelined) {
     // Rotate the G-buffer (3 physical buffers) and the motion buffer (2): direct(f+1) must not overwrite what indirect(f)
     // still reads (its own G-buffer + motion, and G(f-1) for temporal reprojection).  The boundary ids keep their meaning:
     // RT_BUF_GBUFFER0 + (frames & 1) / RT_BUF_MOTION are this frame's buffers once the call returns.
     // Mode 3 (three frames in flight): one more buffer of each kind, taken oldest first, and the direct image (noisy, filtered in place, composed) three deep —
     // direct(f) then overwrites G(f-4), motion(f-3) and the direct image of f-3 and has nothing to wait for in frame f-2 (below).
-    if(c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) {
-      void*& g = c->bufs[RT_BUF_GBUFFER0 + (frames & 1)]; void* t = g; g = c->spareG; c->spareG = c->spareG2; c->spareG2 = t;
-      void*& m = c->bufs[RT_BUF_MOTION]; t = m; m = c->spareMotion; c->spareMotion = c->spareMotion2; c->spareMotion2 = t;
-      if(c->omInst) { t = c->omInst; c->omInst = c->omInstSpare; c->omInstSpare = c->omInstSpare2; c->omInstSpare2 = t; }
-      if(c->vmDelta) { t = c->vmDelta; c->vmDelta = c->vmDeltaSpare; c->vmDeltaSpare = c->vmDeltaSpare2; c->vmDeltaSpare2 = t; }
-      std::swap(c->bufs[RT_BUF_DIRECT_RESULT0 + (frames & 1)], c->spareDirRes);
-    } else {
-      std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
-      std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
-      if(c->omInst) std::swap(c->omInst, c->omInstSpare);
-      if(c->vmDelta) std::swap(c->vmDelta, c->vmDeltaSpare);
-    }
+    rotateRing(c, frames, deep);
   } else {
     RT_HIP(c, joinInFlight(c));
   }
@@ -1573,11 +1548,13 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     E.stage[k] = stage; E.prev[k] = last; last = k; k++;
     return RT_OK;
   };
-  auto run = [&](hipStream_t strm, int stage, int level) -> int {
-    const hipError_t e = launchStageOn(c, strm, F, rt::StageExtra{&OM, &VM, nullptr}, om ? rt::STAGE_MOTION_OBJECT : (vm ? rt::STAGE_MOTION_VERTEX : rt::STAGE_MOTION_NONE),
-                                       *st, cam, stage, level, 0, 0);
-    if(e != hipSuccess) { c->err = std::string("launchStage: ") + hipGetErrorString(e); return RT_ERR_HIP; }
+  auto launched = [&](hipStream_t strm, int stage, const char* launcher, hipError_t e) -> int {   // what follows every launch: its error, or its timestamp
+    if(e != hipSuccess) { c->err = std::string(launcher) + ": " + hipGetErrorString(e); return RT_ERR_HIP; }
     return record(strm, stage);
+  };
+  auto run = [&](hipStream_t strm, int stage, int level) -> int {
+    return launched(strm, stage, "launchStage", launchStageOn(c, strm, F, rt::StageExtra{&OM, &VM, nullptr},
+                                                              om ? rt::STAGE_MOTION_OBJECT : (vm ? rt::STAGE_MOTION_VERTEX : rt::STAGE_MOTION_NONE), *st, cam, stage, level, 0, 0));
   };
   // the direct stage, after the per-instance camera table when instances are in motion: the copy is ordered before the direct stage on its stream, and the
   // indirect stage follows the direct stage in every schedule (stream order, evD).  The table's previous reader is a frame before the last rt_update_instances,
@@ -1596,17 +1573,13 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     }
     return r;
   };
-  // The SVGF history this frame reads is the one the previous SVGF frame wrote, if nothing invalidated it and that frame had the other parity.
-  // The history of this frame's parity becomes valid once both chains are enqueued (svgfEnqueued); until then, and on every error return, it is not.
+  // The history a temporal pass of this frame reads is the one its pass of the previous frame wrote, if nothing invalidated it since (parity_history.h).  Every
+  // history sees every frame begin, whether or not its pass runs; the history of this frame's parity becomes valid once the pass is enqueued (svgfEnqueued for the
+  // two SVGF chains, compose for the resolves); until then, and on every error return, it is not.
+  const bool svgfRead = c->histSvgf.state.begin(frames), taaRead = c->histTaa.state.begin(frames), upsRead = c->histUps.state.begin(frames);
   SvgfArgs svgfA[2] = {};
-  if(svgf) {
-    const bool histOk = c->svgfValid && c->svgfParity == ((frames + 1) & 1);
-    svgfA[0] = svgfArgs(c, F, *st, frames, false, histOk);
-    svgfA[1] = svgfArgs(c, F, *st, frames, true, histOk);
-    c->svgfParity = frames & 1;
-  }
-  if(st->denoise == 0 || svgf) c->svgfValid = false;
-  auto svgfEnqueued = [&]() { if(svgf) c->svgfValid = true; };
+  if(svgf) for(int ind = 0; ind < 2; ind++) svgfA[ind] = svgfArgs(c, F, *st, frames, ind != 0, svgfRead);
+  auto svgfEnqueued = [&]() { if(svgf) c->histSvgf.state.commit(frames); };
   // one component's filter chain: the 4 / 5 A-Trous levels, or the SVGF steps; timed under the stage's RT_STAGE_DENOISE_* entry
   auto filters = [&](hipStream_t strm, bool ind) -> int {
     const int stage = ind ? RT_STAGE_DENOISE_INDIRECT : RT_STAGE_DENOISE_DIRECT;
@@ -1615,11 +1588,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
       for(int i = 0; i < (ind ? 5 : 4); i++) if((r = run(strm, stage, i))) return r;
       return RT_OK;
     }
-    for(int s = 0; s < svgfSteps(ind); s++) {
-      const hipError_t e = launchSvgfStep(strm, svgfA[ind ? 1 : 0], cam, ind, s);
-      if(e != hipSuccess) { c->err = std::string("launchSvgfStep: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-      if((r = record(strm, stage))) return r;
-    }
+    for(int s = 0; s < svgfSteps(ind); s++) if((r = launched(strm, stage, "launchSvgfStep", launchSvgfStep(strm, svgfA[ind ? 1 : 0], cam, ind, s)))) return r;
     return RT_OK;
   };
   // the indirect stage, then the GI spatial pass when the mode is on; both timed under RT_STAGE_INDIRECT
@@ -1628,37 +1597,23 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     if((r = run(strm, RT_STAGE_INDIRECT, 0))) return r;
     if(!gis) return RT_OK;
     const hipError_t e = launchGiSpatial(strm, c->ds, *st, cam, giSpatialArgs(c, F));
-    if(e != hipSuccess) { c->err = std::string("launchGiSpatial: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-    c->gisWritten = true;
-    return record(strm, RT_STAGE_INDIRECT);
+    if(e == hipSuccess) c->gisWritten = true;
+    return launched(strm, RT_STAGE_INDIRECT, "launchGiSpatial", e);
   };
-  // The TAA history this frame reads is the one the previous resolved frame wrote, if nothing invalidated it and that frame had the other parity.  The history
-  // of this frame's parity becomes valid once the pass is enqueued (resolve); until then, and on every error return, it is not.
   TaaArgs taaA{};
-  if(taa) taaA = taaArgs(c, F, frames, c->taaValid && c->taaLast == ((frames + 1) & 1));
-  c->taaValid = false;
-  c->taaHeld[frames & 1] = false;
-  // ... and the same for the upsampling history
+  if(taa) taaA = resolveArgs<TaaArgs>(c, c->histTaa, c->taa, F, frames, taaRead);
   UpscaleArgs upsA{};
-  if(ups) upsA = upscaleArgs(c, F, frames, c->upsValid && c->upsLast == ((frames + 1) & 1), upsDelta);
-  c->upsValid = false;
-  c->upsHeld[frames & 1] = false;
-  // compose, then the TAA or the upsampling resolve when one runs; all timed under RT_STAGE_COMPOSE
+  if(ups) {   // the same at the output size, with the frame's jitter offset in render pixels
+    upsA = resolveArgs<UpscaleArgs>(c, c->histUps, c->ups, F, frames, upsRead);
+    upsA.Wo = c->upsW; upsA.Ho = c->upsH; upsA.dx = upsDelta[0]; upsA.dy = upsDelta[1];
+  }
+  // compose, then the upsampling or the TAA resolve when one runs (never both); all timed under RT_STAGE_COMPOSE
   auto compose = [&](hipStream_t strm) -> int {
     int r;
-    if((r = run(strm, RT_STAGE_COMPOSE, 0))) return r;
-    if(ups) {
-      const hipError_t e = launchUpscaleResolve(strm, upsA, cam);
-      if(e != hipSuccess) { c->err = std::string("launchUpscaleResolve: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-      if((r = record(strm, RT_STAGE_COMPOSE))) return r;
-      c->upsValid = true; c->upsLast = frames & 1; c->upsHeld[frames & 1] = true; c->upsFrame[frames & 1] = frames;
-      return RT_OK;
-    }
-    if(!taa) return RT_OK;
-    const hipError_t e = launchTaaResolve(strm, taaA, cam);
-    if(e != hipSuccess) { c->err = std::string("launchTaaResolve: ") + hipGetErrorString(e); return RT_ERR_HIP; }
-    if((r = record(strm, RT_STAGE_COMPOSE))) return r;
-    c->taaValid = true; c->taaLast = frames & 1; c->taaHeld[frames & 1] = true; c->taaFrame[frames & 1] = frames;
+    if((r = run(strm, RT_STAGE_COMPOSE, 0)) || !(ups || taa)) return r;
+    if((r = ups ? launched(strm, RT_STAGE_COMPOSE, "launchUpscaleResolve", launchUpscaleResolve(strm, upsA, cam))
+                : launched(strm, RT_STAGE_COMPOSE, "launchTaaResolve", launchTaaResolve(strm, taaA, cam)))) return r;
+    (ups ? c->histUps : c->histTaa).state.commit(frames);
     return RT_OK;
   };
   auto mark = [&](hipStream_t strm, int& last) -> hipError_t {  // start-of-chain timestamp on a stream (after its waits)
@@ -1700,7 +1655,7 @@ int rt_render_frame(rt_ctx* c, const rt_state* st, int frames)
     //   parity and written and read on sideStream only; rt_upscale_tonemap and rt_upscale_readback join the frames in flight first.
     const uint64_t s = c->seq;
     const int r = int(s & 3);
-    const uint64_t depth = (c->overlap >= 3 && c->spareG2 && c->spareMotion2 && c->spareDirRes) ? 3u : 2u;
+    const uint64_t depth = deep ? 3u : 2u;
     if(s >= depth) {
       RT_HIP(c, hipStreamWaitEvent(c->stream, c->evI[(s - depth) & 3], 0));
       RT_HIP(c, hipStreamWaitEvent(c->stream, c->evDone[(s - depth) & 3], 0));
@@ -1776,10 +1731,7 @@ int rt_readback(rt_ctx* c, int buffer, void* dst, size_t bytes)
   if(!c || !dst || buffer < 0 || buffer >= RT_BUF_COUNT) return RT_ERR_INVALID_ARG;
   if(c->W == 0) return fail(c, RT_ERR_NO_TARGET, "rt_readback: rt_resize has not been called");
   if(bytes != c->bufBytes[buffer]) return fail(c, RT_ERR_INVALID_ARG, "rt_readback: size mismatch (see rt_buffer_bytes)");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  RT_HIP(c, hipMemcpy(dst, c->bufs[buffer], bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, c->bufs[buffer], dst, bytes);
 }
 
 int rt_upload_history(rt_ctx* c, int buffer, const void* src, size_t bytes)
@@ -1881,11 +1833,8 @@ int rt_select_frame(rt_ctx* c, int frames)
 int rt_rotate_buffers(rt_ctx* c, int frames)
 {
   if(!c) return RT_ERR_INVALID_ARG;
-  if(c->W == 0 || !c->spareG || !c->spareMotion) return fail(c, RT_ERR_NO_TARGET, "rt_rotate_buffers: rt_resize has not been called");
-  std::swap(c->bufs[RT_BUF_GBUFFER0 + (frames & 1)], c->spareG);
-  std::swap(c->bufs[RT_BUF_MOTION], c->spareMotion);
-  if(c->omInst) std::swap(c->omInst, c->omInstSpare);
-  if(c->vmDelta) std::swap(c->vmDelta, c->vmDeltaSpare);
+  if(c->W == 0 || !c->spare[rt_ctx::RING_G][0] || !c->spare[rt_ctx::RING_MOTION][0]) return fail(c, RT_ERR_NO_TARGET, "rt_rotate_buffers: rt_resize has not been called");
+  rotateRing(c, frames, false);
   return RT_OK;
 }
 
@@ -1911,10 +1860,7 @@ int rt_primary_replay_readback(rt_ctx* c, void* dst, size_t bytes)
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(c->replay.state != rt::PRIMARY_REPLAY_VALID || !c->vis.count) return fail(c, RT_ERR_INVALID_ARG, "rt_primary_replay_readback: no recording in force");
   if(bytes != size_t(c->W) * size_t(c->H) * 4) return fail(c, RT_ERR_INVALID_ARG, "rt_primary_replay_readback: size mismatch (W x H x 4 bytes)");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  RT_HIP(c, hipMemcpy(dst, c->vis.count, bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, c->vis.count, dst, bytes);
 }
 
 int rt_set_traversal(rt_ctx* c, int mode)
@@ -1979,11 +1925,12 @@ int rt_tonemap(rt_ctx* c, const rt_tonemapper* tm, int debugging_mode, int frame
   if(c->W == 0) return fail(c, RT_ERR_NO_TARGET, "rt_tonemap: rt_resize has not been called");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, joinInFlight(c));  // the result images of `frames` are complete once compose (side stream) is done
-  const int cur = frames & 1;
+  const int cur = rt::frameParity(frames);
   // the resolved images when frame `frames` was resolved (rt_set_taa), the plain result images otherwise
-  const bool resolved = c->taaHist[cur][0] && c->taaHeld[cur] && c->taaFrame[cur] == frames;
-  const float4* dImg = static_cast<const float4*>(resolved ? c->taaHist[cur][0] : c->bufs[RT_BUF_DIRECT_RESULT0 + cur]);
-  const float4* iImg = static_cast<const float4*>(resolved ? c->taaHist[cur][1] : c->bufs[RT_BUF_INDIRECT_RESULT0 + cur]);
+  void* const* hist = c->histTaa.plane[cur];
+  const bool resolved = hist[0] && c->histTaa.state.holds(frames);
+  const float4* dImg = static_cast<const float4*>(resolved ? hist[0] : c->bufs[RT_BUF_DIRECT_RESULT0 + cur]);
+  const float4* iImg = static_cast<const float4*>(resolved ? hist[1] : c->bufs[RT_BUF_INDIRECT_RESULT0 + cur]);
   RT_HIP(c, launchTonemap(c->stream, dImg, iImg,
                           c->scratch.postRowSums, c->scratch.postMean, *tm, debugging_mode, c->W, c->H, static_cast<uint32_t*>(c->bufs[RT_BUF_LDR]),
                           c->scratch.postMipD, c->scratch.postMipI));
@@ -2099,7 +2046,7 @@ int rt_set_denoiser(rt_ctx* c, const rt_denoiser* d)
     reopenPriorityDecision(c);
   }
   c->den = *d;
-  c->svgfValid = false;
+  c->histSvgf.state.invalidate();
   return RT_OK;
 }
 
@@ -2113,7 +2060,7 @@ int rt_get_denoiser(rt_ctx* c, rt_denoiser* out)
 int rt_denoiser_reset(rt_ctx* c)
 {
   if(!c) return RT_ERR_INVALID_ARG;
-  c->svgfValid = false;
+  c->histSvgf.state.invalidate();
   return RT_OK;
 }
 
@@ -2121,13 +2068,11 @@ int rt_denoiser_readback(rt_ctx* c, int which, void* dst, size_t bytes)
 {
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(which < 0 || which > 3) return fail(c, RT_ERR_INVALID_ARG, "rt_denoiser_readback: which must be 0 (direct colour + n), 1 (indirect colour + n), 2 (direct moments) or 3 (indirect moments)");
-  if(!c->svgfHist[0][0] || c->svgfParity < 0) return fail(c, RT_ERR_NO_TARGET, "rt_denoiser_readback: no frame has been rendered in SVGF mode since the last rt_resize");
+  const rt_ctx::History& h = c->histSvgf;
+  if(!h.plane[0][0] || h.state.last < 0) return fail(c, RT_ERR_NO_TARGET, "rt_denoiser_readback: no frame has been rendered in SVGF mode since the last rt_resize");
   const size_t px = (which & 1) ? size_t(c->W / 2) * (c->H / 2) : size_t(c->W) * c->H;
   if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float2))) return fail(c, RT_ERR_INVALID_ARG, "rt_denoiser_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, c->svgfHist[c->svgfParity][which], bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, h.plane[h.state.last][which], dst, bytes);
 }
 
 // ---- rt_set_gi_spatial: ReSTIR GI spatial reuse (csrc/gi_spatial.hip); the settings are host state read when a frame is enqueued
@@ -2165,10 +2110,7 @@ int rt_gi_spatial_readback(rt_ctx* c, void* dst, size_t bytes)
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(!c->gisResv || !c->gisWritten) return fail(c, RT_ERR_NO_TARGET, "rt_gi_spatial_readback: no frame has been rendered with GI spatial reuse on since the last rt_resize");
   if(bytes != size_t(c->W / 2) * (c->H / 2) * sizeof(rt_indirect_reservoir)) return fail(c, RT_ERR_INVALID_ARG, "rt_gi_spatial_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, c->gisResv, bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, c->gisResv, dst, bytes);
 }
 
 // ---- rt_set_taa: temporal anti-aliasing (csrc/taa.hip); the settings are host state read when a frame is enqueued
@@ -2190,7 +2132,7 @@ int rt_set_taa(rt_ctx* c, const rt_taa* t)
     reopenPriorityDecision(c);
   }
   c->taa = *t;
-  c->taaValid = false;
+  c->histTaa.state.invalidate();
   return RT_OK;
 }
 
@@ -2204,7 +2146,7 @@ int rt_get_taa(rt_ctx* c, rt_taa* out)
 int rt_taa_reset(rt_ctx* c)
 {
   if(!c) return RT_ERR_INVALID_ARG;
-  c->taaValid = false;
+  c->histTaa.state.invalidate();
   return RT_OK;
 }
 
@@ -2212,13 +2154,11 @@ int rt_taa_readback(rt_ctx* c, int which, void* dst, size_t bytes)
 {
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(which < 0 || which > 2) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_readback: which must be 0 (direct), 1 (indirect) or 2 (history length)");
-  if(!c->taaHist[0][0] || c->taaLast < 0) return fail(c, RT_ERR_NO_TARGET, "rt_taa_readback: no frame has been resolved since the last rt_resize");
+  const rt_ctx::History& h = c->histTaa;
+  if(!h.plane[0][0] || h.state.last < 0) return fail(c, RT_ERR_NO_TARGET, "rt_taa_readback: no frame has been resolved since the last rt_resize");
   const size_t px = size_t(c->W) * c->H;
   if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float))) return fail(c, RT_ERR_INVALID_ARG, "rt_taa_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, c->taaHist[c->taaLast][which], bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, h.plane[h.state.last][which], dst, bytes);
 }
 
 // radical inverse of k in `base` as the exact fraction num / base^digits, divided once in IEEE double
@@ -2284,7 +2224,7 @@ int rt_set_upscale(rt_ctx* c, const rt_upscale* u)
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_upscale: TAA is on (rt_set_taa); temporal upsampling brings its own jitter and resolve, switch TAA off first");
   }
   if(std::memcmp(&c->ups, u, sizeof(rt_upscale)) == 0) return RT_OK;
-  const bool sizeChange = c->upsHist[0][0] && (u->outWidth != c->upsW || u->outHeight != c->upsH);
+  const bool sizeChange = c->histUps.plane[0][0] && (u->outWidth != c->upsW || u->outHeight != c->upsH);
   if(u->mode != c->ups.mode || sizeChange) {
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, syncAll(c));
@@ -2292,7 +2232,7 @@ int rt_set_upscale(rt_ctx* c, const rt_upscale* u)
     if(sizeChange) freeUpscaleHistory(c);
   }
   c->ups = *u;
-  c->upsValid = false;
+  c->histUps.state.invalidate();
   return RT_OK;
 }
 
@@ -2306,7 +2246,7 @@ int rt_get_upscale(rt_ctx* c, rt_upscale* out)
 int rt_upscale_reset(rt_ctx* c)
 {
   if(!c) return RT_ERR_INVALID_ARG;
-  c->upsValid = false;
+  c->histUps.state.invalidate();
   return RT_OK;
 }
 
@@ -2314,25 +2254,23 @@ int rt_upscale_readback(rt_ctx* c, int which, void* dst, size_t bytes)
 {
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(which < 0 || which > 3) return fail(c, RT_ERR_INVALID_ARG, "rt_upscale_readback: which must be 0 (direct), 1 (indirect), 2 (history length) or 3 (LDR)");
-  if(!c->upsHist[0][0] || c->upsLast < 0) return fail(c, RT_ERR_NO_TARGET, "rt_upscale_readback: no frame has been resolved since the upsampling history was last freed");
+  const rt_ctx::History& h = c->histUps;
+  if(!h.plane[0][0] || h.state.last < 0) return fail(c, RT_ERR_NO_TARGET, "rt_upscale_readback: no frame has been resolved since the upsampling history was last freed");
   if(which == 3 && !c->upsLdrWritten) return fail(c, RT_ERR_NO_TARGET, "rt_upscale_readback: rt_upscale_tonemap has not run since the upsampling history was allocated");
   const size_t px = size_t(c->upsW) * c->upsH;
   if(bytes != px * (which < 2 ? sizeof(float4) : sizeof(float))) return fail(c, RT_ERR_INVALID_ARG, "rt_upscale_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, which == 3 ? c->upsLdr : c->upsHist[c->upsLast][which], bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, which == 3 ? c->upsLdr : h.plane[h.state.last][which], dst, bytes);
 }
 
 int rt_upscale_tonemap(rt_ctx* c, const rt_tonemapper* tm, int frames)
 {
   if(!c || !tm) return RT_ERR_INVALID_ARG;
-  const int cur = frames & 1;
-  if(!c->upsHist[cur][0] || !c->upsHeld[cur] || c->upsFrame[cur] != frames)
+  void* const* hist = c->histUps.plane[rt::frameParity(frames)];
+  if(!hist[0] || !c->histUps.state.holds(frames))
     return fail(c, RT_ERR_NO_TARGET, "rt_upscale_tonemap: this frame was not resolved (rt_set_upscale), or its history has been overwritten or freed");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, joinInFlight(c));  // the resolved images of `frames` are complete once the pass (side stream) is done
-  RT_HIP(c, launchTonemap(c->stream, static_cast<const float4*>(c->upsHist[cur][0]), static_cast<const float4*>(c->upsHist[cur][1]), c->upsRowSums, c->upsMean, *tm, 0,
+  RT_HIP(c, launchTonemap(c->stream, static_cast<const float4*>(hist[0]), static_cast<const float4*>(hist[1]), c->upsRowSums, c->upsMean, *tm, 0,
                           c->upsW, c->upsH, static_cast<uint32_t*>(c->upsLdr), c->upsMipD, c->upsMipI));
   c->upsLdrWritten = true;
   return RT_OK;
@@ -2364,10 +2302,7 @@ int rt_vertex_motion_readback(rt_ctx* c, void* dst, size_t bytes)
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(!c->vmDelta || !c->vmDeltaValid) return fail(c, RT_ERR_NO_TARGET, "rt_vertex_motion_readback: no frame has been rendered with per-vertex motion vectors on since the last rt_resize");
   if(bytes != size_t(c->W) * c->H * sizeof(float4)) return fail(c, RT_ERR_INVALID_ARG, "rt_vertex_motion_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, c->vmDelta, bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, c->vmDelta, dst, bytes);
 }
 
 int rt_object_motion_readback(rt_ctx* c, void* dst, size_t bytes)
@@ -2375,10 +2310,7 @@ int rt_object_motion_readback(rt_ctx* c, void* dst, size_t bytes)
   if(!c || !dst) return RT_ERR_INVALID_ARG;
   if(!c->omInst || !c->omInstValid) return fail(c, RT_ERR_NO_TARGET, "rt_object_motion_readback: no frame has been rendered with object motion vectors on since the last rt_resize");
   if(bytes != size_t(c->W) * c->H * sizeof(uint32_t)) return fail(c, RT_ERR_INVALID_ARG, "rt_object_motion_readback: size mismatch");
-  RT_HIP(c, hipSetDevice(c->device));
-  RT_HIP(c, syncAll(c));
-  if(bytes) RT_HIP(c, hipMemcpy(dst, c->omInst, bytes, hipMemcpyDeviceToHost));
-  return RT_OK;
+  return readbackDrained(c, c->omInst, dst, bytes);
 }
 
 int rt_object_motion_camera(const rt_scene_camera* cam, const float prevObjectToWorld[12], const float curObjectToWorld[12], rt_scene_camera* out)
