@@ -153,7 +153,14 @@ OBJECT_MOTION_OFF, OBJECT_MOTION_ON, OBJECT_MOTION_VERTEX = 0, 1, 3   # rt_set_o
 
 class RebuildStats(C.Structure):  # rt_rebuild_stats, 32 B
     _fields_ = [("triangles", C.c_uint32), ("nodes", C.c_uint32), ("levels", C.c_uint32), ("maxDepth", C.c_uint32), ("ms", C.c_float), ("sortMs", C.c_float),
-                ("triPad", C.c_float), ("reserved", C.c_uint32)]
+                ("triPad", C.c_float), ("iterations", C.c_uint32)]
+
+
+REBUILD_LBVH, REBUILD_PLOC = 0, 1   # rt_rebuild_options.builder
+
+
+class RebuildOptions(C.Structure):  # rt_rebuild_options, 16 B
+    _fields_ = [("builder", C.c_int32), ("radius", C.c_int32), ("maxIterations", C.c_int32), ("reserved", C.c_int32)]
 
 
 class InstancesStats(C.Structure):  # rt_instances_stats, 32 B

@@ -7,6 +7,9 @@
 //   k_hierarchy  Karras 2012: one thread per internal node of the binary radix tree, equal keys told apart by their sorted position
 //   k_union      binary node boxes, bottom-up in rounds: a node takes its children's boxes only when an EARLIER launch wrote them (the round stamp), so every
 //                hand-off crosses a kernel boundary and needs no fence; as many rounds as the tree is high
+//   (PLOC, opt-in, in place of k_hierarchy and k_union) per iteration k_ploc_neighbour — nearest cluster within `radius` Morton positions by the area
+//                of the union box, boxes staged in LDS —, k_ploc_flags, hipcub::DeviceScan::ExclusiveSum, k_ploc_merge — mutual pairs become nodes, the rest is
+//                compacted into the other cluster buffer —; then k_ploc_ranges top-down, one launch per iteration's nodes: the leaf order the collapse needs
 //   k_collapse   one thread per wide node of a level: opens the binary child of largest surface area until 8, assigns slots by the host builder's octant rule
 //   hipcub::DeviceScan::ExclusiveSum over the level's (internal children, leaf triangles) counts
 //   k_emit       child base / triangle base, the next level's nodes, the leaf records at their final positions
@@ -154,6 +157,112 @@ __global__ __launch_bounds__(AB_BLOCK) void k_union(const BuildArrays b, const u
   __hip_atomic_store(b.stamp + i, round, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- PLOC: the binary hierarchy by bottom-up clustering along the Morton order.  One iteration is four launches — neighbour, flags, scan, merge —
+// and every hand-off between workgroups crosses a launch boundary: no flag, no fence and no atomic inside a launch.  The clusters are double buffered.
+struct PlocClusters { uint32_t* id; float4* lo; float4* hi; };   // position -> binary node, box; hi.w = leaf count (bits)
+
+__global__ __launch_bounds__(AB_BLOCK) void k_ploc_init(const Tri48* table, const uint32_t* val, uint32_t n, PlocClusters c)
+{
+  const uint32_t i = blockIdx.x * AB_BLOCK + threadIdx.x;
+  if(i >= n) return;
+  float lo[3], hi[3];
+  triBox(table, val[i], lo, hi);
+  c.id[i] = n - 1 + i;
+  c.lo[i] = make_float4(lo[0], lo[1], lo[2], 0.f);
+  c.hi[i] = make_float4(hi[0], hi[1], hi[2], __uint_as_float(1u));
+}
+
+// nn[i] = the position j of [i - R, i + R], j != i, that minimises (area of the union box, min(i, j), max(i, j)).  Walking j upwards and keeping the first of equal
+// areas is that order: below i the pair is (j, i), above it (i, j), and i is larger than every j below it.  The block's boxes and a halo of R on each side are staged
+// in LDS as six float planes, so consecutive lanes read consecutive words.
+__global__ __launch_bounds__(AB_BLOCK) void k_ploc_neighbour(const float4* lo, const float4* hi, const uint32_t m, const int R, uint32_t* nn)
+{
+  __shared__ float pl[6][AB_BLOCK + 2 * ACCEL_PLOC_RADIUS_MAX];
+  const long long base = (long long)blockIdx.x * AB_BLOCK - R;   // the position of plane word 0
+  for(int t = threadIdx.x; t < AB_BLOCK + 2 * R; t += AB_BLOCK) {
+    const long long p = base + t;
+    if(p >= 0 && p < (long long)m) {
+      const float4 l = lo[p], h = hi[p];
+      pl[0][t] = l.x; pl[1][t] = l.y; pl[2][t] = l.z; pl[3][t] = h.x; pl[4][t] = h.y; pl[5][t] = h.z;
+    }
+  }
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * AB_BLOCK + threadIdx.x;
+  if(i >= (long long)m) return;
+  const int me = int(threadIdx.x) + R;
+  const long long first = i - R > 0 ? i - R : 0, last = i + R < (long long)m - 1 ? i + R : (long long)m - 1;
+  const float l0 = pl[0][me], l1 = pl[1][me], l2 = pl[2][me], h0 = pl[3][me], h1 = pl[4][me], h2 = pl[5][me];
+  float best = 0.f; int bt = -1;
+  for(int t = int(first - base); t <= int(last - base); t++) {
+    if(t == me) continue;
+    const float dx = fmaxf(h0, pl[3][t]) - fminf(l0, pl[0][t]), dy = fmaxf(h1, pl[4][t]) - fminf(l1, pl[1][t]), dz = fmaxf(h2, pl[5][t]) - fminf(l2, pl[2][t]);
+    const float d = (dx * dy + dy * dz) + dz * dx;
+    if(bt < 0 || d < best) { best = d; bt = t; }
+  }
+  nn[i] = uint32_t(base + bt);   // (m >= 2: the window holds at least one other position)
+}
+
+// keep flag << 32 | merge flag: a mutual pair merges at its lower position and its upper position goes
+__global__ __launch_bounds__(AB_BLOCK) void k_ploc_flags(const uint32_t* nn, const uint32_t m, unsigned long long* flags)
+{
+  const uint32_t i = blockIdx.x * AB_BLOCK + threadIdx.x;
+  if(i >= m) return;
+  const uint32_t j = nn[i];
+  const bool mutual = nn[j] == i;
+  flags[i] = ((unsigned long long)(mutual && j < i ? 0u : 1u) << 32) | (mutual && i < j ? 1u : 0u);
+}
+
+struct PlocNodes { uint2* child; uint2* range; float4* boxLo; float4* boxHi; uint32_t n; };
+
+// merge q of an iteration that `made` nodes precede makes node n - 2 - (made + q): the ids run downwards and the last merge of the build is node 0, the root.
+// range holds (0, leaves - 1) until k_ploc_ranges places the node.
+__global__ __launch_bounds__(AB_BLOCK) void k_ploc_merge(const PlocClusters in, const PlocClusters out, const uint32_t* nn, const unsigned long long* scan, const uint32_t m,
+                                                         const uint32_t made, const PlocNodes b, uint32_t* totals)
+{
+  const uint32_t i = blockIdx.x * AB_BLOCK + threadIdx.x;
+  if(i >= m) return;
+  const uint32_t j = nn[i];
+  const bool mutual = nn[j] == i, keep = !(mutual && j < i), merge = mutual && i < j;
+  const unsigned long long sc = scan[i];
+  const uint32_t pos = uint32_t(sc >> 32), q = uint32_t(sc & 0xffffffffull);
+  if(i == m - 1) { totals[0] = pos + (keep ? 1u : 0u); totals[1] = q + (merge ? 1u : 0u); }
+  if(!keep) return;
+  const float4 li = in.lo[i], hi = in.hi[i];
+  if(!merge) { out.id[pos] = in.id[i]; out.lo[pos] = li; out.hi[pos] = hi; return; }
+  if(made + q + 2u > b.n) return;   // never: n - 1 merges make one cluster of n, and the host counts them
+  const float4 lj = in.lo[j], hj = in.hi[j];
+  const float L[3] = {fminf(li.x, lj.x), fminf(li.y, lj.y), fminf(li.z, lj.z)}, H[3] = {fmaxf(hi.x, hj.x), fmaxf(hi.y, hj.y), fmaxf(hi.z, hj.z)};
+  const float dx = H[0] - L[0], dy = H[1] - L[1], dz = H[2] - L[2];
+  const float area = (dx * dy + dy * dz) + dz * dx;
+  const uint32_t cnt = __float_as_uint(hi.w) + __float_as_uint(hj.w), id = b.n - 2u - (made + q);
+  b.child[id] = make_uint2(in.id[i], in.id[j]);
+  b.range[id] = make_uint2(0u, cnt - 1u);
+  b.boxLo[id] = make_float4(L[0], L[1], L[2], area);
+  b.boxHi[id] = make_float4(H[0], H[1], H[2], 0.f);
+  out.id[pos] = id;
+  out.lo[pos] = make_float4(L[0], L[1], L[2], 0.f);
+  out.hi[pos] = make_float4(H[0], H[1], H[2], __uint_as_float(cnt));
+}
+
+// The leaf order: the collapse and the emission need a subtree's records contiguous in val, which a PLOC subtree is not in Morton order.  Top-down, one launch per
+// iteration's block of ids, the root's first (a node's children were made by earlier iterations, so its parent's launch has placed it): a node at (f, l) puts its
+// left child at (f, f + leavesLeft - 1) and its right child behind it; a leaf child takes its position p, writes its globalId to the final val[p] and is renamed
+// n - 1 + p.  Only a node's parent writes its range, and it reads the (0, leaves - 1) of the merge before it does.
+__global__ __launch_bounds__(AB_BLOCK) void k_ploc_ranges(const PlocNodes b, const uint32_t* valSorted, uint32_t* valFinal, const uint32_t firstId, const uint32_t count)
+{
+  const uint32_t k = blockIdx.x * AB_BLOCK + threadIdx.x;
+  if(k >= count) return;
+  const uint32_t id = firstId + k;
+  const uint2 r = b.range[id];
+  uint2 ch = b.child[id];
+  const uint32_t cntL = ch.x >= b.n - 1 ? 1u : b.range[ch.x].y + 1u;
+  if(ch.x >= b.n - 1) { valFinal[r.x] = valSorted[ch.x - (b.n - 1)]; ch.x = b.n - 1 + r.x; }
+  else b.range[ch.x] = make_uint2(r.x, r.x + cntL - 1u);
+  if(ch.y >= b.n - 1) { valFinal[r.x + cntL] = valSorted[ch.y - (b.n - 1)]; ch.y = b.n - 1 + r.x + cntL; }
+  else b.range[ch.y] = make_uint2(r.x + cntL, r.y);
+  b.child[id] = ch;
+}
+
 __device__ __forceinline__ uint32_t trisOf(const BuildArrays& b, uint32_t id) { if(id >= b.n - 1) return 1u; const uint2 r = b.range[id]; return r.y - r.x + 1u; }
 
 union NodeWords { Node8 n; uint4 w[5]; __device__ NodeWords() {} };
@@ -295,6 +404,31 @@ hipError_t accelBuildAlloc(AccelBuildWork& w, AccelBuildSet set[2], uint32_t tri
   return e;
 }
 
+hipError_t accelBuildAllocPloc(AccelBuildWork& w, std::vector<void*>& pool, bool* allocated)
+{
+  if(allocated) *allocated = false;
+  if(w.clNn) return hipSuccess;
+  const size_t cap = w.cap > 0 ? w.cap : 1;
+  const size_t before = pool.size();
+  hipError_t e = hipSuccess;
+  auto get = [&](size_t bytes, auto** out) {
+    if(e != hipSuccess) return;
+    void* p = nullptr;
+    e = hipMalloc(&p, bytes);
+    if(e == hipSuccess) { pool.push_back(p); *out = static_cast<std::remove_reference_t<decltype(**out)>*>(p); }
+  };
+  AccelBuildWork t = w;
+  for(int k = 0; k < 2; k++) { get(cap * 4, &t.clId[k]); get(cap * sizeof(float4), &t.clLo[k]); get(cap * sizeof(float4), &t.clHi[k]); }
+  get(cap * 4, &t.clNn);
+  if(e != hipSuccess) {   // all or nothing: the work keeps no pointer to what is freed here
+    while(pool.size() > before) { (void)hipFree(pool.back()); pool.pop_back(); }
+    return e;
+  }
+  w = t;
+  if(allocated) *allocated = true;
+  return hipSuccess;
+}
+
 hipError_t launchAccelTable(hipStream_t stream, const Tri48* tris, uint32_t numRecs, const AccelBuildWork& w)
 {
   if(numRecs == 0) return hipSuccess;
@@ -333,7 +467,42 @@ int accelBuildRun(hipStream_t stream, AccelBuildWork& w, const AccelBuildSet& se
   AB_HIP(hipEventRecord(evSort[1], stream));
   // 3. binary hierarchy and its boxes
   BuildArrays b{w.table, w.valOut, w.child, w.range, w.boxLo, w.boxHi, w.stamp, n};
-  if(n > 1) {
+  w.iterations = 0;
+  if(w.builder == ACCEL_BUILDER_PLOC) {
+    // 3'. PLOC: clusters in Morton order merge with their nearest neighbour within `radius` positions until one is left; the host reads the cluster count back once
+    // per iteration, as the collapse below reads its level size.  The boxes are made at merge time, so k_union's rounds are not needed.
+    if(!w.clNn || w.radius < 1u || w.radius > uint32_t(ACCEL_PLOC_RADIUS_MAX)) { (void)hipStreamSynchronize(stream); return ACCEL_BUILD_PLOC_SETUP; }
+    b.val = w.valIn;   // the final leaf order (free since the sort)
+    const PlocClusters cl[2] = {{w.clId[0], w.clLo[0], w.clHi[0]}, {w.clId[1], w.clLo[1], w.clHi[1]}};
+    const PlocNodes pn{w.child, w.range, w.boxLo, w.boxHi, n};
+    hipLaunchKernelGGL(k_ploc_init, gridOf(n), dim3(AB_BLOCK), 0, stream, w.table, w.valOut, n, cl[0]);
+    AB_HIP(hipGetLastError());
+    std::vector<std::pair<uint32_t, uint32_t>> blocks;   // per iteration: (nodes made before it, nodes it made)
+    uint32_t m = n, made = 0;
+    int cur = 0;
+    while(m > 1) {
+      if(w.iterations >= w.maxIterations) { (void)hipStreamSynchronize(stream); return ACCEL_BUILD_PLOC_ITERATIONS; }
+      hipLaunchKernelGGL(k_ploc_neighbour, gridOf(m), dim3(AB_BLOCK), 0, stream, cl[cur].lo, cl[cur].hi, m, int(w.radius), w.clNn);
+      hipLaunchKernelGGL(k_ploc_flags, gridOf(m), dim3(AB_BLOCK), 0, stream, w.clNn, m, w.count);
+      AB_HIP(hipGetLastError());
+      size_t bytes = w.sortTempBytes;
+      AB_HIP(hipcub::DeviceScan::ExclusiveSum(w.sortTemp, bytes, w.count, w.scan, int(m), stream));
+      hipLaunchKernelGGL(k_ploc_merge, gridOf(m), dim3(AB_BLOCK), 0, stream, cl[cur], cl[cur ^ 1], w.clNn, w.scan, m, made, pn, w.totals);
+      AB_HIP(hipGetLastError());
+      uint32_t totals[2] = {0, 0};
+      AB_HIP(hipMemcpyAsync(totals, w.totals, 8, hipMemcpyDeviceToHost, stream));
+      AB_HIP(hipStreamSynchronize(stream));
+      if(totals[1] == 0u || totals[0] + totals[1] != m) return ACCEL_BUILD_PLOC_NO_MERGE;   // the smallest pair of the total order is always mutual
+      blocks.push_back({made, totals[1]});
+      made += totals[1]; m = totals[0]; cur ^= 1;
+      w.iterations++;
+    }
+    if(made != n - 1) return ACCEL_BUILD_COUNT;
+    if(n == 1) AB_HIP(hipMemcpyAsync(w.valIn, w.valOut, 4, hipMemcpyDeviceToDevice, stream));
+    for(size_t t = blocks.size(); t-- > 0;)
+      hipLaunchKernelGGL(k_ploc_ranges, gridOf(blocks[t].second), dim3(AB_BLOCK), 0, stream, pn, w.valOut, w.valIn, n - 1u - (blocks[t].first + blocks[t].second), blocks[t].second);
+    AB_HIP(hipGetLastError());
+  } else if(n > 1) {
     AB_HIP(hipMemsetAsync(w.stamp, 0, size_t(n - 1) * 4, stream));
     hipLaunchKernelGGL(k_hierarchy, gridOf(n - 1), dim3(AB_BLOCK), 0, stream, w.keyOut, n, w.child, w.range);
     AB_HIP(hipGetLastError());
@@ -381,6 +550,9 @@ const char* accelBuildWhy(int code)
 {
   switch(code) {
     case ACCEL_BUILD_TOO_DEEP: return "BVH8 deeper than the traversal stack";
+    case ACCEL_BUILD_PLOC_ITERATIONS: return "PLOC did not reach one cluster within maxIterations merge iterations";
+    case ACCEL_BUILD_PLOC_NO_MERGE: return "internal error: a PLOC iteration merged no pair";
+    case ACCEL_BUILD_PLOC_SETUP: return "internal error: a PLOC build without its cluster buffers or with a radius outside 1..64";
     case ACCEL_BUILD_NO_ROOT: return "internal error: the binary tree's boxes did not reach the root in 128 rounds";
     case ACCEL_BUILD_CAPACITY: return "internal error: the wide nodes or leaf records of a level do not fit the buffers sized for them";
     case ACCEL_BUILD_COUNT: return "internal error: the leaf slots do not hold every triangle exactly once";

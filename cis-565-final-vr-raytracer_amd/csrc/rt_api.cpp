@@ -174,6 +174,8 @@ struct rt_ctx {
     uint32_t* dDirty = nullptr; uint32_t* dFlip = nullptr; uint32_t* dCounters = nullptr;   // the refit state's device words at instance capacity
   } rebuild;
   std::vector<void*> rebuildAllocs;
+  // rt_set_rebuild_options: the values in force (defaults filled in).  They belong to the context, not to the buffers above: a new scene or host build keeps them.
+  rt_rebuild_options rebuildOpt{RT_REBUILD_LBVH, ACCEL_PLOC_RADIUS_DEFAULT, ACCEL_PLOC_ITERATIONS_DEFAULT, 0};
   hipEvent_t evRebuild[4] = {nullptr, nullptr, nullptr, nullptr};   // start, sort begin, sort end, end
   // rt_set_instances (csrc/instances.hip).  The templates: per triangle of every prim mesh one AlphaRec and one opacity micro-map at
   // alphaIdx = meshAlphaBase[mesh] + triangle + 1, filled per mesh by the first table in which the mesh has an instance without RT_INST_FORCE_OPAQUE (meshMade).
@@ -2673,9 +2675,39 @@ static int adoptDeviceTree(rt_ctx* c, const DevScene& next, const AccelBuildResu
   return RT_OK;
 }
 
+// The options of rt_set_rebuild_options go into the working state of the next build; the first PLOC build on these buffers allocates PLOC's own into `pool`
+// (*allocated tells).  A failure leaves `w` and `pool` as they were.
+static hipError_t applyRebuildOptions(const rt_ctx* c, AccelBuildWork& w, std::vector<void*>& pool, bool* allocated)
+{
+  *allocated = false;
+  w.builder = c->rebuildOpt.builder; w.radius = uint32_t(c->rebuildOpt.radius); w.maxIterations = uint32_t(c->rebuildOpt.maxIterations);
+  return w.builder == ACCEL_BUILDER_PLOC ? accelBuildAllocPloc(w, pool, allocated) : hipSuccess;
+}
+
 extern "C" {
 
-/* ---- rebuilding on the device: LBVH -> BVH8 (include/rt_abi.h "Rebuilding on the device", csrc/accel_build.hip) ---- */
+/* ---- the builder of the device rebuild (include/rt_abi.h "The PLOC builder"): the call builds nothing and drops nothing ---- */
+int rt_set_rebuild_options(rt_ctx* c, const rt_rebuild_options* o)
+{
+  if(!c || !o) return RT_ERR_INVALID_ARG;
+  if(o->builder != RT_REBUILD_LBVH && o->builder != RT_REBUILD_PLOC) return fail(c, RT_ERR_INVALID_ARG, "rt_set_rebuild_options: builder must be RT_REBUILD_LBVH or RT_REBUILD_PLOC");
+  if(o->radius < 0 || o->radius > ACCEL_PLOC_RADIUS_MAX) return fail(c, RT_ERR_INVALID_ARG, "rt_set_rebuild_options: radius must be 1..64, or 0 for the default");
+  if(o->maxIterations < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_rebuild_options: maxIterations must be positive, or 0 for the default");
+  if(o->reserved != 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_rebuild_options: reserved must be 0");
+  c->rebuildOpt = *o;
+  if(o->radius == 0) c->rebuildOpt.radius = ACCEL_PLOC_RADIUS_DEFAULT;
+  if(o->maxIterations == 0) c->rebuildOpt.maxIterations = ACCEL_PLOC_ITERATIONS_DEFAULT;
+  return RT_OK;
+}
+
+int rt_get_rebuild_options(rt_ctx* c, rt_rebuild_options* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->rebuildOpt;
+  return RT_OK;
+}
+
+/* ---- rebuilding on the device: LBVH or PLOC -> BVH8 (include/rt_abi.h "Rebuilding on the device", csrc/accel_build.hip) ---- */
 int rt_rebuild_accel(rt_ctx* c)
 {
   if(int rc = needTree(c, "rt_rebuild_accel")) return rc;
@@ -2705,6 +2737,11 @@ int rt_rebuild_accel(rt_ctx* c)
     }
     B.ready = true;
   }
+  {
+    bool allocated = false;
+    const hipError_t e = applyRebuildOptions(c, B.work, c->rebuildAllocs, &allocated);
+    if(e != hipSuccess) { c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
+  }
   // the pad of the scene as it is now, and every instance's handedness (both kept by the update calls)
   const float triPad = triPadOf(R.instMax);
   const std::vector<uint32_t> flipBits = instanceBits(c->instances.size(), [&](size_t i) { return R.flip[i] != 0; });
@@ -2730,6 +2767,7 @@ int rt_rebuild_accel(rt_ctx* c)
     // a build that failed leaves the context's tree as it was: only the other set and the working buffers were written
     if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
     if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_rebuild_accel: BVH8 deeper than the traversal stack");
+    if(br == ACCEL_BUILD_PLOC_ITERATIONS) return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_rebuild_accel: ") + accelBuildWhy(br)).c_str());
     if(br != ACCEL_BUILD_OK) { c->err = std::string("rt_rebuild_accel: ") + accelBuildWhy(br); return RT_ERR_HIP; }   // a builder invariant, not the caller's argument
     RT_HIP(c, hipEventRecord(c->evRebuild[3], s));
     RT_HIP(c, hipStreamSynchronize(s));
@@ -2741,7 +2779,7 @@ int rt_rebuild_accel(rt_ctx* c)
     B.cur = target;
     // rt_update_instances works on the new tree: its maps come from the build
     R.levels = res.levels; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
-    st.nodes = res.nodes; st.levels = uint32_t(depth); st.maxDepth = uint32_t(depth);
+    st.nodes = res.nodes; st.levels = uint32_t(depth); st.maxDepth = uint32_t(depth); st.iterations = B.work.iterations;
     (void)hipEventElapsedTime(&st.ms, c->evRebuild[0], c->evRebuild[3]);
     (void)hipEventElapsedTime(&st.sortMs, c->evRebuild[1], c->evRebuild[2]);
   } else {
@@ -3026,6 +3064,16 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     }
   }
   rt_ctx::Emit::Set& LS = setFits ? EM.set[es] : freshSet;
+  {   // the builder of rt_set_rebuild_options; PLOC's buffers go into the pool of the working buffers they belong to
+    bool allocated = false;
+    const hipError_t e = applyRebuildOptions(c, W.work, fits ? c->rebuildAllocs : freshPool, &allocated);
+    if(e != hipSuccess) {
+      giveUp();
+      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
+      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    }
+    if(allocated) st.reallocated = 1u;
+  }
   if(derive) for(hipEvent_t& e : c->evEmit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
   for(hipEvent_t& e : c->evRebuild) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
   for(hipEvent_t& e : c->evInst) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
@@ -3070,6 +3118,7 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     giveUp();
     if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_set_instances: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
     if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: BVH8 deeper than the traversal stack");
+    if(br == ACCEL_BUILD_PLOC_ITERATIONS) return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_set_instances: ") + accelBuildWhy(br)).c_str());
     c->err = std::string("rt_set_instances: ") + accelBuildWhy(br);
     return RT_ERR_HIP;
   }
@@ -3103,7 +3152,7 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   c->refN = 0;   // the reference sums start again
   const int depth = int(res.levels.size());
   rt_rebuild_stats rs{};
-  rs.triangles = n; rs.nodes = res.nodes; rs.levels = rs.maxDepth = uint32_t(depth); rs.triPad = triPad;
+  rs.triangles = n; rs.nodes = res.nodes; rs.levels = rs.maxDepth = uint32_t(depth); rs.triPad = triPad; rs.iterations = B.work.iterations;
   (void)hipEventElapsedTime(&rs.ms, c->evRebuild[0], c->evRebuild[3]);
   (void)hipEventElapsedTime(&rs.sortMs, c->evRebuild[1], c->evRebuild[2]);
   B.stats = rs;

@@ -89,6 +89,15 @@ class AccelStructure {
     if(rt_rebuild_accel(m_ctx) != RT_OK) { fprintf(stderr, "AccelStructure::rebuild: %s\n", rt_last_error(m_ctx)); return false; }
     return true;
   }
+  // The builder of every later rebuild() / setInstances() (include/rt_abi.h "The PLOC builder"): RT_REBUILD_LBVH (default) or RT_REBUILD_PLOC, a tighter tree
+  // that takes longer to build; radius / maxIterations 0 = the defaults.  Builds nothing.
+  bool setRebuildOptions(int builder, int radius = 0, int maxIterations = 0)
+  {
+    const rt_rebuild_options o{builder, radius, maxIterations, 0};
+    if(rt_set_rebuild_options(m_ctx, &o) != RT_OK) { fprintf(stderr, "AccelStructure::setRebuildOptions: %s\n", rt_last_error(m_ctx)); return false; }
+    return true;
+  }
+  rt_rebuild_options rebuildOptions() const { rt_rebuild_options o{}; (void)rt_get_rebuild_options(m_ctx, &o); return o; }
   // Add and remove instances without a new scene (include/rt_abi.h "Adding and removing instances"): the whole new table.  Emitters stay where they are in it.
   bool setInstances(const rt_instance* instances, uint32_t count)
   {

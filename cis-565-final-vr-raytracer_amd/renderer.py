@@ -22,7 +22,7 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_gi_spatial", "rt_get_gi_spatial", "rt_gi_spatial_readback",
                "rt_set_taa", "rt_get_taa", "rt_taa_reset", "rt_taa_readback", "rt_taa_jitter_camera",
                "rt_set_upscale", "rt_get_upscale", "rt_upscale_reset", "rt_upscale_readback", "rt_upscale_tonemap", "rt_upscale_jitter_camera",
-               "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats",
+               "rt_update_instances", "rt_update_lights", "rt_get_refit_stats", "rt_accel_readback", "rt_rebuild_accel", "rt_get_rebuild_stats", "rt_set_rebuild_options", "rt_get_rebuild_options",
                "rt_set_instances", "rt_get_instances_stats",
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
@@ -136,6 +136,9 @@ def hip_lib():
         if hasattr(L, "rt_rebuild_accel"):   # rebuilding on the device (absent from older A/B libraries)
             L.rt_rebuild_accel.argtypes = [C.c_void_p]
             L.rt_get_rebuild_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_rebuild_options"):   # the PLOC builder of the device rebuild (absent from older A/B libraries)
+            L.rt_set_rebuild_options.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_get_rebuild_options.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "rt_set_instances"):   # adding and removing instances (absent from older A/B libraries)
             L.rt_set_instances.argtypes = abi.SET_INSTANCES_ARGTYPES
             L.rt_get_instances_stats.argtypes = abi.GET_INSTANCES_STATS_ARGTYPES
@@ -523,6 +526,18 @@ class Renderer:
         s = abi.RebuildStats()
         self._chk(hip_lib().rt_get_rebuild_stats(self._h, C.byref(s)), "rt_get_rebuild_stats")
         return s
+
+    def set_rebuild_options(self, builder=abi.REBUILD_LBVH, radius=0, max_iterations=0):
+        """rt_set_rebuild_options: the builder of every later device build (rebuild_accel, set_instances) — abi.REBUILD_LBVH or abi.REBUILD_PLOC with its search
+        radius (1..64) and iteration cap; 0 = the default.  Builds nothing (include/rt_abi.h "The PLOC builder")"""
+        o = abi.RebuildOptions(int(builder), int(radius), int(max_iterations), 0)
+        self._chk(hip_lib().rt_set_rebuild_options(self._h, C.byref(o)), "rt_set_rebuild_options")
+
+    def rebuild_options(self):
+        """rt_get_rebuild_options: the values in force, defaults filled in"""
+        o = abi.RebuildOptions()
+        self._chk(hip_lib().rt_get_rebuild_options(self._h, C.byref(o)), "rt_get_rebuild_options")
+        return o
 
     # ---- adding and removing instances (include/rt_abi.h "Adding and removing instances", DESIGN.md §27)
     def set_instances(self, inst_array):

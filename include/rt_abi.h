@@ -781,6 +781,7 @@ int rt_accel_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
  * centres (63-bit keys), a binary radix tree over the sorted keys, a top-down collapse to 8-wide nodes, and the refit kernel's boxes.  No spatial splits and no SAH:
  * one leaf record per (instance, triangle) pair.  Results are a function of the triangle set only: frames and ray queries on the device-built tree are
  * bit for bit those of the host-built tree; the two differ in speed (profiles/accel_build_timing.txt).  The build is deterministic: the same scene gives the same words.
+ * rt_set_rebuild_options ("The PLOC builder" below) selects another builder for the binary tree, whose trees trace faster and take longer to build.
  *
  * rt_rebuild_accel(ctx): valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise) — the host build stays the way a scene gets its first tree, and it
  *   is the source of what does not depend on position (globalId, TRI_OPAQUE / TRI_NOCULL, alphaIdx, the opacity micro-map), kept per triangle on the device.
@@ -804,10 +805,44 @@ typedef struct {
   float    ms;            /* HIP-event time of the call's kernels and copies on the main stream */
   float    sortMs;        /* of which the radix sort */
   float    triPad;        /* the hit rule's pad = the pad of the tree's boxes after the call */
-  uint32_t reserved;
+  uint32_t iterations;    /* PLOC: merge iterations of the build; 0 for LBVH */
 } rt_rebuild_stats;       /* 32 B */
-int rt_rebuild_accel(rt_ctx* ctx);                       /* LBVH -> BVH8 on the GPU from the context's current scene */
+int rt_rebuild_accel(rt_ctx* ctx);                       /* LBVH (or PLOC, below) -> BVH8 on the GPU from the context's current scene */
 int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * The PLOC builder (added within ABI 2.4, no version bump; csrc/accel_build.hip).  The device build's binary hierarchy is by default an LBVH: cheap to
+ * build, slow to trace.  rt_set_rebuild_options selects PLOC instead (parallel locally-ordered clustering, Meister & Bittner 2018): the sorted triangles start as
+ * one cluster each; in every iteration a cluster looks `radius` positions to each side along the Morton order for the neighbour whose union box has the smallest
+ * surface area, and two clusters that chose each other merge into one node.  The area of the merged box is what a SAH build minimises, so the tree is tighter.
+ * Records, keys, sort, the collapse to 8-wide nodes, the slot rule, the leaf size (<= 3) and the boxes are the LBVH path's: one quantiser, one layout.  The build is
+ * deterministic (ties go to the lower positions; tests/ploc_checker.cpp restates it word for word) and results do not depend on the tree; the
+ * trees differ in speed and in build time (profiles/ploc_timing.txt).
+ *
+ * rt_set_rebuild_options(ctx, options): valid any time after rt_create; the options survive rt_upload_scene, rt_build_accel and rt_resize.  It governs every later
+ *   device build — rt_rebuild_accel and the build inside rt_set_instances — and itself builds nothing and drops nothing.
+ *   Values: builder RT_REBUILD_LBVH (the default) or RT_REBUILD_PLOC; radius 1..64, 0 = the default (16); maxIterations > 0, 0 = the default (512); reserved 0.
+ *   Anything else gives RT_ERR_INVALID_ARG and leaves the options as they were.  radius and maxIterations are kept, and ignored, under RT_REBUILD_LBVH.
+ *   Buffers: PLOC's clusters (two copies: an iteration reads one and writes the other) and neighbour links, 76 B per triangle of the working buffers' capacity, are
+ *   allocated by the first PLOC build into the pool of the rebuild's working buffers and dropped with it (a host build, a new scene, an rt_set_instances that
+ *   outgrows the capacity); switching back to LBVH frees nothing, a repeated PLOC build allocates nothing.  An rt_set_instances that allocates them reports
+ *   rt_instances_stats.reallocated = 1.
+ *   Cost: one read-back of the cluster count per iteration (rt_rebuild_stats.iterations), and about 2 x radius candidate boxes per cluster per iteration.
+ *   Failure: a build that has not reached one cluster after maxIterations iterations is refused like a tree deeper than the stack — RT_ERR_INVALID_ARG,
+ *   rt_last_error "... PLOC did not reach one cluster within maxIterations merge iterations", the previous tree in place and usable.  (Every iteration merges at
+ *   least one pair, so n - 1 iterations always suffice for n triangles; nested boxes come close to needing them.)  An iteration that merges nothing is a broken
+ *   invariant: RT_ERR_HIP.
+ *   Scope: the single-GPU context only, like rt_rebuild_accel.
+ * rt_get_rebuild_options: the values in force, defaults filled in.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_REBUILD_LBVH = 0, RT_REBUILD_PLOC = 1 };
+typedef struct {
+  int32_t builder;        /* RT_REBUILD_*; default RT_REBUILD_LBVH */
+  int32_t radius;         /* PLOC search radius in cluster positions, 1..64; 0 = the default radius */
+  int32_t maxIterations;  /* PLOC: refuse the build after this many merge iterations; 0 = the default cap (512) */
+  int32_t reserved;       /* must be 0 */
+} rt_rebuild_options;     /* 16 B */
+int rt_set_rebuild_options(rt_ctx* ctx, const rt_rebuild_options* options);
+int rt_get_rebuild_options(rt_ctx* ctx, rt_rebuild_options* out);   /* the values in force, defaults filled in */
 /* ------------------------------------------------------------------------------------------------------------------
  * Adding and removing instances (added within ABI 2.4, no version bump; csrc/instances.hip).  rt_update_instances moves instances, the deform
  * calls bend meshes, rt_rebuild_accel gives a new topology; what none of them can do is change WHICH objects exist.  rt_set_instances replaces the whole instance
@@ -818,7 +853,7 @@ int rt_get_rebuild_stats(rt_ctx* ctx, rt_rebuild_stats* out);
  * for bit those of rt_upload_scene + rt_build_accel + rt_rebuild_accel of the new description (leaf records differ in alphaIdx only, whose numbering is per mesh).
  *
  * rt_set_instances(ctx, numInstances, instances): valid after rt_build_accel (RT_ERR_NO_SCENE / RT_ERR_NO_ACCEL otherwise), on a host-built or device-built tree.
- *   Afterwards the context is in the state rt_rebuild_accel leaves: the tree is a device-built tree over the new set (no SAH, no spatial splits: it traces slower
+ *   Afterwards the context is in the state rt_rebuild_accel leaves: the tree is a device-built tree over the new set (an LBVH, or PLOC's when rt_set_rebuild_options selected it; no spatial splits: it traces slower
  *   than a host-built one until a later rt_build_accel, which builds the new scene because the context's copy of the table is replaced); rt_update_instances,
  *   rt_update_vertices, rt_update_skins, rt_update_morphs and rt_rebuild_accel work on it; rt_accel_stats and rt_accel_readback describe it.
  *   Refusals (RT_ERR_INVALID_ARG, nothing changes, rt_last_error names the first offender): a NULL table; numInstances == 0; a total triangle count of 0 or above
@@ -851,7 +886,7 @@ typedef struct {
   uint32_t triangles;        /* leaf records = (instance, triangle) pairs after the call */
   uint32_t added, removed;   /* new count - common prefix length with the old table; old count - that length (diagnostic only) */
   uint32_t bytesUploaded;    /* bytes the call moved host -> device */
-  uint32_t reallocated;      /* 1: the device buffers were too small for the new counts (or absent: first call after a host build) and were allocated */
+  uint32_t reallocated;      /* 1: the device buffers were too small for the new counts (or absent: first call after a host build; PLOC's on its first build) and were allocated */
   float    expandMs;         /* HIP-event time of the record-expansion kernels */
   float    ms;               /* HIP-event time of the whole call on the main stream (expansion + device build) */
 } rt_instances_stats;        /* 32 B */
