@@ -418,14 +418,26 @@ static std::atomic<int> g_liveCtx{0};
 
 static thread_local std::string g_createErr;
 
+// the one rule for a HIP call that failed: the context's error names who failed and why, the code tells out-of-memory from the rest
+static int hipFail(rt_ctx* c, const char* who, hipError_t e)
+{
+  c->err = std::string(who) + ": " + hipGetErrorString(e);
+  return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+}
+
 #define RT_HIP(ctx, call)                                                                                                   \
   do {                                                                                                                      \
     hipError_t e_ = (call);                                                                                                 \
-    if(e_ != hipSuccess) {                                                                                                  \
-      (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                                                       \
-      return (e_ == hipErrorOutOfMemory) ? RT_ERR_OOM : RT_ERR_HIP;                                                         \
-    }                                                                                                                       \
+    if(e_ != hipSuccess) return hipFail((ctx), #call, e_);                                                                  \
   } while(0)
+
+// creates the events of the array that do not exist yet; stops at the first error
+template <size_t N> static hipError_t ensureEvents(hipEvent_t (&ev)[N])
+{
+  for(hipEvent_t& e : ev)
+    if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) return he; }
+  return hipSuccess;
+}
 
 // ---- opacity micro-map ---------------------------------------------------------------------------------------------
 // Cell (i,j) covers barycentrics u in [i/8,(i+1)/8], v in [j/8,(j+1)/8].  Its texture footprint is the bounding box of the
@@ -2504,10 +2516,23 @@ static int ensureRefitState(rt_ctx* c)
   R.dRecNode = const_cast<uint32_t*>(up);
   if((rc = allocZeroed(c, c->accelAllocs, std::max<size_t>(nNodes, 1), &R.dNodeDirty))) return rc;
   if((rc = allocZeroed(c, c->accelAllocs, 4, &R.dCounters))) return rc;
-  for(hipEvent_t& e : c->evRefit) if(!e) RT_HIP(c, hipEventCreate(&e));
+  if(const hipError_t he = ensureEvents(c->evRefit)) return hipFail(c, "hipEventCreate(&e)", he);
   R.treePad = c->ds.triPad;
   R.ready = true;
   return RT_OK;
+}
+
+// The argument block of the refit kernels (refitTail, and the full-mode pass that ends a device build): the tree arrays, the table the records are made from, the
+// bit tables and counters; the mesh arrays are the scene's.
+static RefitArgs refitArgs(const rt_ctx* c, Node8* nodes, Tri48* tris, const uint32_t* recNode, uint32_t* nodeDirty, const TriRef* triRef, const DevInstance* instances,
+                           const uint32_t* dirtyBits, const uint32_t* flipBits, uint32_t* counters, uint32_t numRecs, float pad, bool full)
+{
+  RefitArgs a{};
+  a.nodes = nodes; a.tris = tris; a.triRef = triRef; a.instances = instances;
+  a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
+  a.dirtyBits = dirtyBits; a.flipBits = flipBits; a.recNode = recNode; a.nodeDirty = nodeDirty; a.counters = counters;
+  a.numRecs = numRecs; a.pad = pad; a.full = full ? 1 : 0;
+  return a;
 }
 
 // The refit every update ends with (rt_update_instances, rt_update_vertices, rt_update_skins).  dirty[i] != 0: instance i moved or deformed; R.inst, R.instMax and
@@ -2531,11 +2556,8 @@ static int refitTail(rt_ctx* c, const std::vector<uint8_t>& dirty)
   RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
   uint32_t counters[4] = {0, 0, 0, 0};
   if(c->ds.numTris > 0 && (count > 0 || full)) {
-    RefitArgs a{};
-    a.nodes = const_cast<Node8*>(c->ds.nodes); a.tris = const_cast<Tri48*>(c->ds.tris); a.triRef = c->ds.triRef; a.instances = c->ds.instances;
-    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
-    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = R.dRecNode; a.nodeDirty = R.dNodeDirty; a.counters = R.dCounters;
-    a.numRecs = c->ds.numTris; a.pad = R.treePad; a.full = full ? 1 : 0;
+    const RefitArgs a = refitArgs(c, const_cast<Node8*>(c->ds.nodes), const_cast<Tri48*>(c->ds.tris), R.dRecNode, R.dNodeDirty, c->ds.triRef, c->ds.instances,
+                                  R.dDirty, R.dFlip, R.dCounters, c->ds.numTris, R.treePad, full);
     RT_HIP(c, launchRefitTris(s, a));
     for(size_t l = R.levels.size(); l-- > 0;) RT_HIP(c, launchRefitLevel(s, a, R.levels[l].first, R.levels[l].second));
     RT_HIP(c, hipMemcpyAsync(counters, R.dCounters, 16, hipMemcpyDeviceToHost, s));
@@ -2570,6 +2592,21 @@ static int refitTail(rt_ctx* c, const std::vector<uint8_t>& dirty)
   return RT_OK;
 }
 
+// One device instance row from an object-to-world matrix (rt_update_instances, rt_set_instances): the builder's own expression (buildBvh8, flatten), inverse
+// included.  Returns why the matrix is refused, or nullptr; *flip tells whether it mirrors (TRI_FLIP).
+static const char* makeInstanceRow(const float o2w[12], uint32_t primMesh, uint32_t flags, DevInstance& out, bool* flip)
+{
+  for(int a = 0; a < 12; a++) if(!std::isfinite(o2w[a])) return "non-finite matrix entry";
+  memcpy(out.o2w, o2w, sizeof(out.o2w));
+  float det;
+  inverseAffine(out.o2w, out.w2o, &det);
+  if(!(det != 0.0f) || !std::isfinite(det)) return "singular matrix";
+  for(int a = 0; a < 12; a++) if(!std::isfinite(out.w2o[a])) return "the matrix has no finite inverse";
+  out.primMesh = primMesh; out.flags = flags; out.pad[0] = out.pad[1] = 0;
+  *flip = det < 0.0f;
+  return nullptr;
+}
+
 extern "C" {
 
 int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const float* xf)
@@ -2587,15 +2624,10 @@ int rt_update_instances(rt_ctx* c, uint32_t count, const uint32_t* ids, const fl
       if(ids[k] >= nInst) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: instance id out of range");
       if(seen[ids[k]]) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: duplicate instance id");
       seen[ids[k]] = true;
-      for(int a = 0; a < 12; a++) if(!std::isfinite(xf[12 * k + a])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: non-finite matrix entry");
-      DevInstance& di = rows[k];
-      memcpy(di.o2w, xf + 12 * k, sizeof(di.o2w));
-      float det;
-      inverseAffine(di.o2w, di.w2o, &det);
-      if(!(det != 0.0f) || !std::isfinite(det)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: singular matrix");
-      for(int a = 0; a < 12; a++) if(!std::isfinite(di.w2o[a])) return fail(c, RT_ERR_INVALID_ARG, "rt_update_instances: the matrix has no finite inverse");
-      di.primMesh = c->instances[ids[k]].primMesh; di.flags = c->instances[ids[k]].flags; di.pad[0] = di.pad[1] = 0;
-      flip[k] = det < 0.0f;
+      bool mirrored;
+      if(const char* why = makeInstanceRow(xf + 12 * k, c->instances[ids[k]].primMesh, c->instances[ids[k]].flags, rows[k], &mirrored))
+        return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_update_instances: ") + why).c_str());
+      flip[k] = mirrored;
     }
   }
   RT_HIP(c, hipSetDevice(c->device));
@@ -2651,13 +2683,42 @@ int rt_update_lights(rt_ctx* c, const rt_trig_light* trig, uint32_t numTrig, con
 
 }  // extern "C"
 
-// The context adopts a tree the device builder has completed (rt_rebuild_accel, rt_set_instances): `next` is c->ds with the new arrays and pad; the node and record
-// counts, the traversal stack and rt_accel_stats' numbers follow from `res`.  Where the new stack cannot be allocated the previous tree stays, with its stack.
-static int adoptDeviceTree(rt_ctx* c, const DevScene& next, const AccelBuildResult& res, uint32_t n)
+// The device build both rt_rebuild_accel and rt_set_instances run, on a stream that holds what the caller has enqueued for it (flip bits, and for a new table its
+// rows and records; w.n, w.table and the options are set).  `a`: the full-mode refit block of the target set, over numInst instances.  Clears the counters, marks
+// every instance moved, builds, records evRebuild[3] and synchronises.  A failure leaves the stream idle and only the target set and the working buffers written;
+// the code and the context's message carry `who`.
+static int runDeviceBuild(rt_ctx* c, const char* who, hipStream_t s, AccelBuildWork& work, const AccelBuildSet& target, const RefitArgs& a, size_t numInst,
+                          const AlphaRec* alphaRec, AccelBuildResult& res)
 {
+  hipError_t he = hipMemsetAsync(const_cast<uint32_t*>(a.dirtyBits), 0xff, instanceWords(numInst) * 4, s);
+  if(he == hipSuccess) he = hipMemsetAsync(a.counters, 0, 16, s);
+  int br = ACCEL_BUILD_HIP;
+  if(he == hipSuccess) br = accelBuildRun(s, work, target, a, alphaRec, STACK_MAX, c->evRebuild + 1, res, &he);
+  if(br == ACCEL_BUILD_OK) {
+    if((he = hipEventRecord(c->evRebuild[3], s)) == hipSuccess) he = hipStreamSynchronize(s);
+    if(he == hipSuccess) return RT_OK;
+    br = ACCEL_BUILD_HIP;
+  }
+  (void)hipStreamSynchronize(s);
+  if(br == ACCEL_BUILD_HIP) return hipFail(c, who, he);
+  c->err = std::string(who) + ": " + (br == ACCEL_BUILD_TOO_DEEP ? "BVH8 deeper than the traversal stack" : accelBuildWhy(br));
+  const bool ofScene = br == ACCEL_BUILD_TOO_DEEP || br == ACCEL_BUILD_PLOC_ITERATIONS;   // every other code: a builder invariant, not the caller's argument
+  return ofScene ? RT_ERR_INVALID_ARG : RT_ERR_HIP;
+}
+
+// The context adopts a tree the device builder has completed (rt_rebuild_accel, rt_set_instances).  `next` is c->ds with the caller's own arrays and the new pad;
+// the tree is set `ts` of `W`, the buffers the build ran in; the node and record counts, the traversal stack and rt_accel_stats' numbers follow from `res`.  Where
+// the new stack cannot be allocated the previous tree stays, with its stack.  Otherwise the update calls work on the new tree (its maps come from the build),
+// W.stats tells of the build, the reference sums start again and the seed plane is emptied: the records are in a new order.  *adopted (optional) tells a caller
+// with state of its own to swap which of the two it was; a code with the tree adopted is the seed plane's.
+static int adoptDeviceTree(rt_ctx* c, DevScene next, rt_ctx::Rebuild& W, int ts, const AccelBuildResult& res, uint32_t n, bool* adopted = nullptr)
+{
+  if(adopted) *adopted = false;
+  const AccelBuildSet& T = W.set[ts];
   const int depth = int(res.levels.size());
   const int stackTotal = std::max(8, ((depth + 1 + 3) / 4) * 4);
   const DevScene old = c->ds;
+  next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri;
   c->ds = next;
   c->ds.numNodes = res.nodes; c->ds.numTris = n;
   if(stackTotal != old.stackTotal) {
@@ -2670,9 +2731,19 @@ static int adoptDeviceTree(rt_ctx* c, const DevScene& next, const AccelBuildResu
       return rc;
     }
   }
+  if(adopted) *adopted = true;
   c->numNodes = res.nodes; c->numRefs = n; c->spatialSplits = 0; c->maxDepth = depth;
   c->sahNodeSteps = c->sahTriSteps = 0;   // (the host builder's SAH expectation: not computed on the device)
-  return RT_OK;
+  W.cur = ts;
+  rt_ctx::Refit& R = c->refit;
+  R.levels = res.levels; R.dRecNode = T.recNode; R.dNodeDirty = W.work.nodeDirty; R.treePad = next.triPad;
+  rt_rebuild_stats st{};
+  st.triangles = n; st.nodes = res.nodes; st.levels = st.maxDepth = uint32_t(depth); st.triPad = next.triPad; st.iterations = W.work.iterations;
+  (void)hipEventElapsedTime(&st.ms, c->evRebuild[0], c->evRebuild[3]);
+  (void)hipEventElapsedTime(&st.sortMs, c->evRebuild[1], c->evRebuild[2]);
+  W.stats = st;
+  c->refN = 0;
+  return resetSeedPlane(c);
 }
 
 // The options of rt_set_rebuild_options go into the working state of the next build; the first PLOC build on these buffers allocates PLOC's own into `pool`
@@ -2721,73 +2792,43 @@ int rt_rebuild_accel(rt_ctx* c)
   const uint32_t n = uint32_t(c->numTris);
   hipStream_t s = c->stream;
   if(!B.ready) {   // the first rebuild after a host build: buffers, and the per-triangle table from the host tree's records (still the context's tree)
-    const hipError_t e = accelBuildAlloc(B.work, B.set, n, c->rebuildAllocs);
-    if(e != hipSuccess) {
+    hipError_t e = accelBuildAlloc(B.work, B.set, n, c->rebuildAllocs);
+    const bool queued = e == hipSuccess;
+    if(e == hipSuccess) e = launchAccelTable(s, c->ds.tris, c->ds.numTris, B.work);
+    if(e == hipSuccess) e = ensureEvents(c->evRebuild);
+    if(e != hipSuccess) {   // nothing of a first rebuild that failed is kept: the next call starts again
+      if(queued) (void)hipStreamSynchronize(s);
       freePool(c->rebuildAllocs); B = rt_ctx::Rebuild{};
-      c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e);
-      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
-    }
-    hipError_t e1 = launchAccelTable(s, c->ds.tris, c->ds.numTris, B.work);
-    for(hipEvent_t& e2 : c->evRebuild) if(e1 == hipSuccess && !e2) e1 = hipEventCreate(&e2);
-    if(e1 != hipSuccess) {   // nothing of a first rebuild that failed is kept: the next call starts again
-      (void)hipStreamSynchronize(s);
-      freePool(c->rebuildAllocs); B = rt_ctx::Rebuild{};
-      c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e1);
-      return e1 == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+      return hipFail(c, "rt_rebuild_accel", e);
     }
     B.ready = true;
   }
   {
     bool allocated = false;
     const hipError_t e = applyRebuildOptions(c, B.work, c->rebuildAllocs, &allocated);
-    if(e != hipSuccess) { c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
+    if(e != hipSuccess) return hipFail(c, "rt_rebuild_accel", e);
   }
-  // the pad of the scene as it is now, and every instance's handedness (both kept by the update calls)
-  const float triPad = triPadOf(R.instMax);
-  const std::vector<uint32_t> flipBits = instanceBits(c->instances.size(), [&](size_t i) { return R.flip[i] != 0; });
-  const size_t words = flipBits.size();
-  const std::vector<uint32_t> all(words, 0xffffffffu);
-  rt_rebuild_stats st{};
-  st.triangles = n; st.triPad = triPad;
+  const float triPad = triPadOf(R.instMax);   // the pad of the scene as it is now (kept by the update calls)
   RT_HIP(c, hipEventRecord(c->evRebuild[0], s));
-  if(n > 0) {
-    const int target = B.cur == 0 ? 1 : 0;
-    const AccelBuildSet& T = B.set[target];
-    RT_HIP(c, hipMemcpyAsync(R.dDirty, all.data(), words * 4, hipMemcpyHostToDevice, s));
-    RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), words * 4, hipMemcpyHostToDevice, s));
-    RT_HIP(c, hipMemsetAsync(R.dCounters, 0, 16, s));
-    RefitArgs a{};
-    a.nodes = T.nodes; a.tris = T.tris; a.triRef = c->ds.triRef; a.instances = c->ds.instances;
-    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
-    a.dirtyBits = R.dDirty; a.flipBits = R.dFlip; a.recNode = T.recNode; a.nodeDirty = B.work.nodeDirty; a.counters = R.dCounters;
-    a.numRecs = n; a.pad = triPad; a.full = 1;
-    AccelBuildResult res;
-    hipError_t he = hipSuccess;
-    const int br = accelBuildRun(s, B.work, T, a, c->ds.alphaRec, STACK_MAX, c->evRebuild + 1, res, &he);
-    // a build that failed leaves the context's tree as it was: only the other set and the working buffers were written
-    if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_rebuild_accel: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
-    if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_rebuild_accel: BVH8 deeper than the traversal stack");
-    if(br == ACCEL_BUILD_PLOC_ITERATIONS) return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_rebuild_accel: ") + accelBuildWhy(br)).c_str());
-    if(br != ACCEL_BUILD_OK) { c->err = std::string("rt_rebuild_accel: ") + accelBuildWhy(br); return RT_ERR_HIP; }   // a builder invariant, not the caller's argument
-    RT_HIP(c, hipEventRecord(c->evRebuild[3], s));
-    RT_HIP(c, hipStreamSynchronize(s));
-    // ---- swap ----
-    const int depth = int(res.levels.size());
-    DevScene next = c->ds;
-    next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri; next.triPad = triPad;
-    if((rc = adoptDeviceTree(c, next, res, n))) return rc;
-    B.cur = target;
-    // rt_update_instances works on the new tree: its maps come from the build
-    R.levels = res.levels; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
-    st.nodes = res.nodes; st.levels = uint32_t(depth); st.maxDepth = uint32_t(depth); st.iterations = B.work.iterations;
-    (void)hipEventElapsedTime(&st.ms, c->evRebuild[0], c->evRebuild[3]);
-    (void)hipEventElapsedTime(&st.sortMs, c->evRebuild[1], c->evRebuild[2]);
-  } else {
-    st.nodes = uint32_t(c->numNodes); st.levels = st.maxDepth = uint32_t(c->maxDepth);   // no triangles: the single empty node stays
+  if(n == 0) {   // no triangles: the single empty node stays
+    rt_rebuild_stats st{};
+    st.triPad = triPad; st.nodes = uint32_t(c->numNodes); st.levels = st.maxDepth = uint32_t(c->maxDepth);
+    c->refN = 0;   // the reference sums start again
+    B.stats = st;
+    return resetSeedPlane(c);
   }
-  c->refN = 0;   // the reference sums start again
-  B.stats = st;
-  return resetSeedPlane(c);   // the rebuild has written the records in a new order
+  // every instance's handedness, as the update calls keep it
+  const std::vector<uint32_t> flipBits = instanceBits(c->instances.size(), [&](size_t i) { return R.flip[i] != 0; });
+  RT_HIP(c, hipMemcpyAsync(R.dFlip, flipBits.data(), flipBits.size() * 4, hipMemcpyHostToDevice, s));
+  const int target = B.cur == 0 ? 1 : 0;
+  const AccelBuildSet& T = B.set[target];
+  const RefitArgs a = refitArgs(c, T.nodes, T.tris, T.recNode, B.work.nodeDirty, c->ds.triRef, c->ds.instances, R.dDirty, R.dFlip, R.dCounters, n, triPad, true);
+  AccelBuildResult res;
+  // a build that failed leaves the context's tree as it was: only the other set and the working buffers were written
+  if((rc = runDeviceBuild(c, "rt_rebuild_accel", s, B.work, T, a, c->instances.size(), c->ds.alphaRec, res))) return rc;
+  DevScene next = c->ds;
+  next.triPad = triPad;
+  return adoptDeviceTree(c, next, B, target, res, n);
 }
 
 int rt_get_rebuild_stats(rt_ctx* c, rt_rebuild_stats* out)
@@ -2800,23 +2841,28 @@ int rt_get_rebuild_stats(rt_ctx* c, rt_rebuild_stats* out)
 }  // extern "C"
 
 /* ---- adding and removing instances (include/rt_abi.h "Adding and removing instances", csrc/instances.hip) ---- */
-static bool emissiveMesh(const rt_ctx* c, uint32_t primMesh)   // the scene's light rule (host/scene.cpp createTrigLightBuffer), as rt_set_skins applies it
+// the scene's light rule (host/scene.cpp createTrigLightBuffer): a prim mesh whose material's emissive luminance exceeds 1e-2 has triangle-light records
+static float luminance(const rt_vec3& e) { return e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f; }
+static bool emissiveMesh(const rt_ctx* c, uint32_t primMesh)
 {
   const rt_prim_mesh& pm = c->primMeshes[primMesh];
-  const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-  return e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f;
+  return luminance(c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor) > 1e-2f;
+}
+
+// hipMalloc into a pool, for a run of allocations that share one error: nothing once an earlier one has failed
+template <class T> static void pooledAlloc(hipError_t& e, std::vector<void*>& pool, size_t bytes, T** out)
+{
+  if(e != hipSuccess) return;
+  void* p = nullptr;
+  e = hipMalloc(&p, bytes);
+  if(e == hipSuccess) { pool.push_back(p); *out = static_cast<T*>(p); }
 }
 
 // the buffers of rt_set_instances at a capacity: the rebuild's working buffers and two trees, and what the expansion writes, twice
 static hipError_t allocInstanceBuffers(rt_ctx::Rebuild& B, uint32_t triCap, uint32_t instCap, std::vector<void*>& pool)
 {
   hipError_t e = accelBuildAlloc(B.work, B.set, triCap, pool);
-  auto get = [&](size_t bytes, auto** out) {
-    if(e != hipSuccess) return;
-    void* p = nullptr;
-    e = hipMalloc(&p, bytes);
-    if(e == hipSuccess) { pool.push_back(p); *out = static_cast<std::remove_reference_t<decltype(**out)>*>(p); }
-  };
+  auto get = [&](size_t bytes, auto** out) { pooledAlloc(e, pool, bytes, out); };
   B.table[0] = B.work.table;
   get(size_t(triCap) * sizeof(Tri48), &B.table[1]);
   for(int k = 0; k < 2; k++) { get(size_t(triCap) * sizeof(TriRef), &B.triRef[k]); get(size_t(instCap) * sizeof(DevInstance), &B.inst[k]); }
@@ -2884,7 +2930,7 @@ static int planEmitters(rt_ctx* c, const char* who, uint32_t numInstances, const
     recs += meshRows[mesh];
     if(recs > 0x7fffffffull) { c->err = std::string(who) + ": more than 2^31 - 1 triangle-light records"; return RT_ERR_INVALID_ARG; }
     const rt_vec3& e = c->materials[size_t(c->primMeshes[mesh].materialIndex)].emissiveFactor;   // (a template needs a material: rt_set_emitter_meshes)
-    distrib.insert(distrib.end(), meshRows[mesh], e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f);
+    distrib.insert(distrib.end(), meshRows[mesh], luminance(e));
   }
   P.prefix.push_back(uint32_t(recs));
   P.records = uint32_t(recs);
@@ -2905,12 +2951,7 @@ static hipError_t allocEmitSet(rt_ctx::Emit::Set& S, uint32_t records, uint32_t 
 {
   const size_t recCap = std::max<size_t>(size_t(records) + records / 8, 1), emitCap = std::max<size_t>(size_t(emitting) + emitting / 8, 1);
   hipError_t e = hipSuccess;
-  auto get = [&](size_t bytes, auto** out) {
-    if(e != hipSuccess) return;
-    void* p = nullptr;
-    e = hipMalloc(&p, bytes);
-    if(e == hipSuccess) { S.pool.push_back(p); *out = static_cast<std::remove_reference_t<decltype(**out)>*>(p); }
-  };
+  auto get = [&](size_t bytes, auto** out) { pooledAlloc(e, S.pool, bytes, out); };
   get(recCap * sizeof(rt_trig_light), &S.rec); get(recCap * sizeof(rt_light_source), &S.src); get(recCap * sizeof(rt_impt_samp), &S.alias);
   get((emitCap + 1) * 4, &S.prefix); get(emitCap * 4, &S.ids);
   if(e == hipSuccess) { S.recCap = uint32_t(std::min<size_t>(recCap, 0xffffffffu)); S.emitCap = uint32_t(std::min<size_t>(emitCap, 0xffffffffu)); }
@@ -2957,22 +2998,16 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   if(!instances) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: NULL instance table");
   if(numInstances == 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: an instance table needs at least one instance");
   const size_t nOld = c->instances.size();
-  std::vector<DevInstance> rows(numInstances);   // the builder's own expression (buildBvh8, flatten), inverse included
+  std::vector<DevInstance> rows(numInstances);
   std::vector<uint32_t> prefix(size_t(numInstances) + 1, 0u);
   uint64_t total = 0;
   auto refuse = [&](uint32_t i, const char* what) { c->err = "rt_set_instances: instance " + std::to_string(i) + ": " + what; return RT_ERR_INVALID_ARG; };
   for(uint32_t i = 0; i < numInstances; i++) {
     const rt_instance& in = instances[i];
     if(in.primMesh >= c->primMeshes.size()) return refuse(i, "prim mesh out of range");
-    for(int a = 0; a < 12; a++) if(!std::isfinite(in.objectToWorld[a])) return refuse(i, "non-finite matrix entry");
-    DevInstance& di = rows[i];
-    memcpy(di.o2w, in.objectToWorld, sizeof(di.o2w));
-    float det;
-    inverseAffine(di.o2w, di.w2o, &det);
-    if(!(det != 0.0f) || !std::isfinite(det)) return refuse(i, "singular matrix");
-    for(int a = 0; a < 12; a++) if(!std::isfinite(di.w2o[a])) return refuse(i, "the matrix has no finite inverse");
-    di.primMesh = in.primMesh; di.flags = in.flags; di.pad[0] = di.pad[1] = 0;
-    prefix[i] = uint32_t(total) | (det < 0.0f ? INST_PREFIX_FLIP : 0u);
+    bool mirrored;
+    if(const char* why = makeInstanceRow(in.objectToWorld, in.primMesh, in.flags, rows[i], &mirrored)) return refuse(i, why);
+    prefix[i] = uint32_t(total) | (mirrored ? INST_PREFIX_FLIP : 0u);
     total += c->primMeshes[in.primMesh].indexCount / 3;
     if(total > uint64_t(INST_PREFIX_MASK)) return refuse(i, "the table has more than 2^31 - 1 triangles");
   }
@@ -3040,51 +3075,42 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
   if(!fits) {
     const uint32_t triCap = uint32_t(std::min<uint64_t>(uint64_t(n) + n / 8, INST_PREFIX_MASK)), instCap = numInstances + numInstances / 8;
     const hipError_t e = allocInstanceBuffers(fresh, triCap, instCap, freshPool);
-    if(e != hipSuccess) {
-      freePool(freshPool);
-      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
-      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
-    }
+    if(e != hipSuccess) { freePool(freshPool); return hipFail(c, "rt_set_instances", e); }
     st.reallocated = 1u;
   }
   rt_ctx::Rebuild& W = fits ? B : fresh;
-  // what a call that fails puts back: the shared working buffers describe the context's table again, new buffers go
   // the emitter mode's light buffers: the set the context does not use, or a new one with slack where that is absent or too small
   rt_ctx::Emit& EM = c->emit;
   const int es = EM.cur == 0 ? 1 : 0;
   rt_ctx::Emit::Set freshSet;
   const bool setFits = !derive || (EM.set[es].rec && plan.records <= EM.set[es].recCap && plan.ids.size() <= EM.set[es].emitCap);
+  // what a call that fails puts back, from here to the swap: the shared working buffers describe the context's table again, new buffers go
   auto giveUp = [&] { if(fits) { B.work.n = uint32_t(c->numTris); B.work.table = B.table[B.icur]; } else freePool(freshPool); freePool(freshSet.pool); };
+  auto giveUpHip = [&](hipError_t e) { giveUp(); return hipFail(c, "rt_set_instances", e); };
   if(!setFits) {
     const hipError_t e = allocEmitSet(freshSet, plan.records, uint32_t(plan.ids.size()));
-    if(e != hipSuccess) {
-      giveUp();
-      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
-      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
-    }
+    if(e != hipSuccess) return giveUpHip(e);
   }
   rt_ctx::Emit::Set& LS = setFits ? EM.set[es] : freshSet;
   {   // the builder of rt_set_rebuild_options; PLOC's buffers go into the pool of the working buffers they belong to
     bool allocated = false;
     const hipError_t e = applyRebuildOptions(c, W.work, fits ? c->rebuildAllocs : freshPool, &allocated);
-    if(e != hipSuccess) {
-      giveUp();
-      c->err = std::string("rt_set_instances: ") + hipGetErrorString(e);
-      return e == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
-    }
+    if(e != hipSuccess) return giveUpHip(e);
     if(allocated) st.reallocated = 1u;
   }
-  if(derive) for(hipEvent_t& e : c->evEmit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
-  for(hipEvent_t& e : c->evRebuild) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
-  for(hipEvent_t& e : c->evInst) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
-  for(hipEvent_t& e : c->evRefit) if(!e) { const hipError_t he = hipEventCreate(&e); if(he != hipSuccess) { giveUp(); RT_HIP(c, he); } }
+  {
+    hipError_t e = derive ? ensureEvents(c->evEmit) : hipSuccess;
+    if(e == hipSuccess) e = ensureEvents(c->evRebuild);
+    if(e == hipSuccess) e = ensureEvents(c->evInst);
+    if(e == hipSuccess) e = ensureEvents(c->evRefit);
+    if(e != hipSuccess) return giveUpHip(e);
+  }
   const int ti = fits ? 1 - B.icur : 0, ts = fits ? (B.cur == 0 ? 1 : 0) : 0;
   const AccelBuildSet& T = W.set[ts];
-  const size_t words = instanceWords(numInstances);
   hipStream_t s = c->stream;
-  AccelBuildResult res;
-  hipError_t he = hipSuccess;
-  int br = ACCEL_BUILD_HIP;
+  // ---- the table's own work ahead of the build: rows and prefix, the expansion (it writes the flip bits), the emitter mode's light records.  Like the build, it
+  // writes only spare and working buffers: the context's table, tree and records stay until the swap
+  hipError_t he;
   do {   // (one pass: a HIP error leaves through `break` with `he` set)
     if((he = hipEventRecord(c->evRebuild[0], s)) != hipSuccess) break;
     if((he = hipMemcpyAsync(W.inst[ti], rows.data(), size_t(numInstances) * sizeof(DevInstance), hipMemcpyHostToDevice, s)) != hipSuccess) break;
@@ -3095,40 +3121,22 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     x.triRef = W.triRef[ti]; x.table = W.table[ti]; x.flipBits = W.dFlip; x.numInst = numInstances; x.numTris = n;
     if((he = launchExpandInstances(s, x)) != hipSuccess) break;
     if((he = hipEventRecord(c->evInst[1], s)) != hipSuccess) break;
-    if(derive) {   // the light records and the binding of the new table, into the spare set: the new instance rows are in place on this stream
-      if((he = enqueueLightExpand(c, plan, LS, W.inst[ti], EM.dRows, EM.dMeshFirstRow, LS.rec, LS.src)) != hipSuccess) break;
-    }
-    if((he = hipMemsetAsync(W.dDirty, 0xff, words * 4, s)) != hipSuccess) break;   // every instance marked moved
-    if((he = hipMemsetAsync(W.dCounters, 0, 16, s)) != hipSuccess) break;
-    W.work.n = n; W.work.table = W.table[ti];
-    RefitArgs a{};
-    a.nodes = T.nodes; a.tris = T.tris; a.triRef = W.triRef[ti]; a.instances = W.inst[ti];
-    a.primMeshes = c->ds.primMeshes; a.vertices = c->ds.vertices; a.indices = c->ds.indices;
-    a.dirtyBits = W.dDirty; a.flipBits = W.dFlip; a.recNode = T.recNode; a.nodeDirty = W.work.nodeDirty; a.counters = W.dCounters;
-    a.numRecs = n; a.pad = triPad; a.full = 1;
-    br = accelBuildRun(s, W.work, T, a, TP.dAlpha, STACK_MAX, c->evRebuild + 1, res, &he);
-    if(br != ACCEL_BUILD_OK) break;
-    br = ACCEL_BUILD_HIP;
-    if((he = hipEventRecord(c->evRebuild[3], s)) != hipSuccess) break;
-    if((he = hipStreamSynchronize(s)) != hipSuccess) break;
-    br = ACCEL_BUILD_OK;
+    // the light records and the binding of the new table, into the spare set: the new instance rows are in place on this stream
+    if(derive) he = enqueueLightExpand(c, plan, LS, W.inst[ti], EM.dRows, EM.dMeshFirstRow, LS.rec, LS.src);
   } while(false);
-  if(br != ACCEL_BUILD_OK) {   // the context's table, tree and records were not written: only the spare ones and the working buffers
-    (void)hipStreamSynchronize(s);
-    giveUp();
-    if(br == ACCEL_BUILD_HIP) { c->err = std::string("rt_set_instances: ") + hipGetErrorString(he); return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP; }
-    if(br == ACCEL_BUILD_TOO_DEEP) return fail(c, RT_ERR_INVALID_ARG, "rt_set_instances: BVH8 deeper than the traversal stack");
-    if(br == ACCEL_BUILD_PLOC_ITERATIONS) return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_set_instances: ") + accelBuildWhy(br)).c_str());
-    c->err = std::string("rt_set_instances: ") + accelBuildWhy(br);
-    return RT_ERR_HIP;
-  }
+  if(he != hipSuccess) { (void)hipStreamSynchronize(s); return giveUpHip(he); }
+  W.work.n = n; W.work.table = W.table[ti];
+  const RefitArgs a = refitArgs(c, T.nodes, T.tris, T.recNode, W.work.nodeDirty, W.triRef[ti], W.inst[ti], W.dDirty, W.dFlip, W.dCounters, n, triPad, true);
+  AccelBuildResult res;
+  if((rc = runDeviceBuild(c, "rt_set_instances", s, W.work, T, a, numInstances, TP.dAlpha, res))) { giveUp(); return rc; }
   st.bytesUploaded += uint32_t(size_t(numInstances) * sizeof(DevInstance) + prefix.size() * 4 + 24);   // (24: the seed of the build's centre bounds, accelBuildRun)
   // ---- swap
   DevScene next = c->ds;
-  next.nodes = T.nodes; next.tris = T.tris; next.alphaByTri = T.alphaByTri; next.triRef = W.triRef[ti]; next.instances = W.inst[ti];
-  next.alphaRec = TP.dAlpha; next.triPad = triPad;
+  next.triRef = W.triRef[ti]; next.instances = W.inst[ti]; next.alphaRec = TP.dAlpha; next.triPad = triPad;
   if(derive) { next.trigLights = LS.rec; next.lightInfo.trigLightSize = plan.records; next.lightInfo.trigSampProb = plan.trigSampProb; }
-  if((rc = adoptDeviceTree(c, next, res, n))) { giveUp(); return rc; }
+  bool adopted;
+  rc = adoptDeviceTree(c, next, W, ts, res, n, &adopted);   // (a code with the tree adopted: the seed plane's reset; it is returned once the table is in place too)
+  if(!adopted) { giveUp(); return rc; }
   if(!fits) { freePool(c->rebuildAllocs); c->rebuildAllocs.swap(freshPool); B = fresh; }
   if(derive) {   // lights and tree change hands together
     if(!setFits) { freePool(EM.set[es].pool); EM.set[es] = std::move(freshSet); freshSet.pool.clear(); }
@@ -3140,26 +3148,19 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     (void)hipEventElapsedTime(&lightStats.expandMs, c->evEmit[0], c->evEmit[1]);
     EM.stats = lightStats;
   }
-  B.icur = ti; B.cur = ts;
+  B.icur = ti;
   c->instances.assign(instances, instances + numInstances);
   c->numTris = n;
-  // rt_update_instances and the deform calls work on the new tree: their maps come from the build, the per-instance state from the new table
+  // rt_update_instances and the deform calls work on the new table: the per-instance state and the device words at its capacity
   R.ready = true;
-  R.inst = rows; R.instMax = instMax; R.flip = flip; R.levels = res.levels;
-  R.dDirty = B.dDirty; R.dFlip = B.dFlip; R.dCounters = B.dCounters; R.dRecNode = T.recNode; R.dNodeDirty = B.work.nodeDirty; R.treePad = triPad;
+  R.inst = rows; R.instMax = instMax; R.flip = flip;
+  R.dDirty = B.dDirty; R.dFlip = B.dFlip; R.dCounters = B.dCounters;
   if(c->deform.dOut && numInstances > c->deform.coordCap) { freePool(c->deformAllocs); c->deform.dCoordJobs = nullptr; c->deform.dOut = nullptr; c->deform.coordCap = 0; }
   c->omPrev.clear(); c->omMoved.clear(); c->omPending = false;   // every instance's previous matrix is its current one
-  c->refN = 0;   // the reference sums start again
-  const int depth = int(res.levels.size());
-  rt_rebuild_stats rs{};
-  rs.triangles = n; rs.nodes = res.nodes; rs.levels = rs.maxDepth = uint32_t(depth); rs.triPad = triPad; rs.iterations = B.work.iterations;
-  (void)hipEventElapsedTime(&rs.ms, c->evRebuild[0], c->evRebuild[3]);
-  (void)hipEventElapsedTime(&rs.sortMs, c->evRebuild[1], c->evRebuild[2]);
-  B.stats = rs;
-  st.ms = rs.ms;
+  st.ms = B.stats.ms;
   (void)hipEventElapsedTime(&st.expandMs, c->evInst[0], c->evInst[1]);
   TP.stats = st;
-  return resetSeedPlane(c);   // the records are in a new order
+  return rc;
 }
 
 int rt_get_instances_stats(rt_ctx* c, rt_instances_stats* out)
@@ -3226,7 +3227,7 @@ static int ensureDeformBuffers(rt_ctx* c)
   if((rc = allocZeroed(c, c->deformAllocs, std::max<size_t>(nInst, 1), &D.dCoordJobs))) return rc;
   if((rc = allocZeroed(c, c->deformAllocs, nInst + 1, &D.dOut))) return rc;
   D.coordCap = nInst;
-  for(hipEvent_t& e : c->evDeform) if(!e) RT_HIP(c, hipEventCreate(&e));
+  if(const hipError_t he = ensureEvents(c->evDeform)) return hipFail(c, "hipEventCreate(&e)", he);
   return RT_OK;
 }
 
@@ -3356,7 +3357,7 @@ static int poseAndRefit(rt_ctx* c, const char* who, const std::vector<PoseItem>&
   int rc;
   if((rc = ensureRefitState(c))) return rc;
   if((rc = ensureDeformBuffers(c))) return rc;
-  for(hipEvent_t& e : c->evMorph) if(!e) RT_HIP(c, hipEventCreate(&e));
+  if(const hipError_t he = ensureEvents(c->evMorph)) return hipFail(c, "hipEventCreate(&e)", he);
   hipStream_t s = c->stream;
   RT_HIP(c, hipEventRecord(c->evRefit[0], s));
   RT_HIP(c, hipEventRecord(c->evDeform[0], s));
@@ -3451,8 +3452,7 @@ int rt_set_skins(rt_ctx* c, uint32_t numSkins, const rt_skin* skins, uint64_t nu
         if(!std::isfinite(in.weight[q])) return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: non-finite weight");
       }
     }
-    const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-    if(c->lights.bound == 0 && !c->emit.on && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the scene's light rule (host/scene.cpp createTrigLightBuffer); with a binding the refit tail rewrites the records
+    if(c->lights.bound == 0 && !c->emit.on && emissiveMesh(c, sk.primMesh))   // with a binding the refit tail rewrites the records
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_skins: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
     restFirst[k] = uint32_t(totalVerts);
     totalVerts += pm.vertexCount; totalJoints += sk.jointCount;
@@ -3590,8 +3590,7 @@ int rt_set_morph_targets(rt_ctx* c, uint32_t numSets, const rt_morph_set* sets, 
       const float* d = deltas[size_t(ms.firstDelta + r)].d;
       if(!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: non-finite delta");
     }
-    const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-    if(c->lights.bound == 0 && !c->emit.on && e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
+    if(c->lights.bound == 0 && !c->emit.on && emissiveMesh(c, ms.primMesh))   // the rule of rt_set_skins
       return fail(c, RT_ERR_INVALID_ARG, "rt_set_morph_targets: the prim mesh is emissive (its triangle-light records hold world positions); deform it with rt_update_vertices + rt_update_lights");
     if(D.skinOfMesh.empty() || D.skinOfMesh[ms.primMesh] < 0) { restFirst[k] = uint32_t(poolVerts); poolVerts += pm.vertexCount; }
     totalTargets += ms.targetCount;
@@ -3699,18 +3698,12 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
   if(c->emit.on) return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: the emitter mode is on (the binding is derived from the instance table; rt_set_emitter_meshes with 0 meshes switches it off)");
   rt_ctx::Lights& L = c->lights;
   if(numTrig == 0) {
-    for(const rt_skin& sk : c->deform.skins) {
-      const rt_prim_mesh& pm = c->primMeshes[sk.primMesh];
-      const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-      if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)   // the rule of rt_set_skins
+    for(const rt_skin& sk : c->deform.skins)
+      if(emissiveMesh(c, sk.primMesh))   // the rule of rt_set_skins
         return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a skin on an emissive prim mesh needs the binding (remove the skin first)");
-    }
-    for(const rt_morph_set& ms : c->morph.sets) {
-      const rt_prim_mesh& pm = c->primMeshes[ms.primMesh];
-      const rt_vec3& e = c->materials[size_t(pm.materialIndex > 0 ? pm.materialIndex : 0)].emissiveFactor;
-      if(e.x * 0.2126f + e.y * 0.7152f + e.z * 0.0722f > 1e-2f)
+    for(const rt_morph_set& ms : c->morph.sets)
+      if(emissiveMesh(c, ms.primMesh))
         return fail(c, RT_ERR_INVALID_ARG, "rt_set_light_sources: a morph set on an emissive prim mesh needs the binding (remove the set first)");
-    }
     RT_HIP(c, hipSetDevice(c->device));
     RT_HIP(c, syncAll(c));
     freePool(c->lightAllocs);
@@ -3756,14 +3749,12 @@ int rt_set_light_sources(rt_ctx* c, uint32_t numTrig, const rt_light_source* sou
     if(he == hipSuccess) he = launchLightRecords(c->stream, la);
     if(he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if(he == hipSuccess) he = hipMemcpy(eval.data(), dScratch, size_t(numTrig) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
-    for(hipEvent_t& e : c->evLights) if(he == hipSuccess && !e) he = hipEventCreate(&e);
+    if(he == hipSuccess) he = ensureEvents(c->evLights);
   }
   freePool(temp);
   if(rc || he != hipSuccess) {
     freePool(fresh);
-    if(rc) return rc;
-    c->err = std::string("rt_set_light_sources: ") + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    return rc ? rc : hipFail(c, "rt_set_light_sources", he);
   }
   for(uint32_t k = 0; k < numTrig; k++)
     if(memcmp(&recs[k].v0, &eval[k].v0, 3 * sizeof(rt_vec3)) != 0) {
@@ -3867,8 +3858,8 @@ int rt_set_emitter_meshes(rt_ctx* c, uint32_t numMeshes, const rt_emitter_mesh* 
   hipError_t he = hipSuccess;
   if(!rc) {
     he = hipDeviceSynchronize();   // the arrays above were cleared on the null stream (as in rt_set_light_sources)
-    for(hipEvent_t& e : c->evLights) if(he == hipSuccess && !e) he = hipEventCreate(&e);
-    for(hipEvent_t& e : c->evEmit) if(he == hipSuccess && !e) he = hipEventCreate(&e);
+    if(he == hipSuccess) he = ensureEvents(c->evLights);
+    if(he == hipSuccess) he = ensureEvents(c->evEmit);
     if(he == hipSuccess) he = enqueueLightExpand(c, plan, S, c->ds.instances, dRows, dFirst, dScratch, const_cast<rt_light_source*>(dSrc));
     if(he == hipSuccess) he = hipStreamSynchronize(c->stream);
     if(he == hipSuccess && n) he = hipMemcpy(eval.data(), dScratch, size_t(n) * sizeof(rt_trig_light), hipMemcpyDeviceToHost);
@@ -3877,9 +3868,7 @@ int rt_set_emitter_meshes(rt_ctx* c, uint32_t numMeshes, const rt_emitter_mesh* 
   freePool(temp);
   if(rc || he != hipSuccess) {
     freePool(fresh); freePool(binding);
-    if(rc) return rc;
-    c->err = std::string("rt_set_emitter_meshes: ") + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;
+    return rc ? rc : hipFail(c, "rt_set_emitter_meshes", he);
   }
   for(uint32_t k = 0; k < n; k++)
     if(memcmp(&recs[k], &eval[k], sizeof(rt_trig_light)) != 0) {

@@ -245,3 +245,31 @@ def test_a_build_over_the_iteration_cap_is_refused_and_the_tree_stays(lib):
     check_against(r, t, desc, "nested40 at the cap")
     tgi.same_rays(r, fresh, seq.make_rays(desc, [0], 1024, 3))
     r.destroy(); fresh.destroy()
+
+
+def test_set_instances_over_the_iteration_cap_is_refused_and_the_tree_stays(lib):
+    """The same refusal through rt_set_instances, which shares the build with rt_rebuild_accel but has buffers of its own to put back: as the first call on a context
+    (the buffers it allocated for the table go again), and after a table that succeeded under LBVH (the table fits: the shared working buffers describe the context's
+    table again).  Either way the context is as before the call, and a rebuild with exactly enough iterations gives the checker's tree."""
+    from restir_amd.renderer import hip_lib
+    for branch in ("fresh pool", "put back"):
+        _, r, desc, host = moved_context(lib, "nested40")
+        t = ploc.rebuilt(lib, desc, host, radius=1)
+        assert t.iterations == 39
+        table = refit.instances_of(desc)
+        rows = np.ascontiguousarray(table).view(np.uint8).reshape(-1)
+        if branch == "put back":
+            r.set_instances(table)
+            assert r.instances_stats().reallocated == 1 and r.rebuild_stats().iterations == 0
+        before = [r.accel_readback(w, desc.numInstances).copy() for w in range(3)]
+        r.set_rebuild_options(abi.REBUILD_PLOC, 1, 2)
+        assert hip_lib().rt_set_instances(r._h, len(table), rows.ctypes.data) == abi.ERR_INVALID_ARG, branch
+        assert b"PLOC did not reach one cluster within maxIterations" in hip_lib().rt_last_error(r._h), branch
+        assert all(np.array_equal(a, r.accel_readback(w, desc.numInstances)) for w, a in enumerate(before)), branch
+        fresh = seq.renderer(desc)
+        tgi.same_rays(r, fresh, seq.make_rays(desc, [0], 1024, 3))
+        r.set_rebuild_options(abi.REBUILD_PLOC, 1, 39)
+        r.rebuild_accel()
+        check_against(r, t, desc, "nested40 at the cap, after the refused table: " + branch)
+        tgi.same_rays(r, fresh, seq.make_rays(desc, [0], 1024, 3))
+        r.destroy(); fresh.destroy()
