@@ -146,8 +146,29 @@ RESTIR_NONE, RESTIR_RIS, RESTIR_SPATIAL, RESTIR_TEMPORAL, RESTIR_SPATIOTEMPORAL 
 # ProcScene (host/scene.hpp)
 PROC_CORNELL, PROC_HELMET, PROC_SPONZA, PROC_BISTRO_EXT, PROC_BISTRO_INT, PROC_BISTRO_EXT_REAL, PROC_SPONZA_1K = range(7)
 # rt_accel_readback ids; record sizes of the device tree (csrc/bvh8.h, csrc/dev_scene.h)
-ACCEL_NODES, ACCEL_TRIS, ACCEL_INSTANCES = range(3)
-ACCEL_RECORD_BYTES = (80, 64, 112)
+ACCEL_NODES, ACCEL_TRIS, ACCEL_INSTANCES, ACCEL_ALPHA = range(4)
+ACCEL_RECORD_BYTES = (80, 64, 112, 64)
+# rt_accel_readback(ACCEL_ALPHA): the alpha records (csrc/bvh8.h AlphaRec) with the texel address replaced by the texture's index, all ones for none
+ALPHA_REC_DT = np.dtype([("uv", "<f4", 6), ("baseAlpha", "<f4"), ("cutoff", "<f4"), ("texture", "<u8"), ("w", "<i4"), ("h", "<i4"), ("wrapS", "<i4"),
+                         ("wrapT", "<i4"), ("filter", "<i4"), ("alphaMode", "<i4")])
+# rt_material (80 B) as a numpy row
+MATERIAL_DT = np.dtype([("pbrBaseColorFactor", "<f4", 4), ("pbrBaseColorTexture", "<i4"), ("pbrMetallicFactor", "<f4"), ("pbrRoughnessFactor", "<f4"),
+                        ("pbrMetallicRoughnessTexture", "<i4"), ("emissiveTexture", "<i4"), ("emissiveFactor", "<f4", 3), ("normalTexture", "<i4"),
+                        ("normalTextureScale", "<f4"), ("transmissionFactor", "<f4"), ("transmissionTexture", "<i4"), ("ior", "<f4"), ("alphaMode", "<i4"),
+                        ("alphaCutoff", "<f4"), ("pad", "<i4")])
+
+
+class OpacityMapDesc(C.Structure):  # rt_opacity_map_desc, 64 B
+    _fields_ = [("uv", C.c_float * 6), ("baseAlpha", C.c_float), ("cutoff", C.c_float), ("alphaMode", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("wrapS", C.c_int32), ("wrapT", C.c_int32), ("filter", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class MaterialStats(C.Structure):  # rt_material_stats, 32 B
+    _fields_ = [("materialsWritten", C.c_uint32), ("dirtyMaterials", C.c_uint32), ("alphaRecords", C.c_uint32), ("leafRecords", C.c_uint32),
+                ("texelsScanned", C.c_uint64), ("bytesUploaded", C.c_uint32), ("ms", C.c_float)]
+
+
+assert ALPHA_REC_DT.itemsize == 64 and MATERIAL_DT.itemsize == 80 and C.sizeof(OpacityMapDesc) == 64 and C.sizeof(MaterialStats) == 32
 OBJECT_MOTION_OFF, OBJECT_MOTION_ON, OBJECT_MOTION_VERTEX = 0, 1, 3   # rt_set_object_motion (VERTEX: per-vertex motion vectors; 2 is not a mode)
 
 

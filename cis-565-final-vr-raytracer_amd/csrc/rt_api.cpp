@@ -34,6 +34,8 @@
 #include "morph.h"
 #include "light_records.h"
 #include "light_derive.h"
+#include "opacity_map.h"
+#include "materials.h"
 #include "../host/alias_table.hpp"
 #include "dev_math.h"
 
@@ -184,6 +186,7 @@ struct rt_ctx {
     std::vector<uint32_t> meshAlphaBase;
     std::vector<uint8_t> meshMade;
     AlphaRec* dAlpha = nullptr; uint4* dOmm = nullptr; uint32_t* dMeshAlphaBase = nullptr;
+    size_t numAlpha = 0;                         // records of dAlpha / dOmm: 1 + the triangles of all prim meshes
     rt_instances_stats stats{};
   } inst;
   std::vector<void*> instAllocs;
@@ -251,6 +254,18 @@ struct rt_ctx {
   } emit;
   std::vector<void*> emitAllocs;
   hipEvent_t evEmit[2] = {nullptr, nullptr};     // around k_light_expand
+  // rt_update_materials / rt_update_texture (csrc/materials.hip).  The device words of the re-derivation live in matAllocs, sized by the first call
+  // that needs them and again when the alpha records outgrow them; dropped by rt_upload_scene.  numTextures: the textures the scene uploaded (devTextures has one
+  // white texel more when there were none); hostNumAlpha: the alpha records of the host tree (DevScene::alphaRec after rt_build_accel); the templates count theirs.
+  struct Materials {
+    uint32_t* dDirty = nullptr; uint32_t* dOwner = nullptr; uint32_t* dOwners = nullptr; uint32_t* dCounters = nullptr; uint4* dOmm = nullptr;
+    size_t alphaCap = 0, dirtyWords = 0;
+    rt_material_stats stats{};
+  } mat;
+  std::vector<void*> matAllocs;
+  hipEvent_t evMat[2] = {nullptr, nullptr};      // around the device work of the last edit
+  uint32_t numTextures = 0;
+  size_t hostNumAlpha = 0;
   // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
   // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
   int objMotion = RT_OBJECT_MOTION_OFF;
@@ -440,61 +455,22 @@ template <size_t N> static hipError_t ensureEvents(hipEvent_t (&ev)[N])
 }
 
 // ---- opacity micro-map ---------------------------------------------------------------------------------------------
-// Cell (i,j) covers barycentrics u in [i/8,(i+1)/8], v in [j/8,(j+1)/8].  Its texture footprint is the bounding box of the
-// four corners' texcoords, widened by the bilinear footprint and one texel of slack for float rounding; the cell is
-// classified only when min/max alpha over that footprint decide HitTest (traceray_rq.glsl:86-101) with a safety margin.
-static int wrapTexel(int i, int n, int mode)
-{
-  if(mode == RT_WRAP_CLAMP) return i < 0 ? 0 : (i >= n ? n - 1 : i);
-  if(mode == RT_WRAP_MIRROR) { int p = 2 * n; int m = i % p; if(m < 0) m += p; return m < n ? m : p - 1 - m; }
-  int m = i % n; if(m < 0) m += n;
-  return m;
-}
+// The rule (cell footprint, cell state) is csrc/opacity_map.h's; here is the host's serial scan over an alpha plane (rt_upload_scene's hostAlpha).
 static void buildOpacityMap(const AlphaRec& a, const std::vector<uint8_t>* alpha, uint32_t omm[4])
 {
-  omm[0] = omm[1] = omm[2] = omm[3] = 0;
-  const bool mask = a.alphaMode == RT_ALPHA_MASK;
-  for(int j = 0; j < 8; j++)
-    for(int i = 0; i + j < 8; i++) {
-      double amin = 1.0, amax = 1.0;
-      if(alpha && a.w > 0 && a.h > 0) {
-        double fx0 = 1e300, fx1 = -1e300, fy0 = 1e300, fy1 = -1e300;
-        for(int c = 0; c < 4; c++) {
-          const double u = (i + (c & 1)) / 8.0, v = (j + (c >> 1)) / 8.0, w0 = 1.0 - u - v;
-          const double tx = a.uv0x * w0 + a.uv1x * u + a.uv2x * v, ty = a.uv0y * w0 + a.uv1y * u + a.uv2y * v;
-          fx0 = std::min(fx0, tx * a.w); fx1 = std::max(fx1, tx * a.w); fy0 = std::min(fy0, ty * a.h); fy1 = std::max(fy1, ty * a.h);
-        }
-        if(!(fx1 - fx0 < 4096.0 && fy1 - fy0 < 4096.0) || !std::isfinite(fx0 + fx1 + fy0 + fy1)) continue;  // unknown
-        const long long x0 = (long long)std::floor(fx0 - 0.5) - 1, x1 = (long long)std::floor(fx1 - 0.5) + 2;
-        const long long y0 = (long long)std::floor(fy0 - 0.5) - 1, y1 = (long long)std::floor(fy1 - 0.5) + 2;
-        if((x1 - x0 + 1) * (y1 - y0 + 1) > 65536) continue;  // footprint too large to scan: leave unknown
-        int lo = 255, hi = 0;
-        for(long long y = y0; y <= y1; y++) {
-          const int yy = wrapTexel(int(y), a.h, a.wrapT);
-          for(long long x = x0; x <= x1; x++) {
-            const int t = (*alpha)[size_t(yy) * a.w + wrapTexel(int(x), a.w, a.wrapS)];
-            lo = std::min(lo, t); hi = std::max(hi, t);
-          }
-        }
-        amin = lo / 255.0; amax = hi / 255.0;
-      }
-      const double omin = double(a.baseAlpha) * amin, omax = double(a.baseAlpha) * amax;
-      uint32_t state = 0;
-      if(a.baseAlpha >= 0.f) {
-        if(mask) {
-          if(omin > double(a.cutoff) + 1e-4) state = 1;        // opacity 1 everywhere: rand > 1 never
-          else if(omax < double(a.cutoff) - 1e-4) state = 2;   // opacity 0 everywhere
-        } else {
-          if(omin >= 1.0 + 1e-4) state = 1;                    // blend: rand in [0,1) never exceeds opacity >= 1
-          else if(omax <= 0.0) state = 2;                      // exactly zero alpha
-        }
-      }
-      const int cell = j * 8 + i;
-      omm[cell >> 4] |= state << ((cell & 15) * 2);
-    }
+  const float uv[6] = {a.uv0x, a.uv0y, a.uv1x, a.uv1y, a.uv2x, a.uv2y};
+  ommBuildSerial(uv, a.baseAlpha, a.cutoff, a.alphaMode, a.w, a.h, a.wrapS, a.wrapT, alpha ? alpha->data() : nullptr, 1, omm);
 }
 
 static int fail(rt_ctx* c, int code, const char* msg) { c->err = msg; return code; }
+// what rt_upload_scene and rt_update_materials ask of a material row in a scene of nTex textures: why it is refused, or nullptr
+static const char* checkMaterialRow(const rt_material& m, int32_t nTex)
+{
+  const int32_t ids[5] = {m.pbrBaseColorTexture, m.pbrMetallicRoughnessTexture, m.emissiveTexture, m.normalTexture, m.transmissionTexture};
+  for(int32_t id : ids)
+    if(id < -1 || id >= nTex) return "material references a missing texture";
+  return nullptr;
+}
 // a device buffer of at least 256 bytes with every byte set to `fill` (on the null stream: the caller synchronises the device before its streams touch it)
 static hipError_t mallocFilled(void** p, size_t bytes, int fill)
 {
@@ -684,6 +660,7 @@ struct LoadTimer {
 };
 static int ensureStackOverflow(rt_ctx* c);
 static int syncHostVertices(rt_ctx* c, int mesh = -1);
+static size_t numAlphaRecords(const rt_ctx* c);
 static int allocObjectMotion(rt_ctx* c);
 static void reopenPriorityDecision(rt_ctx* c);
 static void hashBytes(const void* p, size_t n, uint64_t& h0, uint64_t& h1);
@@ -796,6 +773,8 @@ int rt_destroy(rt_ctx* c)
   for(hipEvent_t e : c->evRebuild) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evInst) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evEmit) if(e) (void)hipEventDestroy(e);
+  for(hipEvent_t e : c->evMat) if(e) (void)hipEventDestroy(e);
+  freePool(c->matAllocs);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -846,12 +825,8 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   }
   // everything the kernels use as an array index is checked here: a bad id must come back as an error, not as a GPU fault
   const int32_t nTex = d->textures ? int32_t(d->numTextures) : 0;
-  for(uint32_t i = 0; i < d->numMaterials; i++) {
-    const rt_material& m = d->materials[i];
-    const int32_t ids[5] = {m.pbrBaseColorTexture, m.pbrMetallicRoughnessTexture, m.emissiveTexture, m.normalTexture, m.transmissionTexture};
-    for(int32_t id : ids)
-      if(id < -1 || id >= nTex) return fail(c, RT_ERR_INVALID_ARG, "rt_upload_scene: material references a missing texture");
-  }
+  for(uint32_t i = 0; i < d->numMaterials; i++)
+    if(const char* why = checkMaterialRow(d->materials[i], nTex)) return fail(c, RT_ERR_INVALID_ARG, (std::string("rt_upload_scene: ") + why).c_str());
   if(d->trigLights)
     for(uint32_t i = 0; i < d->lightInfo.trigLightSize; i++)
       if(d->trigLights[i].matIndex >= d->numMaterials || d->trigLights[i].impSamp.alias < 0 || uint32_t(d->trigLights[i].impSamp.alias) >= d->lightInfo.trigLightSize)
@@ -877,6 +852,9 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   dropEmitters(c);            // ... and no emitter mode
   freePool(c->instAllocs);    // ... and no instance templates
   c->inst = rt_ctx::InstTemplates{};
+  freePool(c->matAllocs);     // ... and the material edits' device words are sized again
+  c->mat = rt_ctx::Materials{};
+  c->numTextures = uint32_t(nTex); c->hostNumAlpha = 0;
   c->deform = rt_ctx::Deform{};
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
@@ -1118,6 +1096,7 @@ int rt_build_accel(rt_ctx* c)
     std::vector<AlphaRec> alpha = ha->alpha;   // texture addresses are per device
     for(size_t i = 0; i < alpha.size(); i++) if(ha->alphaTex[i] >= 0) alpha[i].bgra = c->devTextures[size_t(ha->alphaTex[i])].bgra;
     if((rc = upload(c, c->accelAllocs, alpha.data(), alpha.size(), &c->ds.alphaRec))) return rc;
+    c->hostNumAlpha = alpha.size();
     // the latency build's copy, addressable without the triangle record (one dependent access less per alpha candidate); 64 B per triangle
     std::vector<AlphaRec> byTri(bo.tris.size(), AlphaRec{});
     for(size_t i = 0; i < bo.tris.size(); i++) if(!(bo.tris[i].flags & TRI_OPAQUE)) byTri[i] = alpha[bo.tris[i].alphaIdx];
@@ -3062,7 +3041,7 @@ int rt_set_instances(rt_ctx* c, uint32_t numInstances, const rt_instance* instan
     if(!rc) rc = upload(c, c->instAllocs, base.data(), base.size(), &up);
     if(rc) { freePool(c->instAllocs); TP = rt_ctx::InstTemplates{}; return rc; }
     TP.dMeshAlphaBase = const_cast<uint32_t*>(up);
-    TP.meshAlphaBase = base; TP.meshMade.assign(base.size(), 0);
+    TP.meshAlphaBase = base; TP.meshMade.assign(base.size(), 0); TP.numAlpha = size_t(meshTris) + 1;
     st.bytesUploaded += uint32_t(base.size() * 4);
   }
   for(uint32_t i = 0; i < numInstances; i++)
@@ -3186,16 +3165,222 @@ int rt_accel_readback(rt_ctx* c, int which, void* dst, size_t bytes)
     case RT_ACCEL_NODES: src = c->ds.nodes; want = size_t(c->ds.numNodes) * sizeof(Node8); break;
     case RT_ACCEL_TRIS: src = c->ds.tris; want = size_t(c->ds.numTris) * sizeof(Tri48); break;
     case RT_ACCEL_INSTANCES: src = c->ds.instances; want = c->instances.size() * sizeof(DevInstance); break;
-    default: return fail(c, RT_ERR_INVALID_ARG, "rt_accel_readback: which must be RT_ACCEL_NODES / _TRIS / _INSTANCES");
+    case RT_ACCEL_ALPHA: src = c->ds.alphaRec; want = numAlphaRecords(c) * sizeof(AlphaRec); break;
+    default: return fail(c, RT_ERR_INVALID_ARG, "rt_accel_readback: which must be RT_ACCEL_NODES / _TRIS / _INSTANCES / _ALPHA");
   }
+  if(which == RT_ACCEL_ALPHA && bytes % sizeof(AlphaRec) == 0 && bytes < want) want = bytes;   // a prefix of the records (the templates hold every prim mesh's)
   if(bytes != want || (want && !dst)) return fail(c, RT_ERR_INVALID_ARG, "rt_accel_readback: size mismatch");
   RT_HIP(c, hipSetDevice(c->device));
   RT_HIP(c, syncAll(c));
   if(want) RT_HIP(c, hipMemcpy(dst, src, want, hipMemcpyDeviceToHost));
+  if(which == RT_ACCEL_ALPHA) {   // the texel address names a texture of this device: its index instead, all ones for none
+    AlphaRec* recs = static_cast<AlphaRec*>(dst);
+    std::unordered_map<const uint8_t*, uint64_t> indexOf;
+    for(size_t t = c->devTextures.size(); t-- > 0;) indexOf[c->devTextures[t].bgra] = t;
+    for(size_t i = 0; i < want / sizeof(AlphaRec); i++) {
+      const auto it = recs[i].bgra ? indexOf.find(recs[i].bgra) : indexOf.end();
+      const uint64_t id = it == indexOf.end() ? ~0ull : it->second;
+      memcpy(&recs[i].bgra, &id, 8);
+    }
+  }
   return RT_OK;
 }
 
 /* ---- deforming meshes: vertex updates and GPU skinning + the refit of rt_update_instances (include/rt_abi.h "Deforming meshes", csrc/deform.hip) ---- */
+}  // extern "C"
+
+/* ---- editing materials and textures (include/rt_abi.h "Editing materials and textures", csrc/materials.hip, csrc/opacity_map.h) ---- */
+// the alpha records DevScene::alphaRec holds: the templates' once rt_set_instances has put them in force, else the host tree's
+static size_t numAlphaRecords(const rt_ctx* c) { return (c->inst.dAlpha && c->ds.alphaRec == c->inst.dAlpha) ? c->inst.numAlpha : c->hostNumAlpha; }
+
+// the device words of the re-derivation, for `numAlpha` alpha records and the scene's materials; the two events
+static int ensureMaterialState(rt_ctx* c, size_t numAlpha)
+{
+  rt_ctx::Materials& M = c->mat;
+  if(const hipError_t he = ensureEvents(c->evMat)) return hipFail(c, "hipEventCreate(&e)", he);
+  const size_t words = (c->materials.size() + 31) / 32 + 1;
+  if(M.dDirty && numAlpha <= M.alphaCap && words <= M.dirtyWords) return RT_OK;
+  freePool(c->matAllocs);
+  const rt_material_stats keep = M.stats;
+  M = rt_ctx::Materials{};
+  M.stats = keep;
+  const size_t cap = numAlpha + numAlpha / 8 + 1;
+  int rc = allocZeroed(c, c->matAllocs, words, &M.dDirty);
+  if(!rc) rc = allocZeroed(c, c->matAllocs, cap, &M.dOwner);
+  if(!rc) rc = allocZeroed(c, c->matAllocs, cap, &M.dOwners);
+  if(!rc) rc = allocZeroed(c, c->matAllocs, size_t(MAT_CNT_WORDS), &M.dCounters);
+  if(!rc) rc = allocZeroed(c, c->matAllocs, cap, &M.dOmm);
+  if(rc) { freePool(c->matAllocs); M = rt_ctx::Materials{}; M.stats = keep; return rc; }
+  RT_HIP(c, hipDeviceSynchronize());   // the zero fills ran on the null stream, which the context's (non-blocking) streams do not wait for
+  M.alphaCap = cap; M.dirtyWords = words;
+  return RT_OK;
+}
+
+// What both edits end with.  dirty[m] != 0: the alpha records of material m's triangles are stale; the caller has drained the context, recorded evMat[0] and
+// enqueued its copies (material rows, texels) on the main stream, and the context's tables hold the edit.  With a tree and a dirty material: the templates of
+// meshes no alpha-tested instance uses are dropped, then select, build and scatter (csrc/materials.hip); evMat[1], one synchronise, `st` filled in.
+static int rederiveAlpha(rt_ctx* c, const std::vector<uint8_t>& dirty, rt_material_stats& st)
+{
+  hipStream_t s = c->stream;
+  st.dirtyMaterials = uint32_t(dirty.size() - std::count(dirty.begin(), dirty.end(), uint8_t(0)));
+  uint32_t counters[MAT_CNT_WORDS] = {0, 0, 0, 0};
+  if(c->haveAccel && st.dirtyMaterials > 0) {
+    rt_ctx::InstTemplates& TP = c->inst;
+    const bool inForce = TP.dAlpha && c->ds.alphaRec == TP.dAlpha;
+    auto materialOfMesh = [&](size_t mesh) { const int32_t mi = c->primMeshes[mesh].materialIndex; return size_t(mi > 0 ? mi : 0); };
+    // A template nothing in the tree refers to is not re-derived: the next table that needs it makes it from the edited tables.  A live mesh's templates all
+    // have a leaf record: rt_set_instances expands one table row per (instance, triangle) pair and the device builder emits every row, degenerate triangles
+    // included (accel_build.h: the record count of a device tree is the triangle count), so the select pass below reaches every template of a live mesh.
+    if(TP.dAlpha) {
+      std::vector<uint8_t> live(c->primMeshes.size(), 0);
+      if(inForce) for(const rt_instance& in : c->instances) if(!(in.flags & RT_INST_FORCE_OPAQUE)) live[in.primMesh] = 1;
+      for(size_t mesh = 0; mesh < c->primMeshes.size(); mesh++) {
+        if(!TP.meshMade[mesh] || live[mesh] || !dirty[materialOfMesh(mesh)]) continue;
+        const size_t first = size_t(TP.meshAlphaBase[mesh]) + 1, nt = c->primMeshes[mesh].indexCount / 3;
+        if(nt) {
+          RT_HIP(c, hipMemsetAsync(TP.dAlpha + first, 0, nt * sizeof(AlphaRec), s));
+          RT_HIP(c, hipMemsetAsync(TP.dOmm + first, 0, nt * 16, s));
+        }
+        TP.meshMade[mesh] = 0;
+      }
+    }
+    const size_t numAlpha = numAlphaRecords(c);
+    if(c->ds.numTris > 0 && numAlpha > 0) {
+      if(const int rc = ensureMaterialState(c, numAlpha)) return rc;
+      rt_ctx::Materials& M = c->mat;
+      std::vector<uint32_t> bits(M.dirtyWords, 0u);
+      for(size_t m = 0; m < dirty.size(); m++) if(dirty[m]) bits[m >> 5] |= 1u << (m & 31u);
+      MaterialArgs a{};
+      a.tris = const_cast<Tri48*>(c->ds.tris); a.alphaByTri = const_cast<AlphaRec*>(c->ds.alphaByTri);
+      a.table = c->rebuild.ready ? c->rebuild.work.table : nullptr;
+      a.triRef = c->ds.triRef; a.instances = c->ds.instances; a.primMeshes = c->ds.primMeshes; a.materials = c->ds.materials; a.textures = c->ds.textures;
+      a.alphaRec = const_cast<AlphaRec*>(c->ds.alphaRec); a.ommPlane = inForce ? TP.dOmm : M.dOmm;
+      a.dirtyBits = M.dDirty; a.owner = M.dOwner; a.owners = M.dOwners; a.counters = M.dCounters;
+      a.numRecs = c->ds.numTris; a.numGlobal = uint32_t(c->numTris); a.numAlpha = uint32_t(numAlpha); a.numInstances = uint32_t(c->instances.size());
+      a.numPrimMeshes = uint32_t(c->primMeshes.size()); a.numMaterials = uint32_t(c->materials.size()); a.numTextures = uint32_t(c->devTextures.size());
+      RT_HIP(c, hipMemcpyAsync(M.dDirty, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, s));
+      RT_HIP(c, hipMemsetAsync(M.dOwner, 0xff, numAlpha * 4, s));
+      RT_HIP(c, hipMemsetAsync(M.dCounters, 0, sizeof(counters), s));
+      RT_HIP(c, launchMaterialSelect(s, a));
+      RT_HIP(c, hipMemcpyAsync(counters, M.dCounters, sizeof(counters), hipMemcpyDeviceToHost, s));
+      RT_HIP(c, hipStreamSynchronize(s));   // the build's grid is the owner count
+      if(counters[MAT_CNT_OWNERS] > numAlpha) return fail(c, RT_ERR_HIP, "material edit: more owners than alpha records");   // never: one owner per record
+      RT_HIP(c, launchMaterialBuild(s, a, counters[MAT_CNT_OWNERS]));
+      if(counters[MAT_CNT_SELECTED] > 0) RT_HIP(c, launchMaterialScatter(s, a));
+      RT_HIP(c, hipMemcpyAsync(counters, M.dCounters, sizeof(counters), hipMemcpyDeviceToHost, s));
+      st.bytesUploaded += uint32_t(bits.size() * 4);
+    }
+  }
+  RT_HIP(c, hipEventRecord(c->evMat[1], s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  st.alphaRecords = counters[MAT_CNT_OWNERS]; st.leafRecords = counters[MAT_CNT_SELECTED];
+  st.texelsScanned = (uint64_t(counters[MAT_CNT_TEXELS_HI]) << 32) | counters[MAT_CNT_TEXELS_LO];
+  (void)hipEventElapsedTime(&st.ms, c->evMat[0], c->evMat[1]);
+  c->refN = 0;   // the scene changed: the reference sums start again
+  c->mat.stats = st;
+  return RT_OK;
+}
+
+extern "C" {
+
+int rt_update_materials(rt_ctx* c, uint32_t count, const uint32_t* ids, const rt_material* rows)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_materials: no scene uploaded");
+  if(count && (!ids || !rows)) return fail(c, RT_ERR_INVALID_ARG, "rt_update_materials: NULL ids / rows");
+  // the whole call is checked before anything changes
+  const size_t nMat = c->materials.size();
+  auto refuse = [&](uint32_t id, const char* what) { c->err = "rt_update_materials: material " + std::to_string(id) + ": " + what; return RT_ERR_INVALID_ARG; };
+  {
+    std::vector<bool> seen(nMat, false);
+    for(uint32_t k = 0; k < count; k++) {
+      if(ids[k] >= nMat) return refuse(ids[k], "id out of range");
+      if(seen[ids[k]]) return refuse(ids[k], "listed twice");
+      seen[ids[k]] = true;
+      if(const char* why = checkMaterialRow(rows[k], int32_t(c->numTextures))) return refuse(ids[k], why);
+      const float was = luminance(c->materials[ids[k]].emissiveFactor), is = luminance(rows[k].emissiveFactor);
+      if((was > 1e-2f) != (is > 1e-2f))
+        return refuse(ids[k], "the row moves the material across the scene's light rule (luminance of emissiveFactor > 1e-2): the emissive meshes are fixed by the scene");
+      if(c->emit.on && was > 1e-2f && !(was == is))
+        return refuse(ids[k], "the emitter mode is on and the row changes the luminance of an emissive material (the derived alias table would go stale)");
+    }
+  }
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // joins the frames in flight, like rt_update_instances
+  if(const hipError_t he = ensureEvents(c->evMat)) return hipFail(c, "hipEventCreate(&e)", he);
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evMat[0], s));
+  std::vector<uint8_t> dirty(nMat, 0);
+  rt_material* dMat = const_cast<rt_material*>(c->ds.materials);
+  for(uint32_t k = 0; k < count; k++) {
+    rt_material& m = c->materials[ids[k]];
+    const rt_material& n = rows[k];
+    // the alpha-relevant fields, bitwise: what the alpha records and micro-maps were derived from
+    if(memcmp(&m.pbrBaseColorFactor.w, &n.pbrBaseColorFactor.w, 4) || memcmp(&m.alphaCutoff, &n.alphaCutoff, 4) || m.alphaMode != n.alphaMode ||
+       m.pbrBaseColorTexture != n.pbrBaseColorTexture)
+      dirty[ids[k]] = 1;
+    m = n;
+    RT_HIP(c, hipMemcpyAsync(dMat + ids[k], &m, sizeof(rt_material), hipMemcpyHostToDevice, s));
+  }
+  rt_material_stats st{};
+  st.materialsWritten = count; st.bytesUploaded = uint32_t(count * sizeof(rt_material));
+  return rederiveAlpha(c, dirty, st);
+}
+
+int rt_update_texture(rt_ctx* c, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_update_texture: no scene uploaded");
+  auto refuse = [&](const char* what) { c->err = "rt_update_texture: texture " + std::to_string(texture) + ": " + what; return RT_ERR_INVALID_ARG; };
+  if(texture >= c->numTextures) return refuse("out of range");
+  const DevTexture T = c->devTextures[texture];
+  if(w == 0 || h == 0) return refuse("empty rectangle");
+  if(uint64_t(x) + w > uint64_t(T.w) || uint64_t(y) + h > uint64_t(T.h)) return refuse("the rectangle leaves the texture");
+  if(rowPitchBytes < size_t(w) * 4) return refuse("rowPitchBytes is less than 4 w");
+  if(!bgra) return refuse("NULL texels");
+  dropPrimaryReplay(c);   // settled primary visibility does not outlive this call
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  if(const hipError_t he = ensureEvents(c->evMat)) return hipFail(c, "hipEventCreate(&e)", he);
+  hipStream_t s = c->stream;
+  RT_HIP(c, hipEventRecord(c->evMat[0], s));
+  uint8_t* dTex = const_cast<uint8_t*>(T.bgra) + (size_t(y) * size_t(T.w) + x) * 4;
+  RT_HIP(c, hipMemcpy2DAsync(dTex, size_t(T.w) * 4, bgra, rowPitchBytes, size_t(w) * 4, h, hipMemcpyHostToDevice, s));
+  // the context's alpha plane and its hash (rt_build_accel's cache key)
+  std::vector<uint8_t>& plane = c->hostAlpha[texture];
+  bool alphaChanged = false;
+  for(uint32_t r = 0; r < h; r++) {
+    uint8_t* dst = plane.data() + (size_t(y) + r) * size_t(T.w) + x;
+    const uint8_t* src = bgra + size_t(r) * rowPitchBytes + 3;
+    for(uint32_t q = 0; q < w; q++) { const uint8_t v = src[size_t(q) * 4]; if(dst[q] != v) { dst[q] = v; alphaChanged = true; } }
+  }
+  std::vector<uint8_t> dirty(c->materials.size(), 0);
+  if(alphaChanged) {
+    uint64_t h0 = 0x243F6A8885A308D3ull, h1 = 0x13198A2E03707344ull;
+    hashBytes(plane.data(), plane.size(), h0, h1);
+    c->alphaHash[texture] = {h0, h1};
+    for(size_t m = 0; m < c->materials.size(); m++) if(c->materials[m].pbrBaseColorTexture == int32_t(texture)) dirty[m] = 1;
+  }
+  rt_material_stats st{};
+  st.bytesUploaded = uint32_t(size_t(w) * h * 4);
+  return rederiveAlpha(c, dirty, st);
+}
+
+int rt_get_material_stats(rt_ctx* c, rt_material_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->mat.stats;
+  return RT_OK;
+}
+
+int rt_opacity_map(const rt_opacity_map_desc* d, const uint8_t* bgra, uint32_t omm[4])
+{
+  if(!d || !omm || (bgra && (d->w <= 0 || d->h <= 0))) return RT_ERR_INVALID_ARG;
+  ommBuildSerial(d->uv, d->baseAlpha, d->cutoff, d->alphaMode, d->w, d->h, d->wrapS, d->wrapT, bgra ? bgra + 3 : nullptr, 4, omm);
+  return RT_OK;
+}
+
 }  // extern "C"
 
 // the context's copy of the vertices of skinned meshes is refreshed here, at the top of what reads it, not by rt_update_skins (mesh < 0: every stale mesh)

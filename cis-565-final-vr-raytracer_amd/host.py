@@ -33,6 +33,8 @@ def host_lib():
             "rth_scene_update_instances": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_set_instances": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_update_vertices": [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p],
+            "rth_scene_set_materials": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32],
+            "rth_scene_set_texture": [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_size_t],
             "rth_scene_light_sources": [C.c_void_p, C.c_void_p, C.c_uint32],
             "rth_scene_emitter_meshes": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
@@ -131,6 +133,18 @@ class Scene:
         assert rows.size % 32 == 0
         if host_lib().rth_scene_update_vertices(self._h, int(prim_mesh), int(first), rows.size // 32, rows.ctypes.data) != 0:
             raise ValueError("Scene.updateVertices: prim mesh or vertex range out of bounds")
+    def setMaterials(self, ids, rows):
+        """Scene::setMaterials: rows (abi.MATERIAL_DT records or n x 80 bytes) replace the material rows `ids`; the triangle-light records follow a changed
+        emission; desc() afterwards describes the edited scene (Renderer.update_materials takes the same arguments)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(-1)
+        if rows.size != 80 * ids.size or host_lib().rth_scene_set_materials(self._h, ids.ctypes.data, rows.ctypes.data, ids.size) != 0:
+            raise ValueError("Scene.setMaterials: an id out of range, a row that is not 80 bytes, or a row that moves a material across the light rule")
+    def setTexture(self, texture, x, y, bgra):
+        """Scene::setTexture: bgra (h, w, 4) uint8 replaces the texels at (x, y) of one texture (Renderer.update_texture takes the same arguments)"""
+        a = np.ascontiguousarray(bgra, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4 or host_lib().rth_scene_set_texture(self._h, int(texture), int(x), int(y), a.shape[1], a.shape[0], a.ctypes.data, 4 * a.shape[1]) != 0:
+            raise ValueError("Scene.setTexture: (h, w, 4) texels inside the texture")
     def lightSources(self):
         """Scene::lightSources: the (instance, triangle) every triangle-light record came from, in record order (abi.LIGHT_SOURCE_DT rows): what
         Renderer.set_light_sources takes"""

@@ -82,6 +82,14 @@ int rth_scene_update_vertices(void* s, uint32_t primMesh, uint32_t first, uint32
 {
   return static_cast<Scene*>(s)->updateVertices(primMesh, first, count, rows) ? 0 : -1;
 }
+int rth_scene_set_materials(void* s, const uint32_t* ids, const rt_material* rows, uint32_t count)
+{
+  return static_cast<Scene*>(s)->setMaterials(ids, rows, count) ? 0 : -1;
+}
+int rth_scene_set_texture(void* s, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes)
+{
+  return static_cast<Scene*>(s)->setTexture(texture, x, y, w, h, bgra, rowPitchBytes) ? 0 : -1;
+}
 // Scene::lightSources: returns the number of sources; copies min(cap, number) {instance, triangle} pairs into out (out may be NULL with cap 0: the count alone)
 uint32_t rth_scene_light_sources(void* s, rt_light_source* out, uint32_t cap)
 {

@@ -115,6 +115,29 @@ class AccelStructure {
     if(!scene.setInstances(instances, count)) { fprintf(stderr, "AccelStructure::setInstances: the scene refused the table\n"); return false; }
     return true;
   }
+  // Edit materials and texels without a new scene (include/rt_abi.h "Editing materials and textures"): the device is asked first, its checks are the stricter
+  // ones; then the scene's own tables follow.  Only where an emission changed, and the scene recomputed its light records, are they handed over
+  // (rt_update_lights), as update() does for a move (in the emitter mode the device has refused a row that changes an emitter's luminance before the scene is asked).
+  bool setMaterials(Scene& scene, const uint32_t* ids, const rt_material* rows, uint32_t count)
+  {
+    if(rt_update_materials(m_ctx, count, ids, rows) != RT_OK) { fprintf(stderr, "AccelStructure::setMaterials: %s\n", rt_last_error(m_ctx)); return false; }
+    bool lightsChanged = false;
+    if(!scene.setMaterials(ids, rows, count, &lightsChanged)) { fprintf(stderr, "AccelStructure::setMaterials: the scene refused the rows\n"); return false; }
+    if(!lightsChanged) return true;
+    const rt_scene_desc d = scene.getDesc(nullptr);
+    if(rt_update_lights(m_ctx, d.trigLights, d.trigLights ? d.lightInfo.trigLightSize : 0, d.puncLights, d.puncLights ? d.lightInfo.puncLightSize : 0, &d.lightInfo) != RT_OK) {
+      fprintf(stderr, "AccelStructure::setMaterials: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    return true;
+  }
+  bool setTexture(Scene& scene, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes)
+  {
+    if(rt_update_texture(m_ctx, texture, x, y, w, h, bgra, rowPitchBytes) != RT_OK) { fprintf(stderr, "AccelStructure::setTexture: %s\n", rt_last_error(m_ctx)); return false; }
+    if(!scene.setTexture(texture, x, y, w, h, bgra, rowPitchBytes)) { fprintf(stderr, "AccelStructure::setTexture: the scene refused the rectangle\n"); return false; }
+    return true;
+  }
+  rt_material_stats materialStats() const { rt_material_stats s{}; (void)rt_get_material_stats(m_ctx, &s); return s; }
   rt_instances_stats instancesStats() const { rt_instances_stats s{}; (void)rt_get_instances_stats(m_ctx, &s); return s; }
   rt_rebuild_stats rebuildStats() const { rt_rebuild_stats s{}; (void)rt_get_rebuild_stats(m_ctx, &s); return s; }
   void destroy() {}  // owned by the context

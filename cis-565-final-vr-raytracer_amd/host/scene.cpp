@@ -344,6 +344,41 @@ bool Scene::updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, co
   return true;
 }
 
+bool Scene::setMaterials(const uint32_t* ids, const rt_material* rows, uint32_t count, bool* lightsChanged)
+{
+  if(lightsChanged) *lightsChanged = false;
+  if(count && (!ids || !rows)) return false;
+  for(uint32_t k = 0; k < count; k++) {
+    if(ids[k] >= m_materials.size() || ids[k] >= m_gltf.materials.size()) return false;
+    const float* was = m_gltf.materials[ids[k]].emissiveFactor;
+    const V3 e{rows[k].emissiveFactor.x, rows[k].emissiveFactor.y, rows[k].emissiveFactor.z};
+    if((luminance(was) > 1e-2f) != (luminance(&e.x) > 1e-2f)) return false;   // the light rule: the emissive meshes are fixed by the scene
+  }
+  bool emission = false;
+  for(uint32_t k = 0; k < count; k++) {
+    m_materials[ids[k]] = rows[k];
+    float* e = m_gltf.materials[ids[k]].emissiveFactor;
+    const float n[3] = {rows[k].emissiveFactor.x, rows[k].emissiveFactor.y, rows[k].emissiveFactor.z};
+    if(memcmp(e, n, sizeof(n)) != 0) { memcpy(e, n, sizeof(n)); emission = true; }
+  }
+  if(emission) {   // the records' weights and the alias table depend on the emission
+    createTrigLightBuffer();
+    if(m_lightBufInfo.puncLightSize > 0 || m_lightBufInfo.trigLightSize > 0)
+      m_lightBufInfo.trigSampProb = m_trigLightWeight / (m_trigLightWeight + m_puncLightWeight);
+    if(lightsChanged) *lightsChanged = true;
+  }
+  return true;
+}
+
+bool Scene::setTexture(uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes)
+{
+  if(texture >= m_gltf.textures.size() || texture >= m_textures.size() || !bgra || w == 0 || h == 0 || rowPitchBytes < size_t(w) * 4) return false;
+  TextureImage& t = m_gltf.textures[texture];
+  if(uint64_t(x) + w > uint64_t(t.width) || uint64_t(y) + h > uint64_t(t.height) || t.bgra.size() < size_t(t.width) * size_t(t.height) * 4) return false;
+  for(uint32_t r = 0; r < h; r++) memcpy(t.bgra.data() + ((size_t(y) + r) * size_t(t.width) + x) * 4, bgra + size_t(r) * rowPitchBytes, size_t(w) * 4);
+  return true;
+}
+
 rt_scene_desc Scene::getDesc(const HdrSampling* env) const
 {
   rt_scene_desc d{};

@@ -98,6 +98,13 @@ class Scene {
   // positions in the loader's arrays, and the triangle-light records are recomputed as by updateInstances, so a deformed emitter lights from its new shape
   // (rt_update_vertices takes the same rows, rt_update_lights the records from getDesc()).  False (nothing changed) for a mesh or a range out of bounds.
   bool updateVertices(uint32_t primMesh, uint32_t first, uint32_t count, const rt_vertex* rows);
+  // Edit materials and texels on the host (include/rt_abi.h "Editing materials and textures"): rows replace the material rows `ids`; the loader's copy of a changed
+  // emissiveFactor follows and the triangle-light records are recomputed as by updateInstances (their count stays: a row may not move a material across the light
+  // rule, luminance of emissiveFactor > 1e-2, which both calls refuse).  setTexture replaces the w x h texels at (x, y) of one texture, row r at bgra + r
+  // rowPitchBytes.  False (nothing changed) for an id or a rectangle out of range, NULL data or a pitch below 4 w.  rt_update_materials / rt_update_texture take
+  // the same arguments; getDesc() afterwards describes the edited scene.  *lightsChanged (optional): an emission changed and the light records were recomputed.
+  bool setMaterials(const uint32_t* ids, const rt_material* rows, uint32_t count, bool* lightsChanged = nullptr);
+  bool setTexture(uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes);
   // The source of every triangle-light record, in the order createTrigLightBuffer emits them (include/rt_abi.h "Light sources"): record k is triangle
   // sources[k].triangle (index-list position / 3, relative to the prim mesh) of node = instance sources[k].instance.  rt_set_light_sources takes the list; the
   // update calls then move the records with the geometry on the device, and updateInstances / updateVertices + rt_update_lights are no longer needed for emitters.

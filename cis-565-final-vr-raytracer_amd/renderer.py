@@ -27,7 +27,8 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_set_object_motion", "rt_object_motion_camera", "rt_object_motion_readback", "rt_vertex_motion_readback",
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats", "rt_set_emitter_meshes", "rt_get_emitter_stats",
-               "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
+               "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats",
+               "rt_update_materials", "rt_update_texture", "rt_get_material_stats", "rt_opacity_map", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -165,6 +166,11 @@ def hip_lib():
             L.rt_set_morph_targets.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
             L.rt_update_morphs.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
             L.rt_get_morph_stats.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_update_materials"):   # editing materials and textures (absent from older A/B libraries)
+            L.rt_update_materials.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+            L.rt_update_texture.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_size_t]
+            L.rt_get_material_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_opacity_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "rt_get_primary_replay_stats"):   # settled primary visibility (absent from older A/B libraries)
             L.rt_get_primary_replay_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_primary_replay_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -610,6 +616,54 @@ class Renderer:
         self._chk(hip_lib().rt_get_morph_stats(self._h, C.byref(s)), "rt_get_morph_stats")
         return s
 
+    # ---- editing materials and textures (include/rt_abi.h "Editing materials and textures")
+    def update_materials(self, ids, rows):
+        """rt_update_materials: rows = abi.MATERIAL_DT records (or n x 80 bytes) that replace the material rows `ids`; the alpha records and opacity micro-maps of
+        the triangles whose alpha parameters or base colour texture changed are re-derived on the GPU; drains the frames in flight"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        rows = np.ascontiguousarray(rows).view(np.uint8).reshape(-1)
+        if rows.size != 80 * ids.size:
+            raise ValueError("update_materials: 80 bytes per id")
+        self._chk(hip_lib().rt_update_materials(self._h, ids.size, ids.ctypes.data, rows.ctypes.data), "rt_update_materials")
+
+    def update_texture(self, texture, x, y, bgra, row_pitch=None):
+        """rt_update_texture: bgra = (h, w, 4) uint8 texels that replace the rectangle at (x, y) of one texture.  row_pitch (bytes): the texels are handed over in
+        a staging buffer whose rows are that far apart (the padding is filled with 0xA5 and never read); a pitch below 4 w is passed on for the library to refuse"""
+        a = np.ascontiguousarray(bgra, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("update_texture: (h, w, 4) uint8 texels")
+        h, w = a.shape[0], a.shape[1]
+        pitch = 4 * w if row_pitch is None else int(row_pitch)
+        if pitch != 4 * w:   # a padded copy with the rows `pitch` bytes apart: what a host with a wider staging buffer hands over
+            if pitch < 4 * w:
+                self._chk(hip_lib().rt_update_texture(self._h, int(texture), int(x), int(y), w, h, a.ctypes.data, pitch), "rt_update_texture")
+                return
+            buf = np.full((h, pitch), 0xA5, dtype=np.uint8)
+            buf[:, :4 * w] = a.reshape(h, 4 * w)
+            a = buf
+        self._chk(hip_lib().rt_update_texture(self._h, int(texture), int(x), int(y), w, h, a.ctypes.data, pitch), "rt_update_texture")
+
+    def material_stats(self):
+        s = abi.MaterialStats()
+        self._chk(hip_lib().rt_get_material_stats(self._h, C.byref(s)), "rt_get_material_stats")
+        return s
+
+    @staticmethod
+    def opacity_map(uv, base_alpha, cutoff, alpha_mode, bgra=None, wrap_s=10497, wrap_t=10497, filter=9729):
+        """rt_opacity_map (no context, no GPU): the four micro-map words of one triangle — uv = 6 floats (uv0 uv1 uv2), bgra = (h, w, 4) uint8 or None"""
+        d = abi.OpacityMapDesc()
+        d.uv[:] = [float(v) for v in np.asarray(uv, dtype=np.float32).reshape(6)]
+        d.baseAlpha, d.cutoff, d.alphaMode, d.wrapS, d.wrapT, d.filter = float(base_alpha), float(cutoff), int(alpha_mode), int(wrap_s), int(wrap_t), int(filter)
+        tex = None
+        if bgra is not None:
+            tex = np.ascontiguousarray(bgra, dtype=np.uint8)
+            d.h, d.w = tex.shape[0], tex.shape[1]
+        out = (C.c_uint32 * 4)()
+        rc = hip_lib().rt_opacity_map(C.byref(d), tex.ctypes.data if tex is not None else None, out)
+        if rc != 0:
+            raise RtError(f"rt_opacity_map failed ({rc})")
+        return np.array(list(out), dtype=np.uint32)
+
     def primary_replay_stats(self):
         """rt_get_primary_replay_stats: state, K, the pixel classes of the recording in force and the launches recorded / replayed"""
         s = abi.PrimaryReplayStats()
@@ -688,9 +742,13 @@ class Renderer:
         return out
 
     def accel_readback(self, which, num_instances=None):
-        """the device tree as raw bytes: abi.ACCEL_NODES (80 B per node), ACCEL_TRIS (64 B per leaf record), ACCEL_INSTANCES (112 B per instance; pass num_instances)"""
+        """the device tree as raw bytes: abi.ACCEL_NODES (80 B per node), ACCEL_TRIS (64 B per leaf record), ACCEL_INSTANCES (112 B per instance; pass num_instances),
+        ACCEL_ALPHA (64 B per alpha record, view as abi.ALPHA_REC_DT; num_instances is then the record count, or None: 1 + the largest alphaIdx of the leaf records)"""
         st = self.accel_stats()
-        count = {abi.ACCEL_NODES: st["nodes"], abi.ACCEL_TRIS: st["references"], abi.ACCEL_INSTANCES: num_instances}[which]
+        if which == abi.ACCEL_ALPHA and num_instances is None:
+            tris = self.accel_readback(abi.ACCEL_TRIS).view(np.uint32).reshape(-1, 16)
+            num_instances = int(tris[:, 11].max()) + 1 if len(tris) else 1
+        count = {abi.ACCEL_NODES: st["nodes"], abi.ACCEL_TRIS: st["references"], abi.ACCEL_INSTANCES: num_instances, abi.ACCEL_ALPHA: num_instances}[which]
         out = np.empty(int(count) * abi.ACCEL_RECORD_BYTES[which], dtype=np.uint8)
         self._chk(hip_lib().rt_accel_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_accel_readback")
         return out

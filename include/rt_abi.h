@@ -768,7 +768,7 @@ typedef struct {
   float    triPad;        /* the hit rule's pad after the call */
   float    treePad;       /* the pad the tree's boxes are computed with (>= triPad) */
 } rt_refit_stats;         /* 32 B */
-enum { RT_ACCEL_NODES = 0, RT_ACCEL_TRIS = 1, RT_ACCEL_INSTANCES = 2 };
+enum { RT_ACCEL_NODES = 0, RT_ACCEL_TRIS = 1, RT_ACCEL_INSTANCES = 2, RT_ACCEL_ALPHA = 3 /* "Editing materials and textures" below */ };
 int rt_update_instances(rt_ctx* ctx, uint32_t count, const uint32_t* instanceIds, const float* objectToWorld);
 int rt_update_lights(rt_ctx* ctx, const rt_trig_light* trigLights, uint32_t numTrig, const rt_punc_light* puncLights, uint32_t numPunc, const rt_light_buf_info* info);
 int rt_get_refit_stats(rt_ctx* ctx, rt_refit_stats* out);
@@ -1191,6 +1191,63 @@ enum { RT_MORPH_NORMALS = 1, RT_MORPH_TANGENTS = 2 };
 int rt_set_morph_targets(rt_ctx* ctx, uint32_t numSets, const rt_morph_set* sets, uint64_t numDeltas, const rt_morph_delta* deltas);
 int rt_update_morphs(rt_ctx* ctx, uint32_t count, const uint32_t* setIds, const float* weights);
 int rt_get_morph_stats(rt_ctx* ctx, rt_morph_stats* out);
+/* ------------------------------------------------------------------------------------------------------------------
+ * Editing materials and textures (added within ABI 2.4, no version bump; csrc/materials.hip, csrc/opacity_map.h).  The plain fields of a material
+ * row are an 80-byte copy; what a new scene was needed for is the state DERIVED from a material's alpha parameters (pbrBaseColorFactor.w, alphaCutoff, alphaMode,
+ * pbrBaseColorTexture) and from the alpha channel of its base colour texture: one 64-byte alpha record per triangle that takes the alpha test, its copy in the
+ * latency build's per-record array, and one 8x8 opacity micro-map per such triangle (in the leaf records, in the device builder's table and in the templates of
+ * rt_set_instances).  The two calls below re-derive that state on the GPU for the triangles of the DIRTY materials, and for nothing else: a material is dirty when
+ * one of the four fields above changed bitwise, or when an alpha byte of its base colour texture changed.  If no material is dirty no kernel is launched.
+ * After either call the device material rows, the context's copy of them, the alpha records, the per-record copies, every affected micro-map and the templates
+ * hold the words that rt_upload_scene + rt_build_accel of the edited description would give (after rt_set_instances: in the per-mesh alphaIdx numbering of that
+ * section; a template of a mesh that has no alpha-tested instance in the current table is dropped and made again from the edited tables when a table needs it).
+ * The micro-map rule is stated once, in csrc/opacity_map.h; rt_opacity_map evaluates it on the host.  Two clarifications of the rule came with that header: a cell
+ * with a non-finite corner texcoord, or a corner beyond 2^31 - 4096 texels in magnitude, is "unknown" (state 0), where the scan used to convert the value to an
+ * integer that cannot hold it.
+ *
+ * rt_update_materials(ctx, count, materialIds, materials): materials[k] replaces row materialIds[k].  Valid after rt_upload_scene (RT_ERR_NO_SCENE otherwise);
+ *   before rt_build_accel it is a row copy into the context's and the device's tables.  The whole call is checked before anything changes; it joins the frames in
+ *   flight, as rt_update_instances does.  RT_ERR_INVALID_ARG, nothing changed, rt_last_error names the first offender: NULL arrays with count > 0; an id out of
+ *   range; an id listed twice; a row that fails the checks rt_upload_scene applies to a material row (a texture id outside the scene's textures); a row that moves
+ *   the material across the scene's light rule (luminance of emissiveFactor > 1e-2) in either direction: the emissive meshes are fixed by the scene, as for
+ *   rt_set_skins; while the emitter mode is on, a row that changes the luminance of emissiveFactor of an emissive material (the derived alias table would go
+ *   stale; a stated scope limit).  With the emitter mode off, light records stay the host's business, as at upload: a host that changed an emission follows with
+ *   rt_update_lights.  A HIP error after the checks (RT_ERR_HIP) may leave the call partly applied, as for the other update calls: upload the scene again.
+ * rt_update_texture(ctx, texture, x, y, w, h, bgra, rowPitchBytes): replaces the w x h texels at (x, y) of one texture, same size, same sampler; row r of the
+ *   rectangle starts at bgra + r rowPitchBytes.  RT_ERR_INVALID_ARG, nothing changed: a texture outside the scene's textures; an empty rectangle or one that
+ *   leaves the texture; rowPitchBytes < 4 w; NULL data.  Updates the device texels, the context's alpha plane and the plane's hash.  When an alpha byte inside the
+ *   rectangle differs, every material whose pbrBaseColorTexture is this texture is dirty; a texture used only as an emissive, normal or roughness texture, or an
+ *   edit that leaves every alpha byte as it was, launches nothing.
+ * Both: settled primary visibility is dropped; the reference-mode sums reset; NO history is invalidated: the material hash of the G-buffer and
+ *   ReSTIR's own lag apply, as for rt_update_lights.  The next rt_build_accel sees the edit in its cache key: a cached host build of the old scene is not reused.
+ *   rt_rebuild_accel, rt_update_instances and rt_set_instances commute with the edits.  Scope: the single-GPU context only; rt_mgpu_* contexts, rt_run_stage
+ *   hosts and restir_amd/tiled.py are unchanged.  Not covered: texture resizes, sampler changes, the emitter mode's re-derivation.
+ * rt_get_material_stats: what the last of the two calls that succeeded did.
+ * rt_opacity_map(desc, bgra, omm): no context, no GPU.  The four micro-map words of one triangle: uv = uv0 uv1 uv2, bgra = the w x h BGRA8 texels of the base
+ *   colour texture or NULL for none (w, h and the wrap modes are then not read).  RT_ERR_INVALID_ARG for NULL desc / omm or a texture with w <= 0 or h <= 0.
+ * rt_accel_readback(RT_ACCEL_ALPHA): the alpha records, 64 B each (record 0 is the all-zero record of opaque triangles; the count is 1 + the alpha-tested
+ *   triangles of a host tree, 1 + the triangles of all prim meshes once rt_set_instances has run); the 8 bytes of the texel address are replaced by the texture's
+ *   index as uint64, all ones for none, so that two contexts compare equal.  `bytes` may also be a smaller multiple of 64: the first bytes / 64 records.
+ * ---------------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  float uv[6];
+  float baseAlpha, cutoff;
+  int32_t alphaMode, w, h, wrapS, wrapT, filter;
+  uint32_t reserved[2];
+} rt_opacity_map_desc;         /* 64 B */
+typedef struct {
+  uint32_t materialsWritten;   /* rows the call copied (rt_update_texture: 0) */
+  uint32_t dirtyMaterials;     /* materials whose alpha records had to be re-derived */
+  uint32_t alphaRecords;       /* alpha records rebuilt (one micro-map each) */
+  uint32_t leafRecords;        /* leaf records rewritten */
+  uint64_t texelsScanned;      /* texels the build kernel read */
+  uint32_t bytesUploaded;      /* host -> device: material rows or texels, plus the dirty words */
+  float    ms;                 /* HIP-event time of the device work (copies and kernels) */
+} rt_material_stats;           /* 32 B */
+int rt_update_materials(rt_ctx* ctx, uint32_t count, const uint32_t* materialIds, const rt_material* materials);
+int rt_update_texture(rt_ctx* ctx, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes);
+int rt_get_material_stats(rt_ctx* ctx, rt_material_stats* out);
+int rt_opacity_map(const rt_opacity_map_desc* d, const uint8_t* bgra, uint32_t omm[4]);
 /* ---- Settled primary visibility -------------------------------------------------------------------------------------------------------
  * While the launch camera (viewInverse, projInverse, size: bitwise) and the scene stay what they were, full-frame direct launches of the throughput build stop
  * tracing the primary ray: the third launch at a camera (RESTIR_VIS_REST_FRAMES at-rest launches, default and minimum 2) also RECORDS per pixel the leaf record of
@@ -1255,6 +1312,7 @@ static_assert(sizeof(rt_morph_set) == 16, "rt_morph_set");
 static_assert(sizeof(rt_morph_delta) == 16, "rt_morph_delta");
 static_assert(sizeof(rt_morph_stats) == 32, "rt_morph_stats");
 static_assert(sizeof(rt_primary_replay_stats) == 32, "rt_primary_replay_stats");
+static_assert(sizeof(rt_opacity_map_desc) == 64 && sizeof(rt_material_stats) == 32, "rt_opacity_map_desc / rt_material_stats");
 #endif
 
 #endif /* RT_ABI_H */
