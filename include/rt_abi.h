@@ -1220,8 +1220,11 @@ int rt_get_morph_stats(rt_ctx* ctx, rt_morph_stats* out);
  *   edit that leaves every alpha byte as it was, launches nothing.
  * Both: settled primary visibility is dropped; the reference-mode sums reset; NO history is invalidated: the material hash of the G-buffer and
  *   ReSTIR's own lag apply, as for rt_update_lights.  The next rt_build_accel sees the edit in its cache key: a cached host build of the old scene is not reused.
- *   rt_rebuild_accel, rt_update_instances and rt_set_instances commute with the edits.  Scope: the single-GPU context only; rt_mgpu_* contexts, rt_run_stage
- *   hosts and restir_amd/tiled.py are unchanged.  Not covered: texture resizes, sampler changes, the emitter mode's re-derivation.
+ *   Every other call that edits a loaded scene commutes with the edits, in either order and any interleaving: rt_update_instances, rt_rebuild_accel (under either
+ *   builder of rt_set_rebuild_options), rt_build_accel, rt_set_instances (with and without the emitter mode), rt_update_vertices, rt_update_skins, rt_update_morphs,
+ *   rt_set_skins / rt_set_morph_targets (an edit may name the material of a mesh that has a skin or a morph set), rt_set_light_sources and rt_update_lights —
+ *   the state afterwards is that of rt_upload_scene + rt_build_accel of the description with all of them applied (tests/test_gpu_scene_edits.py).
+ *   Scope: the single-GPU context only; rt_mgpu_* contexts, rt_run_stage hosts and restir_amd/tiled.py are unchanged.  Not covered: texture resizes, sampler changes, the emitter mode's re-derivation.
  * rt_get_material_stats: what the last of the two calls that succeeded did.
  * rt_opacity_map(desc, bgra, omm): no context, no GPU.  The four micro-map words of one triangle: uv = uv0 uv1 uv2, bgra = the w x h BGRA8 texels of the base
  *   colour texture or NULL for none (w, h and the wrap modes are then not read).  RT_ERR_INVALID_ARG for NULL desc / omm or a texture with w <= 0 or h <= 0.

@@ -347,6 +347,13 @@ def clone(t):
     return c
 
 
+def clone_shallow(t):
+    """Tables that share every array with `t`: for readers (draw, draw_refusal) that need another instance table over the same rows and texels"""
+    c = Tables.__new__(Tables)
+    c.base, c.keep, c.mats, c.inst, c.tex_rows, c.texels = t.base, t.keep, t.mats, t.inst, t.tex_rows, t.texels
+    return c
+
+
 def apply(t, op):
     """the op on the tables (what a fresh context of t.desc() then uploads); a refused op changes nothing"""
     kind = op["kind"]

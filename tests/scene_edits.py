@@ -4,7 +4,7 @@ Twin: a host.Scene plus the per-mesh skin and morph state.  It mirrors every sce
 (Scene.updateInstances / setInstances / updateVertices; the posed rows from tests/skin_checker.cpp and tests/morph_checker.cpp, morph first, then skin), so
 Twin.desc() is at any point the description a host would upload from scratch.  It never reads anything back from a renderer.
 
-ops(scene, seed, n): a list of plain records (kind, args) over the alphabet KINDS + REFUSED.  The arguments are symbolic (instance ids and the name of a move,
+ops(scene, seed, n): a list of plain records (kind, args) over the alphabet KINDS + REFUSED (KINDS_V2 + REFUSED for a seed outside SEEDS, see "Two families").  The arguments are symbolic (instance ids and the name of a move,
 not matrices): Twin.calls() turns a record into the concrete calls against the twin's state at that point, so a sequence is reproducible from (scene, seed, n)
 alone and prints as a few lines of JSON.  Every call carries the CPU verdict of the ABI's refusal rules on it (instances.verdict for tables, the restated rules
 of the other calls below); the generator emits only records whose calls pass, except the one REFUSED record per sequence, whose call must fail.
@@ -16,24 +16,54 @@ are seeded random draws.
 
 What the alphabet leaves out on purpose: a re-bind may pass through the empty table (set_skins / set_morph_targets with no entries) but ends with one skin table
 and one morph table in place, and a morph set goes to a skinned mesh only once that skin has been posed — so that update_skins and update_morphs stay legal at
-every step and the order of the kinds can be planned without looking at the state."""
+every step and the order of the kinds can be planned without looking at the state.
+
+Two families.  Seeds in SEEDS walk KINDS, and their records are what they were before the alphabet was widened (tests/test_scene_edits_cpu.py holds their digest).
+Every other seed walks KINDS_V2 = KINDS + materials, texture, rebuild_options (rt_update_materials, rt_update_texture, rt_set_rebuild_options).
+The default sequences of the wider family (SCENES x SEEDS_V2, one seed per light mode) are drawn together over the 69 ordered pairs that have a new kind on a side:
+each walk takes its share and goes on with the pairs it has not held itself, so every sequence alternates old and new kinds.  Their records stay symbolic:
+  materials        a kind of materials.MATERIAL_KINDS, material ids and a seed; the rows are materials.draw over materials.of_scene(twin.sc), the twin follows with
+                   Scene.setMaterials.  model: rt_material_stats' dirtyMaterials (an alpha field changed bitwise) and alphaRecords (Twin.alpha_records).
+  texture          a kind of materials.RECT_KINDS, a texture, the material that steered the draw and a seed; the twin follows with Scene.setTexture.
+  rebuild_options  a builder and a radius of ploc.RADII; the twin remembers the options in force (they survive build_accel), what the last device build ran with,
+                   and whether PLOC's buffers exist: the first PLOC build on the working buffers makes rt_set_instances report a reallocation.
+The refusals of the three calls are restated from include/rt_abi.h in _update_materials, _update_texture and _set_rebuild_options (NULL arrays cannot be passed
+through the Renderer's methods and are left to tests/test_gpu_materials.py).  The generator steers three arguments and never the order of the kinds: where no instance takes
+the alpha test (Cornell as loaded) the next table change clears RT_INST_FORCE_OPAQUE of a non-emitter, and the next edit gives that instance's material a MASK
+mode; an edit of an alpha field names a material of an alpha-tested instance where there is one; the street sequences' refused record is one of each new call, the emitter-mode one's
+the luminance change that only that mode refuses.
+Emission: materials.MATERIAL_KINDS never touches emissiveFactor, so every fourth materials record is of the extra kind "emission": it scales the emissiveFactor of
+an emissive material inside the light rule (a row across the rule is a refusal).  In mode "update" the checkpoint's rt_update_lights carries the twin's records;
+in mode "binding" the row is followed by rt_update_lights, which include/rt_abi.h prescribes for a host that changed an emission and which leaves the binding in
+place (the light-source section defines that combination, so such rows are drawn in that mode too); in mode "emitter" the row is accepted only while the luminance
+keeps its bits, so the scale is 1 and the roughness alone changes — the row that changes the luminance is one of that mode's refusals.  The twin re-derives
+lightLuminIntegInv of its state after every accepted row, as a host does."""
 import tempfile
 from collections import namedtuple
 import numpy as np
 
 from helpers import abi, host
+import blend
 import emitters
 import instances
+import materials
 import morph
+import ploc
 import refit
 import skin
 
 KINDS = ("update_instances", "rebuild_accel", "build_accel", "set_instances", "set_emitters", "update_skins", "update_morphs", "update_vertices", "rebind", "lights")
+KINDS_V2 = KINDS + ("materials", "texture", "rebuild_options")      # the wider alphabet: DESIGN.md §31 and §32
+NEW_KINDS = KINDS_V2[len(KINDS):]
 REFUSED = "refused"
 UPDATES = ("update_instances", "update_skins", "update_morphs", "update_vertices")      # the kinds that refit the tree in place
 SCENES = ("cornell", "street")
-SEEDS = (1, 2, 3)
+SEEDS = (1, 2, 3)                       # these seeds walk KINDS; every other seed walks KINDS_V2
+SEEDS_V2 = (4, 5, 6)                    # the default sequences of the wider alphabet, one per light mode
 OPS, EVERY = 24, 4                      # ops per sequence; a checkpoint after every fourth op and after the last
+DEVICE_BUILDS = ("rebuild_accel", "set_instances", "set_emitters")      # the kinds that build a tree with the builder of rt_set_rebuild_options
+ALPHA_KINDS = ("cutoff", "base_alpha", "mode", "base_texture")          # the materials.MATERIAL_KINDS that change an alpha-relevant field
+TEXTURE_WORDS = (4, 7, 8, 12, 15)       # rt_material: base colour, metallic-roughness, emissive, normal, transmission texture
 MODES = ("binding", "update", "emitter")   # how a sequence keeps its light records current: rt_set_light_sources, rt_update_lights, rt_set_emitter_meshes
 SIZE = (67, 45)                         # test_gpu_refit.SIZES[1]: ragged tiles
 Libs = namedtuple("Libs", "inst skin morph")
@@ -53,6 +83,11 @@ def mode_of(seed):
     return MODES[seed % 3]
 
 
+def kinds_of_seed(seed):
+    """the alphabet a seed walks"""
+    return KINDS if seed in SEEDS else KINDS_V2
+
+
 def checkpoints(n):
     """the op indices after which a sequence of n ops is checked"""
     return [i for i in range(n) if (i + 1) % EVERY == 0 or i == n - 1]
@@ -66,9 +101,18 @@ def finite(a):
 
 
 class Twin:
-    def __init__(self, scene, mode, libs=None):
+    def __init__(self, scene, mode, libs=None, wide=False):
         self.libs = libs or build()
-        self.scene, self.mode = scene, mode
+        self.scene, self.mode, self.wide = scene, mode, wide      # wide: the sequence walks KINDS_V2 (the generator steers a few arguments, see _draw)
+        self.options = (ploc.LBVH, ploc.DEFAULT_RADIUS)      # rt_set_rebuild_options in force (builder, radius); they survive build_accel
+        self.ploc_buffers = False               # PLOC's buffers exist in the pool of the rebuild's working buffers
+        self.tree = "host"                      # "host": host tree and host alpha records; "rebuilt": a device tree over the host's alpha records (the builder's
+        #                                         table exists); "templates": rt_set_instances has put the per-mesh templates in force
+        self.built_with = None                  # the options the last device build ran with; None after a host build
+        self.pristine = True                    # nothing has changed the tree since the last host build: a fresh context numbers its alpha records alike
+        self.drawn = {"materials": 0, "texture": 0, "rebuild_options": 0}      # how many records of a kind the generator has drawn (their arguments take turns)
+        self.refuse = None                      # (call, reason or None) the generator's REFUSED record is held to (None: any)
+        self._tables = None                     # materials.Tables over the scene as it is now (_tables_of); dropped by every edit of rows, texels or the table
         self.sc = refit.cornell() if scene == "cornell" else refit.street()
         d = self.sc.desc()
         self.base = refit.instances_of(d)
@@ -114,6 +158,36 @@ class Twin:
     def free_meshes(self):
         """prim meshes rt_update_vertices accepts: no skin, no morph set, at least one vertex"""
         return [m for m in range(len(self.tris_of)) if self.vertex_count[m] and not self.skin_of(m) and not self.set_of(m)]
+
+    # ---- materials, textures and what an edit re-derives (include/rt_abi.h "Editing materials and textures")
+    def material_of_mesh(self):
+        """the material row of every prim mesh (an index below 0 reads row 0)"""
+        return np.maximum(refit.prim_meshes_of(self.sc.desc())["materialIndex"], 0)
+
+    def tested(self):
+        """instances of the current table that take the alpha test (no RT_INST_FORCE_OPAQUE)"""
+        return np.nonzero((self.table()["flags"] & instances.FORCE_OPAQUE) == 0)[0]
+
+    def hot_materials(self):
+        """materials of the alpha-tested instances: an edit of their alpha fields re-derives records"""
+        m = self.material_of_mesh()
+        return sorted(set(int(m[self.table()["primMesh"][i]]) for i in self.tested()))
+
+    def lit_materials(self):
+        """materials the scene's light rule calls emissive: luminance of emissiveFactor > 1e-2"""
+        return [k for k, row in enumerate(blend.materials_of(self.sc.desc())) if _luminance(row) > np.float32(1e-2)]
+
+    def deformed_materials(self):
+        """materials of the prim meshes that have a skin or a morph set now"""
+        m = self.material_of_mesh()
+        return sorted(set(int(m[s["sk"].mesh]) for s in self.skins) | set(int(m[s["mm"].mesh]) for s in self.sets))
+
+    def alpha_records(self, dirty):
+        """rt_material_stats.alphaRecords of an edit that makes the materials `dirty` dirty: on the host's alpha records one per (instance, triangle) pair of
+        their alpha-tested instances; once the templates are in force one per triangle of their prim meshes that have such an instance"""
+        table, m = self.table(), self.material_of_mesh()
+        mesh = [int(table["primMesh"][i]) for i in self.tested() if int(m[table["primMesh"][i]]) in dirty]
+        return int(sum(int(self.tris_of[k]) for k in (sorted(set(mesh)) if self.tree == "templates" else mesh)))
 
     def deformable(self):
         """prim meshes the sequences bind skins and morph sets to: the meshes the deform tests use, an emissive one where the light records can follow"""
@@ -192,10 +266,53 @@ class Twin:
                 yield Call("set_light_sources", (self.sc.lightSources(),), None, None)
             else:
                 yield Call("update_lights", (), None, None)      # (the description is the twin's at the time of the call)
+        elif kind == "materials":
+            yield self._update_materials(a["ids"], self._rows_for(a))
+            if a["kind"] == "emission" and a["scale"] != 1.0 and self.mode == "binding":      # a host that changed an emission follows with rt_update_lights, which
+                yield Call("update_lights", (), None, None)                                   # leaves the binding in place (in mode "update" the checkpoint's call does)
+        elif kind == "texture":
+            op = self._rect_for(a)
+            yield self._update_texture(op["texture"], op["x"], op["y"], op["texels"], op["pitch"])
+        elif kind == "rebuild_options":
+            yield self._set_rebuild_options(a["builder"], a["radius"])
         elif kind == REFUSED:
             yield self._refused(a)
         else:
             raise ValueError(kind)
+
+    def _tables_of(self, material=None):
+        """materials.Tables over the twin's scene; with `material`, over a one-row table that makes it the only material materials.draw can pick"""
+        if self._tables is None:      # (a copy of every texel: made once per edit, not once per question)
+            self._tables = materials.of_scene(self.sc)
+        t = materials.clone_shallow(self._tables)      # the rows and texels are shared and only read; the instance rows are the twin's current ones
+        t.inst = self.table()
+        if material is not None:
+            row = t.inst[:1].copy()
+            row["primMesh"], row["flags"] = int(np.nonzero(self.material_of_mesh() == material)[0][0]), 0
+            t.inst = row
+        return t
+
+    def _rows_for(self, a):
+        """the rows of a `materials` record: materials.draw of the record's kind, once per id, from the record's seed"""
+        rows = []
+        if a["kind"] == "emission":      # not one of materials.MATERIAL_KINDS: emissiveFactor times the record's scale (inside the light rule) and a drawn roughness
+            for k, m in enumerate(a["ids"]):
+                row = blend.materials_of(self.sc.desc())[m].copy()
+                row[blend.W_EMISSIVE] = (row[blend.W_EMISSIVE].view(np.float32) * np.float32(a["scale"])).view(np.uint32)
+                row[materials.W_ROUGHNESS] = materials.f2u(np.random.default_rng([a["seed"], k]).uniform(0.05, 1.0))
+                rows.append(row)
+            return np.stack(rows)
+        for k, m in enumerate(a["ids"]):
+            op = materials.draw(self._tables_of(m), np.random.default_rng([a["seed"], k]), a["kind"])
+            assert op["ids"] == [m], (op["ids"], m)
+            rows.append(op["rows"][0])
+        return np.stack(rows)
+
+    def _rect_for(self, a, tables=None):
+        """the rectangle of a `texture` record: materials.draw of the record's kind from the record's seed, over the tables the record's material selects"""
+        op = materials.draw(tables if tables is not None else self._tables_of(a["material"]), np.random.default_rng([a["seed"], 0]), a["kind"])
+        assert op["texture"] == a["texture"], (op["texture"], a)
+        return op
 
     def _table_for(self, kind, a):
         d, cur = self.sc.desc(), self.table()
@@ -248,7 +365,9 @@ class Twin:
         t = None if table is None else instances.rows(table)
         n, tris = (0, 0) if t is None else (len(t), int(self.tris_of[t["primMesh"][t["primMesh"] < len(self.tris_of)]].sum()))
         fits = self.cap is not None and tris <= self.cap[0] and n <= self.cap[1]
-        return Call("set_instances", (t,), None if code == instances.OK else "%s (instance %d)" % (instances.MESSAGE[code], off), {"reallocates": not fits})
+        first_ploc = self.options[0] == ploc.PLOC and not self.ploc_buffers      # the first PLOC build on the working buffers allocates PLOC's own
+        return Call("set_instances", (t,), None if code == instances.OK else "%s (instance %d)" % (instances.MESSAGE[code], off),
+                    {"reallocates": not fits or first_ploc, "fits": fits})
 
     def _update_skins(self, ids, joints):
         joints = np.ascontiguousarray(joints, np.float32).reshape(-1, 12)
@@ -317,6 +436,77 @@ class Twin:
             if self.vertices()["texcoord"][at:at + len(rows)].tobytes() != rows["texcoord"].tobytes():
                 why = "texcoord bits differ"
         return Call("update_vertices", (mesh, first, rows), why, None)
+
+    def _update_materials(self, ids, rows):
+        """rt_update_materials: refused for an id out of range, an id listed twice, a texture id outside the scene's textures, a row that crosses the light rule in
+        either direction, and — emitter mode on — a row that changes the luminance of an emissive material.  model: what rt_material_stats reports"""
+        ids = [int(i) for i in ids]
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, 20)
+        d = self.sc.desc()
+        cur = blend.materials_of(d)
+        why = None
+        if any(i >= len(cur) for i in ids):
+            why = "id out of range"
+        elif len(set(ids)) != len(ids):
+            why = "id listed twice"
+        else:
+            for i, row in zip(ids, rows):
+                tex = row[list(TEXTURE_WORDS)].view(np.int32)
+                was, now = _luminance(cur[i]), _luminance(row)
+                if ((tex < -1) | (tex >= int(d.numTextures))).any():
+                    why = "a missing texture"
+                elif (was > np.float32(1e-2)) != (now > np.float32(1e-2)):
+                    why = "the row crosses the light rule"
+                elif self.mode == "emitter" and was > np.float32(1e-2) and not was == now:
+                    why = "emitter mode: the luminance of an emissive material changes"
+                if why:
+                    break
+        model = None
+        if why is None:      # a field changed bitwise counts
+            words = list(materials.ALPHA_WORDS)
+            dirty = [i for i, row in zip(ids, rows) if not np.array_equal(row[words], cur[i][words])]
+            model = self._edit_model(dirty)
+        return Call("update_materials", (ids, rows), why, model)
+
+    def _update_texture(self, texture, x, y, texels, pitch=None):
+        """rt_update_texture: refused for a texture outside the scene's textures, an empty rectangle, one that leaves the texture, and a pitch below 4 w"""
+        t = self._tables_of()
+        h, w = texels.shape[:2]
+        why, model = None, None
+        if texture >= len(t.tex_rows):
+            why = "texture out of range"
+        elif w == 0 or h == 0:
+            why = "empty rectangle"
+        elif x + w > t.texture_size(texture)[0] or y + h > t.texture_size(texture)[1]:
+            why = "the rectangle leaves the texture"
+        elif pitch is not None and pitch < 4 * w:
+            why = "rowPitchBytes below 4 w"
+        else:      # an alpha byte changed counts: every material whose base colour texture this is
+            changed = not np.array_equal(t.texels[texture][y:y + h, x:x + w, 3], texels[..., 3])
+            dirty = [int(m) for m in np.nonzero(t.mats[:, blend.W_BASE_TEXTURE].view(np.int32) == texture)[0]] if changed else []
+            model = self._edit_model(dirty)
+        return Call("update_texture", (texture, x, y, texels, pitch), why, model)
+
+    def _edit_model(self, dirty):
+        """what rt_material_stats reports of an accepted edit, and where the edit falls: the state of the tree, the materials of the deformed meshes, whether
+        the tree is still the last host build's (the check after the edit then compares every word with a fresh context's, alphaIdx included)"""
+        return {"dirty": len(dirty), "records": self.alpha_records(dirty), "materials": dirty, "state": self.tree, "deformed": self.deformed_materials(),
+                "pristine": self.pristine}
+
+    def _set_rebuild_options(self, builder, radius=0, max_iterations=0):
+        """rt_set_rebuild_options: builder LBVH or PLOC, radius 0..64 (0: the default), maxIterations >= 0 (0: the default); anything else is refused"""
+        why = None
+        if builder not in (ploc.LBVH, ploc.PLOC):
+            why = "unknown builder"
+        elif not 0 <= radius <= 64:
+            why = "radius outside 0..64"
+        elif max_iterations < 0:
+            why = "negative maxIterations"
+        return Call("set_rebuild_options", (builder, radius, max_iterations), why, None)
+
+    def options_readback(self):
+        """rt_get_rebuild_options as the twin expects it: [builder, radius, maxIterations, reserved] (the sequences leave the iteration cap at its default)"""
+        return [self.options[0], self.options[1], ploc.DEFAULT_MAX_ITERATIONS, 0]
 
     def _emissive_refused(self, meshes):
         return self.mode == "update" and any(m in self.emissive_meshes for m in meshes)      # no binding: the host could no longer supply the light records
@@ -410,12 +600,48 @@ class Twin:
             return self._update_vertices(mesh, 0, rows)
         if call == "set_skins":
             return self._set_skins([self.free_meshes()[0]], 2, 0)      # refused while a morph set exists
+        if call == "materials":
+            t = self._tables_of()
+            if why == "emitter_luminance":      # twice as bright: inside the light rule, refused only while the emitter mode is on
+                m = self.lit_materials()[0]
+                row = t.mats[m].copy()
+                row[blend.W_EMISSIVE] = (row[blend.W_EMISSIVE].view(np.float32) * np.float32(2)).view(np.uint32)
+                return self._update_materials([m], row.reshape(1, 20))
+            op = materials.draw_refusal(t, np.random.default_rng(a["inst"]), why)
+            return self._update_materials(op["ids"], op["rows"])
+        if call == "texture":
+            op = materials.draw_refusal(self._tables_of(), np.random.default_rng(a["inst"]), why)
+            return self._update_texture(op["texture"], op["x"], op["y"], op["texels"], op["pitch"])
+        if call == "rebuild_options":
+            return self._set_rebuild_options(*{"builder": (2, 0, 0), "radius": (ploc.PLOC, 65, 0), "negative_radius": (ploc.PLOC, -1, 0), "iterations": (ploc.PLOC, 16, -1)}[why])
         raise ValueError(call)
 
     # ---- committing a call: the twin follows; returns the instances the call touched
     def commit(self, call):
         assert call.verdict is None, call.verdict
         name, d = call.name, self.sc.desc()
+        if name in ("update_instances", "update_skins", "update_morphs", "update_vertices", "rebuild_accel", "set_instances"):
+            self.pristine = False
+        if name in ("update_materials", "update_texture", "set_instances"):
+            self._tables = None
+        if name in ("update_materials", "update_texture"):      # touched: the alpha-tested instances of the dirty materials, so that the next rays are aimed at them
+            if name == "update_materials":
+                self.sc.setMaterials(call.args[0], call.args[1])
+                p, t = self.sc.lightWeights      # a changed emission changes the weight of the lights: the state a host derives from it (host.default_state)
+                self.st.lightLuminIntegInv = 1.0 / (p + t) if (p + t) > 0 else float("inf")
+            else:
+                texture, x, y, texels, _ = call.args
+                self.sc.setTexture(texture, x, y, texels)
+            m, table = self.material_of_mesh(), self.table()      # (... and at the first and the last instance: the edit may have made the others invisible)
+            return [int(i) for i in self.tested() if int(m[table["primMesh"][i]]) in call.model["materials"]] + [0, len(table) - 1]
+        if name == "set_rebuild_options":
+            self.options = (call.args[0], call.args[1] or ploc.DEFAULT_RADIUS)
+            return []
+        if name == "rebuild_accel":
+            self.tree = "rebuilt" if self.tree == "host" else self.tree
+            self.built_with = self.options
+            self.ploc_buffers |= self.options[0] == ploc.PLOC
+            return []
         if name == "update_instances":
             ids, xf = call.args
             self.emitter_moved |= bool(set(ids) & set(self.emitting()))
@@ -426,14 +652,18 @@ class Twin:
                 elif k == "back":
                     self.far.discard(i)
             return list(ids)
-        if name == "build_accel":
+        if name == "build_accel":      # a host build drops the rebuild's working buffers (PLOC's with them) and the templates' numbering; the options stay
             self.cap = None
+            self.tree, self.built_with, self.ploc_buffers, self.pristine = "host", None, False, True
             return []
         if name == "set_instances":
             old, new = self.table(), call.args[0]
-            if call.model["reallocates"]:
+            if not call.model["fits"]:
                 tris = int(self.tris_of[new["primMesh"]].sum())
                 self.cap = (tris + tris // 8, len(new) + len(new) // 8)
+                self.ploc_buffers = False      # new working buffers
+            self.ploc_buffers |= self.options[0] == ploc.PLOC
+            self.tree, self.built_with = "templates", self.options
             self.sc.setInstances(new)
             self.home = new["objectToWorld"].copy()
             self.far = set()
@@ -472,6 +702,12 @@ class Twin:
         return out, touched
 
 
+def _luminance(row):
+    """luminance of emissiveFactor of a material row (20 words) in fp32, term by term: what the scene's light rule compares with 1e-2"""
+    e = np.asarray(row, np.uint32)[blend.W_EMISSIVE].view(np.float32)
+    return np.float32(np.float32(e[0] * np.float32(0.2126) + e[1] * np.float32(0.7152)) + e[2] * np.float32(0.0722))
+
+
 def _spoil(m, why):
     m = m.copy()
     if why == "nan":
@@ -482,10 +718,12 @@ def _spoil(m, why):
 
 
 # ---- the order of the kinds -----------------------------------------------------------------------------------------------------------------------------------
-def _walk(rng, n, emitter, todo):
-    """n kinds with one REFUSED among them; every step prefers a pair (previous kind, kind) that is still in `todo`, and takes it out"""
-    allowed = [k for k in KINDS if emitter or k != "set_emitters"]
+def _walk(rng, n, emitter, todo, kinds=KINDS, quota=None):
+    """n kinds with one REFUSED among them; every step prefers a pair (previous kind, kind) that is still in `todo`, and takes it out.  quota: after that many
+    pairs (or once `todo` is empty) the walk leaves the rest of `todo` to the walks drawn after it and goes on over the pairs of pairs_v2() it has not held itself"""
+    allowed = [k for k in kinds if emitter or k != "set_emitters"]
     refused_at = int(rng.integers(2, max(3, n - 2)))
+    shared, taken = todo, 0
 
     def open_from(a):
         return sum((a, b) in todo for b in allowed)
@@ -503,7 +741,11 @@ def _walk(rng, n, emitter, todo):
         pick = [b for b in allowed if score[b] == best]
         b = pick[int(rng.integers(len(pick)))]
         if prev is not None:
+            taken += (prev, b) in todo
+            shared.discard((prev, b))
             todo.discard((prev, b))
+            if quota is not None and (taken >= quota or not shared) and todo is shared:      # from here on the pairs of its own that this walk has not held yet
+                todo = {p for p in pairs_v2() if all(k in allowed for k in p)} - set(zip(out, out[1:] + [b]))
         out.append(b)
         prev = b
     return out
@@ -527,20 +769,50 @@ def _default_plans(n, salt):
     return plans, todo
 
 
+SALT_V2 = 0      # where the wider family's search for a tie-break salt starts: the first start whose sequences meet every coverage condition of
+#                  tests/test_scene_edits_cpu.py (edits in each state of the tree, on a deformed mesh, under each builder ...), which looking at pairs alone does not give
+
+
+def pairs_v2():
+    """what the wider family has to cover: the 69 ordered pairs of KINDS_V2 with a new kind on at least one side"""
+    return {(a, b) for a in KINDS_V2 for b in KINDS_V2 if a in NEW_KINDS or b in NEW_KINDS}
+
+
+def _default_plans_v2(n, salt):
+    """the default sequences of the wider alphabet (SCENES x SEEDS_V2) drawn together, the emitter-mode ones first, over pairs_v2()"""
+    todo = pairs_v2()
+    slots = sorted(((sc, sd) for sc in SCENES for sd in SEEDS_V2), key=lambda s: (mode_of(s[1]) != "emitter", SCENES.index(s[0]), s[1]))
+    share = -(-len(todo) // len(slots))      # each walk but the last takes its share of the pairs and then goes on with pairs of its own: every sequence is dense in new kinds
+    plans = {s: _walk(np.random.default_rng([n, SCENES.index(s[0]), s[1], salt]), n, mode_of(s[1]) == "emitter", todo, KINDS_V2, share if k + 1 < len(slots) else n)
+             for k, s in enumerate(slots)}
+    return plans, todo
+
+
 def kinds_of(scene, seed, n):
     """the order of the kinds of one sequence"""
-    if seed in SEEDS:
-        if n not in _plans:      # the first tie-break salt that leaves no pair open (or, for a short n, the one that leaves the fewest)
+    if seed in SEEDS_V2:
+        if ("v2", n) not in _plans:      # as below, over the wider family
             best = None
-            for salt in range(64):
-                plans, left = _default_plans(n, salt)
+            for salt in range(SALT_V2, SALT_V2 + 64):
+                plans, left = _default_plans_v2(n, salt)
                 if best is None or len(left) < len(best[1]):
                     best = (plans, left)
                 if not left:
                     break
-            _plans[n] = best[0]
-        return list(_plans[n][(scene, seed)])
-    return _walk(np.random.default_rng([n, SCENES.index(scene), seed]), n, mode_of(seed) == "emitter", {(a, b) for a in KINDS for b in KINDS})
+            _plans[("v2", n)] = best[0]
+        return list(_plans[("v2", n)][(scene, seed)])
+    if seed not in SEEDS:
+        return _walk(np.random.default_rng([n, SCENES.index(scene), seed]), n, mode_of(seed) == "emitter", {(a, b) for a in KINDS_V2 for b in KINDS_V2}, KINDS_V2)
+    if n not in _plans:      # the first tie-break salt that leaves no pair open (or, for a short n, the one that leaves the fewest)
+        best = None
+        for salt in range(64):
+            plans, left = _default_plans(n, salt)
+            if best is None or len(left) < len(best[1]):
+                best = (plans, left)
+            if not left:
+                break
+        _plans[n] = best[0]
+    return list(_plans[n][(scene, seed)])
 
 
 # ---- the arguments --------------------------------------------------------------------------------------------------------------------------------------------
@@ -567,6 +839,9 @@ def _draw(kind, t, rng):
     if kind == "set_instances":
         plain = [i for i in range(n) if int(cur["primMesh"][i]) not in t.emissive_meshes and t.tris_of[cur["primMesh"][i]] <= 64]
         alpha = [i for i in range(n) if int(cur["primMesh"][i]) in t.alpha_meshes]
+        steer = t.wide and not len(t.tested())      # no instance takes the alpha test (Cornell as loaded): a flip clears RT_INST_FORCE_OPAQUE of a non-emitter first
+        if steer:
+            alpha = [i for i in range(n) if int(cur["primMesh"][i]) not in t.emissive_meshes]
         room = (t.cap[1] - n + 1) if t.cap is not None else 2
         variants = [{"how": "append", "src": pick(plain), "move": pick(("mirror", "scale", "rotate")), "shift": [round(float(x), 3) for x in rng.uniform(-0.15, 0.15, 3)]},
                     {"how": "delete", "inst": max(i for i in range(n) if int(cur["primMesh"][i]) not in t.emissive_meshes)},      # the last non-emitter
@@ -579,6 +854,8 @@ def _draw(kind, t, rng):
         order = [(turn + k) % len(variants) for k in range(len(variants))]
         if n > len(t.base) + 10:      # large enough: shrink first
             order = [3] + [k for k in order if k not in (0, 2, 3)] + [0]
+        if steer:
+            order = [4] + [k for k in order if k != 4]
         for k in order:
             a = variants[k]
             if (a["how"] == "shrink" and a["count"] < 1) or (a["how"] == "grow" and n + a["count"] > len(t.base) + 16):
@@ -629,12 +906,51 @@ def _draw(kind, t, rng):
         if len(ok) > 1 and rng.random() < 0.4:
             morphs.append(pick([m for m in ok if m not in morphs]))
         return {"skins": None, "morphs": morphs, "via_empty": via_empty, "seed": seed}
+    if kind in NEW_KINDS:      # their arguments take turns, from a start that differs per sequence, so that a few sequences reach every variant
+        turn = 3 * SCENES.index(t.scene) + MODES.index(t.mode) + t.drawn[kind]
+        t.drawn[kind] += 1
+        lit = t.lit_materials()
+        hot = [m for m in t.hot_materials() if m not in lit]
+    if kind == "materials" and lit and t.drawn[kind] % 4 == 2:      # every fourth record, from the second on, changes an emission without crossing the light rule: the
+        # emitter mode accepts the row only while the luminance keeps its bits (scale 1: the roughness alone changes)
+        a = {"kind": "emission", "ids": [lit[0]], "seed": int(rng.integers(1, 1 << 20)), "scale": 1.0 if t.mode == "emitter" else float(pick([0.5, 1.5, 2.0]))}
+        if t._update_materials(a["ids"], t._rows_for(a)).verdict is not None:      # (dimmed down to the light rule: brighter instead)
+            a["scale"] = 2.0
+        return a
+    if kind == "materials":
+        mk = materials.MATERIAL_KINDS[turn % len(materials.MATERIAL_KINDS)]
+        mats = blend.materials_of(t.sc.desc())
+        plain = [m for m in hot if mats[m, blend.W_ALPHA_MODE] == blend.ALPHA_OPAQUE]
+        if hot and len(plain) == len(hot):      # every alpha-tested instance still has an OPAQUE material (Cornell after its flip): the first edit gives one a MASK
+            mk, hot = "mode", plain
+        cold = [m for m in sorted(set(int(m) for m in t.material_of_mesh())) if m not in lit and m not in hot]
+        ids = [pick(hot)] if hot and (mk in ALPHA_KINDS or not cold or rng.random() < 0.5) else [pick(cold)]
+        rest = [m for m in hot + cold if m not in ids]
+        if rest and rng.random() < 0.35:
+            ids.append(pick(rest))
+        return {"kind": mk, "ids": ids, "seed": int(rng.integers(1, 1 << 20))}
+    if kind == "texture":
+        rk = materials.RECT_KINDS[turn % len(materials.RECT_KINDS)]
+        mats = blend.materials_of(t.sc.desc())
+        textured = [m for m in hot if mats[m, blend.W_BASE_TEXTURE].view(np.int32) >= 0]
+        material = pick(textured) if textured and rng.random() < 0.8 else None      # mostly a texture whose alpha an alpha-tested instance reads
+        seed = int(rng.integers(1, 1 << 20))
+        op = materials.draw(t._tables_of(material), np.random.default_rng([seed, 0]), rk)
+        return {"kind": rk, "texture": int(op["texture"]), "material": material, "seed": seed}
+    if kind == "rebuild_options":      # always the other builder, so every record switches
+        return {"builder": ploc.LBVH if t.options[0] == ploc.PLOC else ploc.PLOC, "radius": int(ploc.RADII[turn % len(ploc.RADII)])}
     if kind == REFUSED:
         cases = [("update_instances", w) for w in ("range", "twice", "nan", "singular")] + [("set_instances", w) for w in ("nan", "singular", "prim_mesh", "empty")] + \
                 [("update_skins", w) for w in ("range", "nan")] + [("update_morphs", w) for w in ("range", "twice", "nan")] + \
                 [("update_vertices", w) for w in ("outside", "nan", "skinned")] + [("set_skins", "morphs_exist")]
+        if t.wide:
+            cases += [("materials", w) for w in ("id_range", "duplicate", "bad_texture", "light_rule_on", "light_rule_off", "emitter_luminance")] + \
+                     [("texture", w) for w in ("texture_range", "empty_rect", "rect_outside", "pitch")] + \
+                     [("rebuild_options", w) for w in ("builder", "radius", "negative_radius", "iterations")]
         if t.mode != "emitter" and t.emitting():
             cases.append(("set_instances", "emitter_moved"))
+        if t.refuse:      # (the default street sequences of the wider family: one per new call, so that the six hold a refusal of each)
+            cases = [c for c in cases if c[0] == t.refuse[0] and t.refuse[1] in (None, c[1])]
         for k in rng.permutation(len(cases)):
             a = {"call": cases[int(k)][0], "why": cases[int(k)][1], "inst": int(rng.integers(n))}
             if t._refused(a).verdict is not None:
@@ -645,12 +961,20 @@ def _draw(kind, t, rng):
 _ops = {}
 
 
+def twin_of(scene, seed):
+    """the twin a sequence starts from, before its set-up"""
+    t = Twin(scene, mode_of(seed), wide=seed not in SEEDS)
+    if seed in SEEDS_V2 and scene == "street":      # one refusal of each new call; the emitter-mode sequence holds the refusal only that mode has
+        t.refuse = {"update": ("texture", None), "emitter": ("materials", "emitter_luminance"), "binding": ("rebuild_options", None)}[t.mode]
+    return t
+
+
 def ops(scene, seed, n=OPS):
     """the records of one sequence: [(kind, args)]"""
     key = (scene, seed, n)
     if key not in _ops:
         rng = np.random.default_rng([SCENES.index(scene), seed, n, 8])
-        t = Twin(scene, mode_of(seed))
+        t = twin_of(scene, seed)
         for call in t.setup():
             t.commit(call)
         out = []
@@ -662,10 +986,9 @@ def ops(scene, seed, n=OPS):
     return [(k, dict(a)) for k, a in _ops[key]]
 
 
-def replay(scene, seed, n=OPS):
-    """(twin after its set-up, the records): what a runner starts from"""
-    t = Twin(scene, mode_of(seed))
-    return t, ops(scene, seed, n)
+def replay(scene, seed, n=OPS, records=None):
+    """(twin before its set-up, the records): what a runner starts from.  `records`: these instead of the generated ones (a hand-written sequence)"""
+    return twin_of(scene, seed), ops(scene, seed, n) if records is None else [(k, dict(a)) for k, a in records]
 
 
 def touched_or_ends(touched, count):
@@ -684,22 +1007,24 @@ def aimed_rays(desc, touched, seed, f):
 _frames = {}
 
 
-def oracle_frames(scene, seed, n=OPS):
-    """[{buffer: bytes}] per checkpoint: the oracle is given twin.desc() before each frame, as test_gpu_refit.Sequence.oracle_frames does"""
+def oracle_frames(scene, seed, n=OPS, records=None, forget=()):
+    """[{buffer: bytes}] per checkpoint: the oracle is given twin.desc() before each frame, as test_gpu_refit.Sequence.oracle_frames does.  `records` / `forget`: a
+    hand-written sequence, and the indices of its records that the twin does not follow (tests/test_gpu_scene_edits.py, the forgetful drivers); not kept"""
     from helpers import frame_buffers
     from oracle.binding import Oracle
     key = (scene, seed, n)
-    if key not in _frames:
+    if key not in _frames or records is not None:
         W, H = SIZE
-        t, records = replay(scene, seed, n)
+        t, records_ = replay(scene, seed, n, records)
         for call in t.setup():
             t.commit(call)
         o = Oracle(0)
         o.upload_scene(t.desc())
         o.resize(W, H)
-        out, marks = [], checkpoints(n)
-        for i, op in enumerate(records):
-            t.apply(op)
+        out, marks = [], checkpoints(len(records_))
+        for i, op in enumerate(records_):
+            if i not in forget:
+                t.apply(op)
             if i in marks:
                 f = len(out)
                 cam = t.camera(f, W, H)
@@ -707,5 +1032,7 @@ def oracle_frames(scene, seed, n=OPS):
                 o.set_camera(cam)
                 o.render_frame(t.st, f)
                 out.append({b: o.readback(b).copy() for b in frame_buffers(f)})
+        if records is not None:
+            return out
         _frames[key] = out
     return _frames[key]
