@@ -169,6 +169,18 @@ class MaterialStats(C.Structure):  # rt_material_stats, 32 B
 
 
 assert ALPHA_REC_DT.itemsize == 64 and MATERIAL_DT.itemsize == 80 and C.sizeof(OpacityMapDesc) == 64 and C.sizeof(MaterialStats) == 32
+# rt_environment_readback ids; rt_impt_samp (16 B) as a numpy row
+ENV_TEXELS, ENV_ACCEL = range(2)
+IMPT_SAMP_DT = np.dtype([("alias", "<i4"), ("q", "<f4"), ("pdf", "<f4"), ("aliasPdf", "<f4")])
+ENV_MAX_TEXELS = 1 << 23   # the device build's (and rt_env_accel's) limit
+
+
+class EnvironmentStats(C.Structure):  # rt_environment_stats, 40 B
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("integral", C.c_float), ("average", C.c_float), ("numSmall", C.c_uint32), ("numLarge", C.c_uint32),
+                ("builtOnDevice", C.c_uint32), ("ms", C.c_float), ("deviceBytes", C.c_uint64)]
+
+
+assert IMPT_SAMP_DT.itemsize == 16 and C.sizeof(EnvironmentStats) == 40
 OBJECT_MOTION_OFF, OBJECT_MOTION_ON, OBJECT_MOTION_VERTEX = 0, 1, 3   # rt_set_object_motion (VERTEX: per-vertex motion vectors; 2 is not a mode)
 
 

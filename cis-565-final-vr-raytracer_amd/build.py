@@ -17,7 +17,7 @@ HOST_LIB = os.path.join(_HERE, "host", "librestir_host.so")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
              "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize", "-Wno-unused-result", "-x", "hip"]
 # translation units compiled once
-HIP_SRC = ["rt_api.cpp", "mgpu.cpp", "bvh8_builder.cpp", "filters.hip", "post.hip", "microbench.hip", "svgf.hip", "gi_spatial.hip", "taa.hip", "upscale.hip", "refit.hip", "accel_build.hip", "instances.hip", "deform.hip", "light_records.hip", "light_derive.hip", "morph.hip", "vmotion.hip", "materials.hip"]
+HIP_SRC = ["rt_api.cpp", "mgpu.cpp", "bvh8_builder.cpp", "filters.hip", "post.hip", "microbench.hip", "svgf.hip", "gi_spatial.hip", "taa.hip", "upscale.hip", "refit.hip", "accel_build.hip", "instances.hip", "deform.hip", "light_records.hip", "light_derive.hip", "morph.hip", "vmotion.hip", "materials.hip", "env_accel.hip"]
 # THE table of the builds of the traced stages: csrc/stages.hip is compiled once per entry with -D<switch>=1 for each switch (what the switches do: the note at the
 # top of stages.hip).  The name is the build's namespace, which stages.hip pastes from the same switches, and one of RT_STAGE_BUILDS in csrc/stage_select.h, where
 # the rule that picks a build per launch lives (tests/test_stage_select_cpu.py holds the two lists together; DESIGN.md §28: adding a build).

@@ -36,6 +36,7 @@
 #include "light_derive.h"
 #include "opacity_map.h"
 #include "materials.h"
+#include "env_accel.h"
 #include "../host/alias_table.hpp"
 #include "dev_math.h"
 
@@ -266,6 +267,18 @@ struct rt_ctx {
   hipEvent_t evMat[2] = {nullptr, nullptr};      // around the device work of the last edit
   uint32_t numTextures = 0;
   size_t hostNumAlpha = 0;
+  // rt_set_environment (csrc/env_accel.hip).  Two pairs of (map, table): a call fills the pair that DevScene does not name and DevScene takes it
+  // only when the call is accepted.  live = -1: DevScene names the scene's own pair (sceneAllocs, rt_upload_scene).  A pair grows to the largest map it has held;
+  // the work arrays of the device build (row areas, W, prefixes, ranks, tile sums, counters) likewise.  rt_upload_scene frees everything.
+  struct Env {
+    struct Pair { float* texels = nullptr; rt_impt_samp* accel = nullptr; size_t cap = 0; } pair[2];
+    int live = -1;
+    float* dArea = nullptr; size_t areaCap = 0;
+    uint64_t* dW = nullptr; EnvU128* dP = nullptr; uint32_t* dIdx = nullptr; EnvBlockSum* dBlockSums = nullptr; uint32_t* dCounters = nullptr;
+    size_t workCap = 0;
+    rt_environment_stats stats{};
+  } env;
+  hipEvent_t evEnv[2] = {nullptr, nullptr};      // around the device work of the last accepted call
   // rt_set_object_motion (the RT_OM builds of csrc/stages.hip).  omPrev[i] is instance i's objectToWorld at the last rendered frame where omMoved[i]
   // is set (rt_update_instances records it once per frame; every other instance's previous matrix is its current one); a rendered frame clears the flags.
   int objMotion = RT_OBJECT_MOTION_OFF;
@@ -645,6 +658,16 @@ template <class T> static int allocZeroed(rt_ctx* c, std::vector<void*>& pool, s
   return rc;
 }
 static void freePool(std::vector<void*>& pool) { for(void* p : pool) (void)hipFree(p); pool.clear(); }
+// what rt_set_environment allocated (the caller has drained the context and no longer lets c->ds name a pair); the statistics go with it
+static void freeEnvironment(rt_ctx* c)
+{
+  rt_ctx::Env& E = c->env;
+  for(auto& p : E.pair) { if(p.texels) (void)hipFree(p.texels); if(p.accel) (void)hipFree(p.accel); }
+  for(void* p : {static_cast<void*>(E.dArea), static_cast<void*>(E.dW), static_cast<void*>(E.dP), static_cast<void*>(E.dIdx), static_cast<void*>(E.dBlockSums),
+                 static_cast<void*>(E.dCounters)})
+    if(p) (void)hipFree(p);
+  E = rt_ctx::Env{};
+}
 // the emitter mode leaves the context: templates and derived light buffers go (the caller has drained the context and replaces what c->ds.trigLights names)
 static void dropEmitters(rt_ctx* c)
 {
@@ -775,6 +798,8 @@ int rt_destroy(rt_ctx* c)
   for(hipEvent_t e : c->evEmit) if(e) (void)hipEventDestroy(e);
   for(hipEvent_t e : c->evMat) if(e) (void)hipEventDestroy(e);
   freePool(c->matAllocs);
+  for(hipEvent_t e : c->evEnv) if(e) (void)hipEventDestroy(e);
+  freeEnvironment(c);
   delete c;
   if(g_liveCtx.fetch_sub(1) == 1) { std::lock_guard<std::mutex> one(g_accelMutex); g_accelCache.reset(); }   // the last context takes the cached host build with it
   return RT_OK;
@@ -855,6 +880,7 @@ int rt_upload_scene(rt_ctx* c, const rt_scene_desc* d)
   freePool(c->matAllocs);     // ... and the material edits' device words are sized again
   c->mat = rt_ctx::Materials{};
   c->numTextures = uint32_t(nTex); c->hostNumAlpha = 0;
+  freeEnvironment(c);         // ... and the environment is the scene's own again
   c->deform = rt_ctx::Deform{};
   c->refit = rt_ctx::Refit{};
   c->rebuild = rt_ctx::Rebuild{};
@@ -3378,6 +3404,172 @@ int rt_opacity_map(const rt_opacity_map_desc* d, const uint8_t* bgra, uint32_t o
 {
   if(!d || !omm || (bgra && (d->w <= 0 || d->h <= 0))) return RT_ERR_INVALID_ARG;
   ommBuildSerial(d->uv, d->baseAlpha, d->cutoff, d->alphaMode, d->w, d->h, d->wrapS, d->wrapT, bgra ? bgra + 3 : nullptr, 4, omm);
+  return RT_OK;
+}
+
+}  // extern "C"
+
+/* ---- the environment (include/rt_abi.h "The environment", csrc/env_accel.hip, csrc/env_accel.h) ---- */
+// one device array of the environment's, at least `count` elements: kept when it is large enough, else freed and made again (cap follows)
+template <class T> static int ensureEnvArray(rt_ctx* c, T** p, size_t* cap, size_t count)
+{
+  if(*p && *cap >= count) return RT_OK;
+  if(*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+  void* d = nullptr;
+  RT_HIP(c, hipMalloc(&d, std::max<size_t>(count, 1) * sizeof(T)));
+  *p = static_cast<T*>(d); *cap = count;
+  return RT_OK;
+}
+static uint64_t envDeviceBytes(const rt_ctx::Env& E)
+{
+  uint64_t b = 0;
+  for(const auto& p : E.pair) b += (p.texels ? p.cap * 16 : 0) + (p.accel ? p.cap * sizeof(rt_impt_samp) : 0);
+  if(E.dArea) b += E.areaCap * 4;
+  if(E.dW) b += E.workCap * (sizeof(uint64_t) + sizeof(EnvU128) + 4) + ((E.workCap + ENV_SCAN_TILE - 1) / ENV_SCAN_TILE) * sizeof(EnvBlockSum) + ENV_CNT_WORDS * 4;
+  return b;
+}
+
+extern "C" {
+
+int rt_set_environment(rt_ctx* c, int width, int height, const float* rgba32f, const rt_impt_samp* accel)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_set_environment: no scene uploaded");
+  if(width < 0 || height < 0) return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: negative size");
+  // the 1 x 1 black map of rt_upload_scene
+  static const float black[4] = {0, 0, 0, 0};
+  static const rt_impt_samp one{0, 1.0f, 0.0f, 0.0f};
+  if(width == 0 || height == 0 || !rgba32f) { width = height = 1; rgba32f = black; accel = &one; }
+  const uint64_t n = uint64_t(width) * uint64_t(height);
+  if(n > 0x7fffffffull) return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: more than 2^31 - 1 texels (alias is an int32)");
+  if(!accel && n > ENV_MAX_TEXELS) return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: more than 2^23 texels and no table: the device build's integer range");
+  if(accel) {   // the copy path's checks run on the host: the table as rt_upload_scene checks it, the texels for +inf
+    for(uint64_t i = 0; i < n; i++)
+      if(accel[i].alias < 0 || uint64_t(accel[i].alias) >= n) return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: environment alias table entry out of range");
+    for(uint64_t i = 0; i < n; i++)
+      if(envIsPosInf(rgba32f[i * 4]) || envIsPosInf(rgba32f[i * 4 + 1]) || envIsPosInf(rgba32f[i * 4 + 2]))
+        return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: a texel is +inf");
+  }
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));   // joins the frames in flight, like the other edits
+  if(const hipError_t he = ensureEvents(c->evEnv)) return hipFail(c, "hipEventCreate(&e)", he);
+  rt_ctx::Env& E = c->env;
+  hipStream_t s = c->stream;
+  const int target = E.live == 0 ? 1 : 0;   // the pair DevScene does not name
+  rt_ctx::Env::Pair& P = E.pair[target];
+  if(P.cap < n) {
+    if(P.texels) (void)hipFree(P.texels);
+    if(P.accel) (void)hipFree(P.accel);
+    P = rt_ctx::Env::Pair{};
+    size_t cap = 0;
+    float4* t = nullptr;
+    int rc = ensureEnvArray(c, &t, &cap, size_t(n));
+    P.texels = reinterpret_cast<float*>(t);
+    if(!rc) { cap = 0; rc = ensureEnvArray(c, &P.accel, &cap, size_t(n)); }
+    if(rc) { if(P.texels) (void)hipFree(P.texels); P = rt_ctx::Env::Pair{}; return rc; }
+    P.cap = size_t(n);
+  }
+  uint32_t counters[ENV_CNT_WORDS] = {};
+  std::vector<float> area;
+  RT_HIP(c, hipEventRecord(c->evEnv[0], s));
+  RT_HIP(c, hipMemcpyAsync(P.texels, rgba32f, size_t(n) * 16, hipMemcpyHostToDevice, s));
+  if(accel) RT_HIP(c, hipMemcpyAsync(P.accel, accel, size_t(n) * sizeof(rt_impt_samp), hipMemcpyHostToDevice, s));
+  else {
+    int rc = ensureEnvArray(c, &E.dArea, &E.areaCap, size_t(height));
+    if(!rc && !(E.dW && E.workCap >= n)) {
+      for(void* p : {static_cast<void*>(E.dW), static_cast<void*>(E.dP), static_cast<void*>(E.dIdx), static_cast<void*>(E.dBlockSums), static_cast<void*>(E.dCounters)})
+        if(p) (void)hipFree(p);
+      E.dW = nullptr; E.dP = nullptr; E.dIdx = nullptr; E.dBlockSums = nullptr; E.dCounters = nullptr; E.workCap = 0;
+      size_t cap = 0;
+      const size_t tiles = (size_t(n) + ENV_SCAN_TILE - 1) / ENV_SCAN_TILE;
+      rc = ensureEnvArray(c, &E.dW, &cap, size_t(n));
+      if(!rc) { cap = 0; rc = ensureEnvArray(c, &E.dP, &cap, size_t(n)); }
+      if(!rc) { cap = 0; rc = ensureEnvArray(c, &E.dIdx, &cap, size_t(n)); }
+      if(!rc) { cap = 0; rc = ensureEnvArray(c, &E.dBlockSums, &cap, tiles); }
+      if(!rc) { cap = 0; rc = ensureEnvArray(c, &E.dCounters, &cap, size_t(ENV_CNT_WORDS)); }
+      if(!rc) E.workCap = size_t(n);
+    }
+    if(rc) return rc;
+    area.resize(size_t(height));
+    envRowAreas(width, height, area.data());
+    EnvBuildArgs a{};
+    a.texels = P.texels; a.area = E.dArea; a.accel = P.accel; a.W = E.dW; a.P = E.dP; a.idx = E.dIdx; a.blockSums = E.dBlockSums; a.counters = E.dCounters;
+    a.n = uint32_t(n); a.w = uint32_t(width);
+    RT_HIP(c, hipMemcpyAsync(E.dArea, area.data(), area.size() * 4, hipMemcpyHostToDevice, s));
+    RT_HIP(c, hipMemsetAsync(E.dCounters, 0, sizeof(counters), s));
+    RT_HIP(c, launchEnvAccelBuild(s, a));
+    RT_HIP(c, hipMemcpyAsync(counters, E.dCounters, sizeof(counters), hipMemcpyDeviceToHost, s));
+  }
+  RT_HIP(c, hipEventRecord(c->evEnv[1], s));
+  RT_HIP(c, hipStreamSynchronize(s));
+  if(!accel && counters[ENV_CNT_BAD]) return fail(c, RT_ERR_INVALID_ARG, "rt_set_environment: a texel is +inf, or its importance or luminance overflows to +inf");
+  // accepted: DevScene takes the pair
+  dropPrimaryReplay(c);   // miss pixels carry the environment's radiance in the G-buffer
+  E.live = target;
+  c->ds.env = P.texels; c->ds.envAccel = P.accel; c->ds.envW = width; c->ds.envH = height;
+  c->refN = 0;            // the scene changed: the reference sums start again
+  rt_environment_stats st{};
+  st.width = width; st.height = height;
+  if(!accel) {
+    float M, ML;
+    memcpy(&M, &counters[ENV_CNT_MAX_IMP], 4); memcpy(&ML, &counters[ENV_CNT_MAX_LUM], 4);
+    const uint64_t T = uint64_t(counters[ENV_CNT_T]) | (uint64_t(counters[ENV_CNT_T + 1]) << 32), TL = uint64_t(counters[ENV_CNT_TL]) | (uint64_t(counters[ENV_CNT_TL + 1]) << 32);
+    st.integral = float(envUnscale(T, envScaleExp(M)));
+    st.average = float(envUnscale(TL, envScaleExp(ML)) / double(n));
+    st.numSmall = counters[ENV_CNT_SMALL]; st.numLarge = uint32_t(n) - st.numSmall;
+    st.builtOnDevice = 1;
+  }
+  (void)hipEventElapsedTime(&st.ms, c->evEnv[0], c->evEnv[1]);
+  st.deviceBytes = envDeviceBytes(E);
+  E.stats = st;
+  return RT_OK;
+}
+
+int rt_environment_readback(rt_ctx* c, int which, void* dst, size_t bytes)
+{
+  if(!c) return RT_ERR_INVALID_ARG;
+  if(!c->haveScene) return fail(c, RT_ERR_NO_SCENE, "rt_environment_readback: no scene uploaded");
+  if(which != RT_ENV_TEXELS && which != RT_ENV_ACCEL) return fail(c, RT_ERR_INVALID_ARG, "rt_environment_readback: which must be RT_ENV_TEXELS / RT_ENV_ACCEL");
+  const size_t want = size_t(c->ds.envW) * size_t(c->ds.envH) * 16;
+  if(bytes != want || !dst) return fail(c, RT_ERR_INVALID_ARG, "rt_environment_readback: size mismatch");
+  RT_HIP(c, hipSetDevice(c->device));
+  RT_HIP(c, syncAll(c));
+  RT_HIP(c, hipMemcpy(dst, which == RT_ENV_TEXELS ? static_cast<const void*>(c->ds.env) : static_cast<const void*>(c->ds.envAccel), want, hipMemcpyDeviceToHost));
+  return RT_OK;
+}
+
+int rt_get_environment_stats(rt_ctx* c, rt_environment_stats* out)
+{
+  if(!c || !out) return RT_ERR_INVALID_ARG;
+  *out = c->env.stats;
+  out->width = c->haveScene ? c->ds.envW : 0; out->height = c->haveScene ? c->ds.envH : 0;
+  out->deviceBytes = envDeviceBytes(c->env);
+  return RT_OK;
+}
+
+static bool envHostArgsOk(int width, int height, const void* rgba32f, const void* out)
+{
+  return rgba32f && out && width >= 1 && height >= 1 && uint64_t(width) * uint64_t(height) <= ENV_MAX_TEXELS;
+}
+int rt_env_accel(int width, int height, const float* rgba32f, rt_impt_samp* out, float* integral, float* average)
+{
+  if(!envHostArgsOk(width, height, rgba32f, out)) return RT_ERR_INVALID_ARG;
+  try {
+    EnvAccelResult r;
+    if(envAccelHost(width, height, rgba32f, out, r)) return RT_ERR_INVALID_ARG;
+    if(integral) *integral = r.integral;
+    if(average) *average = r.average;
+  } catch(...) { return RT_ERR_OOM; }
+  return RT_OK;
+}
+int rt_env_importance(int width, int height, const float* rgba32f, float* out)
+{
+  if(!envHostArgsOk(width, height, rgba32f, out)) return RT_ERR_INVALID_ARG;
+  try {
+    std::vector<rt_impt_samp> table(size_t(width) * size_t(height));
+    EnvAccelResult r;
+    if(envAccelHost(width, height, rgba32f, table.data(), r, out)) return RT_ERR_INVALID_ARG;
+  } catch(...) { return RT_ERR_OOM; }
   return RT_OK;
 }
 

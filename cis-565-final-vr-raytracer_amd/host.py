@@ -39,6 +39,7 @@ def host_lib():
             "rth_scene_emitter_meshes": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
             "rth_scene_stats": [C.c_void_p, C.c_void_p], "rth_scene_desc": [C.c_void_p, C.c_void_p, C.c_void_p],
             "rth_env_destroy": [C.c_void_p], "rth_env_load": [C.c_void_p, C.c_char_p], "rth_env_set": [C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+            "rth_env_adopt": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float], "rth_env_importance": [C.c_void_p, C.c_void_p],
             "rth_env_make_sky": [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint32], "rth_env_integral": [C.c_void_p], "rth_env_average": [C.c_void_p],
             "rth_env_width": [C.c_void_p], "rth_env_height": [C.c_void_p], "rth_env_get_accel": [C.c_void_p, C.c_void_p],
             "rth_default_state": [C.c_void_p], "rth_alias_table": [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -57,9 +58,22 @@ class HdrSampling:
             host_lib().rth_env_destroy(self._h); self._h = None
     def loadEnvironment(self, path):
         return host_lib().rth_env_load(self._h, path.encode()) == 0
-    def setEnvironment(self, rgba):
+    def setEnvironment(self, rgba, renderer=None):
+        """(h, w, 4) float32 texels.  With a renderer.Renderer: HdrSampling::setEnvironment over a context — the call forwards to rt_set_environment, the table is
+        built on the GPU, and getIntegral() / getAverage() / accel() afterwards are the device's (include/rt_abi.h "The environment")"""
         a = np.ascontiguousarray(rgba, dtype=np.float32)
-        host_lib().rth_env_set(self._h, a.ctypes.data, a.shape[1], a.shape[0])
+        if renderer is None:
+            host_lib().rth_env_set(self._h, a.ctypes.data, a.shape[1], a.shape[0])
+            return
+        renderer.set_environment(a)
+        st, table = renderer.environment_stats(), renderer.environment_readback(abi.ENV_ACCEL)
+        host_lib().rth_env_adopt(self._h, a.ctypes.data, a.shape[1], a.shape[0], table.ctypes.data, st.integral, st.average)
+    def importance(self):
+        """the importances createEnvironmentAccel builds its table from, (h, w) float32"""
+        w, h = self.size
+        out = np.zeros((h, w), dtype=np.float32)
+        host_lib().rth_env_importance(self._h, out.ctypes.data)
+        return out
     def makeSyntheticSky(self, w, h, sun_peak=5e4, seed=7):
         host_lib().rth_env_make_sky(self._h, w, h, sun_peak, seed)
     def getIntegral(self): return host_lib().rth_env_integral(self._h)
@@ -68,7 +82,7 @@ class HdrSampling:
     def size(self): return host_lib().rth_env_width(self._h), host_lib().rth_env_height(self._h)
     def accel(self):
         w, h = self.size
-        a = np.zeros(w * h, dtype=np.dtype([("alias", "<i4"), ("q", "<f4"), ("pdf", "<f4"), ("aliasPdf", "<f4")]))
+        a = np.zeros(w * h, dtype=abi.IMPT_SAMP_DT)
         host_lib().rth_env_get_accel(self._h, a.ctypes.data)
         return a
 

@@ -67,6 +67,34 @@ void HdrSampling::setEnvironment(const float* rgba, int w, int h)
   createEnvironmentAccel();
 }
 
+void HdrSampling::adoptEnvironment(const float* rgba, int w, int h, const rt_impt_samp* accel, float integral, float average)
+{
+  m_w = w; m_h = h;
+  m_pixels.assign(rgba, rgba + size_t(w) * h * 4);
+  m_accel.assign(accel, accel + size_t(w) * h);
+  m_integral = integral; m_average = average;
+}
+
+std::vector<float> HdrSampling::importance() const
+{
+  const uint32_t rx = uint32_t(m_w), ry = uint32_t(m_h);
+  std::vector<float> importance(size_t(rx) * ry);
+  float cosTheta0 = 1.0f;
+  const float stepPhi = float(2.0 * M_PI) / float(rx);
+  const float stepTheta = float(M_PI) / float(ry);
+  const float* px = m_pixels.data();
+  for(uint32_t y = 0; y < ry; ++y) {
+    const float cosTheta1 = std::cos(float(y + 1) * stepTheta);
+    const float area = (cosTheta0 - cosTheta1) * stepPhi;
+    cosTheta0 = cosTheta1;
+    for(uint32_t x = 0; x < rx; ++x) {
+      const size_t i = size_t(y) * rx + x;
+      importance[i] = area * std::max(px[i * 4], std::max(px[i * 4 + 1], px[i * 4 + 2]));
+    }
+  }
+  return importance;
+}
+
 void HdrSampling::makeSyntheticSky(int w, int h, float sunPeak, uint32_t seed)
 {
   std::vector<float> px(size_t(w) * h * 4);

@@ -14,6 +14,12 @@ class HdrSampling {
   bool loadEnvironment(const std::string& hdrImage);
   // same products from pixels already in memory (RGBA32F, w*h*4 floats)
   void setEnvironment(const float* rgba, int w, int h);
+  // the same pixels with products made elsewhere: the table, integral and average of rt_set_environment's device build (rt_environment_readback,
+  // rt_get_environment_stats) or of rt_env_accel (include/rt_abi.h "The environment"); AccelStructure::setEnvironment in renderer.hpp forwards to the device and
+  // ends here, so that getIntegral() / getAverage() / accel() describe the environment the context uses
+  void adoptEnvironment(const float* rgba, int w, int h, const rt_impt_samp* accel, float integral, float average);
+  // the importances createEnvironmentAccel feeds its table with (row area x max(r, g, b)), recomputed with its expressions
+  std::vector<float> importance() const;
   // procedural stand-in for the absent daytime.hdr: sky gradient + sun lobe
   void makeSyntheticSky(int w, int h, float sunPeak, uint32_t seed);
 

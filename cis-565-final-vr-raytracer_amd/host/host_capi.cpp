@@ -120,6 +120,11 @@ void* rth_env_create() { return new(std::nothrow) HdrSampling(); }
 void rth_env_destroy(void* e) { delete static_cast<HdrSampling*>(e); }
 int rth_env_load(void* e, const char* path) { RTH_GUARD(static_cast<HdrSampling*>(e)->loadEnvironment(path) ? 0 : -1); }
 void rth_env_set(void* e, const float* rgba, int w, int h) { static_cast<HdrSampling*>(e)->setEnvironment(rgba, w, h); }
+void rth_env_adopt(void* e, const float* rgba, int w, int h, const rt_impt_samp* accel, float integral, float average)
+{
+  static_cast<HdrSampling*>(e)->adoptEnvironment(rgba, w, h, accel, integral, average);
+}
+void rth_env_importance(void* e, float* out) { const std::vector<float> v = static_cast<HdrSampling*>(e)->importance(); memcpy(out, v.data(), v.size() * sizeof(float)); }
 void rth_env_make_sky(void* e, int w, int h, float sunPeak, uint32_t seed) { static_cast<HdrSampling*>(e)->makeSyntheticSky(w, h, sunPeak, seed); }
 float rth_env_integral(void* e) { return static_cast<HdrSampling*>(e)->getIntegral(); }
 float rth_env_average(void* e) { return static_cast<HdrSampling*>(e)->getAverage(); }

@@ -137,6 +137,24 @@ class AccelStructure {
     if(!scene.setTexture(texture, x, y, w, h, bgra, rowPitchBytes)) { fprintf(stderr, "AccelStructure::setTexture: the scene refused the rectangle\n"); return false; }
     return true;
   }
+  // Swap the environment without a new scene (include/rt_abi.h "The environment"): the device builds the importance table; the HdrSampling then adopts texels,
+  // table, integral and average, so that getIntegral() (rt_state.envMapLuminIntegInv = 1 / it) and getAverage() describe what the context uses.
+  bool setEnvironment(HdrSampling& env, const float* rgba, int w, int h)
+  {
+    if(rt_set_environment(m_ctx, w, h, rgba, nullptr) != RT_OK) { fprintf(stderr, "AccelStructure::setEnvironment: %s\n", rt_last_error(m_ctx)); return false; }
+    rt_environment_stats s{};
+    (void)rt_get_environment_stats(m_ctx, &s);
+    std::vector<rt_impt_samp> table(size_t(s.width) * size_t(s.height));
+    std::vector<float> texels(table.size() * 4);
+    if(rt_environment_readback(m_ctx, RT_ENV_ACCEL, table.data(), table.size() * sizeof(rt_impt_samp)) != RT_OK ||
+       rt_environment_readback(m_ctx, RT_ENV_TEXELS, texels.data(), texels.size() * sizeof(float)) != RT_OK) {
+      fprintf(stderr, "AccelStructure::setEnvironment: %s\n", rt_last_error(m_ctx));
+      return false;
+    }
+    env.adoptEnvironment(texels.data(), s.width, s.height, table.data(), s.integral, s.average);   // (the texels as stored: 1 x 1 black for an empty map)
+    return true;
+  }
+  rt_environment_stats environmentStats() const { rt_environment_stats s{}; (void)rt_get_environment_stats(m_ctx, &s); return s; }
   rt_material_stats materialStats() const { rt_material_stats s{}; (void)rt_get_material_stats(m_ctx, &s); return s; }
   rt_instances_stats instancesStats() const { rt_instances_stats s{}; (void)rt_get_instances_stats(m_ctx, &s); return s; }
   rt_rebuild_stats rebuildStats() const { rt_rebuild_stats s{}; (void)rt_get_rebuild_stats(m_ctx, &s); return s; }

@@ -28,7 +28,8 @@ ABI_SYMBOLS = ["rt_create", "rt_destroy", "rt_set_stream", "rt_upload_scene", "r
                "rt_update_vertices", "rt_set_skins", "rt_update_skins", "rt_vertices_readback", "rt_get_deform_stats",
                "rt_set_light_sources", "rt_lights_readback", "rt_get_light_stats", "rt_set_emitter_meshes", "rt_get_emitter_stats",
                "rt_set_morph_targets", "rt_update_morphs", "rt_get_morph_stats",
-               "rt_update_materials", "rt_update_texture", "rt_get_material_stats", "rt_opacity_map", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
+               "rt_update_materials", "rt_update_texture", "rt_get_material_stats", "rt_opacity_map",
+               "rt_set_environment", "rt_environment_readback", "rt_get_environment_stats", "rt_env_accel", "rt_env_importance", "rt_get_primary_replay_stats", "rt_primary_replay_readback",
                "rt_mgpu_create", "rt_mgpu_destroy", "rt_mgpu_upload_scene", "rt_mgpu_resize", "rt_mgpu_set_camera", "rt_mgpu_render_frame", "rt_mgpu_readback",
                "rt_mgpu_sync", "rt_mgpu_set_balance", "rt_mgpu_set_serialize", "rt_mgpu_set_pipeline", "rt_mgpu_set_gather", "rt_mgpu_set_solo", "rt_mgpu_set_bands", "rt_mgpu_get_stats", "rt_mgpu_get_link_stats", "rt_mgpu_get_stream_layout", "rt_mgpu_last_error", "rt_mgpu_plan_bands"]
 
@@ -171,6 +172,12 @@ def hip_lib():
             L.rt_update_texture.argtypes = [C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p, C.c_size_t]
             L.rt_get_material_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_opacity_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rt_set_environment"):   # the environment (absent from older A/B libraries)
+            L.rt_set_environment.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            L.rt_environment_readback.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+            L.rt_get_environment_stats.argtypes = [C.c_void_p, C.c_void_p]
+            L.rt_env_accel.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rt_env_importance.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "rt_get_primary_replay_stats"):   # settled primary visibility (absent from older A/B libraries)
             L.rt_get_primary_replay_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.rt_primary_replay_readback.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -663,6 +670,56 @@ class Renderer:
         if rc != 0:
             raise RtError(f"rt_opacity_map failed ({rc})")
         return np.array(list(out), dtype=np.uint32)
+
+    # ---- the environment (include/rt_abi.h "The environment")
+    def set_environment(self, rgba, accel=None):
+        """rt_set_environment: rgba = (h, w, 4) float32 texels (None: the 1 x 1 black map); accel = abi.IMPT_SAMP_DT rows to copy, or None: the table is built on
+        the GPU by the rule of csrc/env_accel.h.  Afterwards environment_stats().integral is what rt_state.envMapLuminIntegInv is the inverse of."""
+        if rgba is None:
+            self._chk(hip_lib().rt_set_environment(self._h, 0, 0, None, None), "rt_set_environment")
+            return
+        a = np.ascontiguousarray(rgba, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("set_environment: (h, w, 4) float32 texels")
+        t = None
+        if accel is not None:
+            t = np.ascontiguousarray(accel).view(np.uint8).reshape(-1)
+            if t.size != 16 * a.shape[0] * a.shape[1]:
+                raise ValueError("set_environment: 16 bytes of table per texel")
+        self._chk(hip_lib().rt_set_environment(self._h, a.shape[1], a.shape[0], a.ctypes.data, t.ctypes.data if t is not None else None), "rt_set_environment")
+
+    def environment_stats(self):
+        s = abi.EnvironmentStats()
+        self._chk(hip_lib().rt_get_environment_stats(self._h, C.byref(s)), "rt_get_environment_stats")
+        return s
+
+    def environment_readback(self, which):
+        """rt_environment_readback: abi.ENV_TEXELS -> (h, w, 4) float32, abi.ENV_ACCEL -> w h abi.IMPT_SAMP_DT rows, of the environment in use"""
+        st = self.environment_stats()
+        out = np.empty(st.width * st.height * 16, dtype=np.uint8)
+        self._chk(hip_lib().rt_environment_readback(self._h, int(which), out.ctypes.data, out.nbytes), "rt_environment_readback")
+        return out.view(np.float32).reshape(st.height, st.width, 4) if which == abi.ENV_TEXELS else out.view(abi.IMPT_SAMP_DT)
+
+    @staticmethod
+    def env_accel(rgba):
+        """rt_env_accel (no context, no GPU): (abi.IMPT_SAMP_DT rows, integral, average) of (h, w, 4) float32 texels, by the rule of csrc/env_accel.h"""
+        a = np.ascontiguousarray(rgba, dtype=np.float32)
+        out = np.zeros(a.shape[0] * a.shape[1], dtype=abi.IMPT_SAMP_DT)
+        integral, average = C.c_float(), C.c_float()
+        rc = hip_lib().rt_env_accel(a.shape[1], a.shape[0], a.ctypes.data, out.ctypes.data, C.byref(integral), C.byref(average))
+        if rc != 0:
+            raise RtError(f"rt_env_accel failed ({rc})")
+        return out, integral.value, average.value
+
+    @staticmethod
+    def env_importance(rgba):
+        """rt_env_importance (no context, no GPU): step 1 of the rule, (h, w) float32"""
+        a = np.ascontiguousarray(rgba, dtype=np.float32)
+        out = np.zeros(a.shape[:2], dtype=np.float32)
+        rc = hip_lib().rt_env_importance(a.shape[1], a.shape[0], a.ctypes.data, out.ctypes.data)
+        if rc != 0:
+            raise RtError(f"rt_env_importance failed ({rc})")
+        return out
 
     def primary_replay_stats(self):
         """rt_get_primary_replay_stats: state, K, the pixel classes of the recording in force and the launches recorded / replayed"""

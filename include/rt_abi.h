@@ -1251,6 +1251,54 @@ int rt_update_materials(rt_ctx* ctx, uint32_t count, const uint32_t* materialIds
 int rt_update_texture(rt_ctx* ctx, uint32_t texture, uint32_t x, uint32_t y, uint32_t w, uint32_t h, const uint8_t* bgra, size_t rowPitchBytes);
 int rt_get_material_stats(rt_ctx* ctx, rt_material_stats* out);
 int rt_opacity_map(const rt_opacity_map_desc* d, const uint8_t* bgra, uint32_t omm[4]);
+/* ------------------------------------------------------------------------------------------------------------------
+ * The environment (added within ABI 2.4, no version bump; csrc/env_accel.hip, csrc/env_accel.h).  The RGBA32F lat-long map and its importance table
+ * (one rt_impt_samp {alias, q, pdf, aliasPdf} per texel) used to enter through rt_upload_scene alone.  rt_set_environment replaces both without a new scene, and
+ * with accel == NULL it builds the table on the GPU by the rule csrc/env_accel.h states once for host and device: importance = row area x max(r, g, b) in fp32
+ * (NaN and negative texels count 0), quantised against the maximum to integers below 2^40, so that every sum is an integer sum and the table is the same bits
+ * whatever adds them up, in whatever order; an exact alias table from two 128-bit prefix sums (deficits of the below-average texels, excesses of the others, both
+ * in index order) and two binary searches, q a multiple of 2^-24 taken between two rounded marks of those sums, so that the probability of every texel is within
+ * 2^-24 / n of its share whatever the number of texels that alias to it; pdf = max(r, g, b) / integral.  rt_env_accel is the same rule on the host, word for word.  The table is NOT
+ * HdrSampling::createEnvironmentAccel's (a float sum and a sequential sweep whose result depends on the order); both are proper alias tables of the same
+ * importances, and a context given either renders what the oracle renders from that table.
+ *
+ * rt_set_environment(ctx, width, height, rgba32f, accel): valid after rt_upload_scene (RT_ERR_NO_SCENE otherwise).  width == 0, height == 0 or rgba32f == NULL:
+ *   the 1 x 1 black map of rt_upload_scene (accel is then not read).  accel != NULL: the table is checked as rt_upload_scene checks it (every alias inside the
+ *   table), then map and table are copied.  accel == NULL: the table is built on the device; width x height <= 2^23 (the rule's integer range).  The size may
+ *   differ from the current map's.  RT_ERR_INVALID_ARG, nothing changed, rt_last_error says why: a negative size; more than 2^23 texels with accel == NULL; an
+ *   alias outside the table; a texel with +inf in r, g or b, or finite texels whose importance or luminance overflows fp32 to +inf (found on the host for the
+ *   copy path, by the first kernel on the device path: the build runs in a staging pair of buffers, which replaces the pair in use only when the device's flag is
+ *   clear, as rt_update_skins stages its rows).  The context keeps two pairs (map + table) and builds into the one not in use, each sized by the largest map it has
+ *   held, plus the build's work arrays (28 B per texel): repeated calls at one size allocate nothing.  rt_upload_scene frees them.
+ *   Every accepted call joins the frames in flight, runs on the main stream and returns after its copies and kernels have completed; resets the reference-mode
+ *   sums; drops settled primary visibility (miss pixels carry the environment's radiance in the G-buffer).  It does not touch sun & sky: while rt_sun_and_sky
+ *   .in_use == 1 the map is stored and not seen.  Reservoirs and the SVGF / TAA / upsampling histories are left alone, as by the other edits; so are the tree and
+ *   the stream-priority decision.  The caller sets rt_state.envMapLuminIntegInv = 1 / integral (rt_get_environment_stats, or its own HdrSampling::getIntegral()
+ *   on the copy path), exactly as after rt_upload_scene.  A HIP error after the checks (RT_ERR_HIP) leaves the environment in use as it was.
+ * rt_environment_readback(ctx, which, dst, bytes): RT_ENV_TEXELS (16 B per texel) or RT_ENV_ACCEL (16 B per texel) of the environment in use; bytes must be
+ *   width x height x 16.  Drains the context.
+ * rt_get_environment_stats: the environment in use and what the last accepted rt_set_environment did.  integral, average, numSmall and numLarge are the device
+ *   build's (0 after a copy-path call or before any call: the caller's HdrSampling knows its own).
+ * rt_env_accel(width, height, rgba32f, out, integral, average): no context, no GPU; the rule on the host.  RT_ERR_INVALID_ARG for NULL rgba32f / out, a size
+ *   below 1, more than 2^23 texels, or a texel that refuses the map (out is then untouched).  integral / average may be NULL.  rt_env_importance: step 1 of the
+ *   rule alone, width x height floats (the same refusals).  Scope: the single-GPU context; rt_mgpu_* contexts and restir_amd/tiled.py upload a table of
+ *   rt_env_accel's through their scene description.
+ * ---------------------------------------------------------------------------------------------------------------- */
+enum { RT_ENV_TEXELS = 0, RT_ENV_ACCEL = 1 };
+typedef struct {
+  int32_t  width, height;      /* the environment in use */
+  float    integral;           /* sum of the importances (what HdrSampling::getIntegral() is to its own table) */
+  float    average;            /* mean luminance of the texels */
+  uint32_t numSmall, numLarge; /* texels below / not below the average importance */
+  uint32_t builtOnDevice;      /* 1: the table in use was built by the device */
+  float    ms;                 /* HIP-event time of the device work of the last accepted call (copies and kernels) */
+  uint64_t deviceBytes;        /* device memory the context holds for rt_set_environment (both pairs + work arrays) */
+} rt_environment_stats;        /* 40 B */
+int rt_set_environment(rt_ctx* ctx, int width, int height, const float* rgba32f, const rt_impt_samp* accel);
+int rt_environment_readback(rt_ctx* ctx, int which, void* dst, size_t bytes);
+int rt_get_environment_stats(rt_ctx* ctx, rt_environment_stats* out);
+int rt_env_accel(int width, int height, const float* rgba32f, rt_impt_samp* out, float* integral, float* average);
+int rt_env_importance(int width, int height, const float* rgba32f, float* out);
 /* ---- Settled primary visibility -------------------------------------------------------------------------------------------------------
  * While the launch camera (viewInverse, projInverse, size: bitwise) and the scene stay what they were, full-frame direct launches of the throughput build stop
  * tracing the primary ray: the third launch at a camera (RESTIR_VIS_REST_FRAMES at-rest launches, default and minimum 2) also RECORDS per pixel the leaf record of
@@ -1316,6 +1364,7 @@ static_assert(sizeof(rt_morph_delta) == 16, "rt_morph_delta");
 static_assert(sizeof(rt_morph_stats) == 32, "rt_morph_stats");
 static_assert(sizeof(rt_primary_replay_stats) == 32, "rt_primary_replay_stats");
 static_assert(sizeof(rt_opacity_map_desc) == 64 && sizeof(rt_material_stats) == 32, "rt_opacity_map_desc / rt_material_stats");
+static_assert(sizeof(rt_environment_stats) == 40, "rt_environment_stats");
 #endif
 
 #endif /* RT_ABI_H */
